@@ -24,6 +24,12 @@ torch.distributed (RCCL) is used only for the barrier and the max-over-ranks tim
 
 PyTorch is plumbing only (device memory, streams, graph capture, distributed); every kernel is launched through the C ABI of
 libsvtav1_hip.so (include/svt_hip.h).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the result line; nothing else.  `--full` adds
+everything else this script measures or checks, after the timed region: the parity spot check and the parity gate against the reference's kernels,
+the F = 1 / 4 / 8 sweep, the step without the restoration stages, the 1080p run, the configs[1] / [2] / [3] sub-lines, per-stage times and the
+roofline, the PCIe-inclusive rate and the CPU baseline (the --no-* options still leave single parts out).  `--dump-outputs DIR` writes what the last
+timed step computed (see dump_outputs) so that two builds can be compared output for output: the inputs depend only on the arguments.
 """
 import argparse
 import ctypes as C
@@ -312,7 +318,13 @@ def main():
                                                             "table, and a second stream per frame for the source side measured slower anyway, 8.60 vs 8.26 ms)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying one captured HIP graph per step")
     ap.add_argument("--stages", default="all", help="comma list (debug): " + ",".join(k for k, _ in ALL_STAGES))
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other measurement and check of this script (parity gate, sweeps, "
+                                                         "sub-lines, per-stage times, roofline, transfers, CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                                                                        "at most 64 MB: larger arrays as a fixed, seeded sample; DIR/manifest.json says which)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N without a launcher: spawn the N ranks here (one process per GPU, torch.distributed.run on 127.0.0.1) and relay rank 0's JSON line.
     # Under a launcher (WORLD_SIZE set) the two must agree: a silent 1-GPU measurement labelled N would be worse than no number.
@@ -350,7 +362,8 @@ def main():
     import txfm_common as tc
     E = Env()
     E.pkg = load_package()
-    orc = C.CDLL(os.path.join(ROOT, "oracle", "liboracle.so"))   # the checker: parity spot check and (port) CPU baseline only, after the timed region
+    # the checker: parity spot check and (port) CPU baseline only, after the timed region of a --full run
+    orc = C.CDLL(os.path.join(ROOT, "oracle", "liboracle.so")) if args.full else None
     E.ctx = E.pkg.Context(local_rank)
     E.L, E.mc, E.tc, E.workload = E.ctx.L, mc, tc, workload
     L, ctx = E.L, E.ctx
@@ -575,12 +588,16 @@ def main():
     per_rank_ms = [t / args.steps * 1e3 for t in shard.gather_floats(elapsed, dist if world > 1 else None, dev)]
     elapsed = shard.max_over_ranks(elapsed, dist if world > 1 else None, dev)   # ... the job's time is the slowest rank's
 
+    # what the timed steps computed, before anything below reuses the buffers: the frames of the last step's batch (steps rotate over the batches of make_steps)
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % len(step_fns)
+        dump_outputs(args.dump_outputs, pipes[last * nF:(last + 1) * nF], args)
     # what the TIMED replays left in frame 0's buffers (device -> host copies only; compared with the gated pass further down)
-    timed_final = final_outputs(pipes[0]) if rank == 0 else None
+    timed_final = final_outputs(pipes[0]) if rank == 0 and args.full else None
 
     # ---- the same step at other batch sizes (rank 0 reports; a few dozen steps each)
     sweep = {str(nF): {"ms_per_step": elapsed / args.steps * 1e3, "sb_per_s": nF * n_sb * args.steps / elapsed}}
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         for f in sweep_fs:
             if f == nF or f > len(pipes):
                 continue
@@ -594,7 +611,7 @@ def main():
     # ---- the step without the restoration stages = BASELINE.json configs[2] (ME + sub-pel + transform + deblock + CDEF on 4K 8-bit); the self-guided
     #      search and filter are configs[3]'s work, included in the headline step because the round-1 review asked for the complete search there
     subsets = {}
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         sub = [(k, n_) for k, n_ in stages if not k.startswith("sgr")]
         if 0 < len(sub) < len(stages):
             fns = make_steps(nF, sub)
@@ -605,11 +622,11 @@ def main():
 
     # ---- the same step on 1920x1080 frames (north_star: "synthetic 1080p / 4K 4:2:0"): a short second run of this script, rank 0 of a 1-GPU job only
     also_1080p = None
-    if world == 1 and not args.no_1080p and not args.no_sweep and (args.width, args.height) == (3840, 2160):
+    if args.full and world == 1 and not args.no_1080p and not args.no_sweep and (args.width, args.height) == (3840, 2160):
         import subprocess
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--width", "1920", "--height", "1080", "--frames", str(4 * nF), "--steps", "30", "--warmup", "3", "--no-sweep",
-                                "--no-transfers", "--no-cpu-baseline", "--no-1080p", "--no-variants"], capture_output=True, text=True, timeout=300)
+        try:   # --full: its per-stage times and parity checks, like the headline run's
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--width", "1920", "--height", "1080", "--frames", str(4 * nF), "--steps", "30", "--warmup", "3", "--full",
+                                "--no-sweep", "--no-transfers", "--no-cpu-baseline", "--no-1080p", "--no-variants"], capture_output=True, text=True, timeout=300)
             d2 = json.loads(r.stdout.strip().splitlines()[-1])
             also_1080p = {"value": d2["value"], "unit": d2["unit"], "ms_per_step": d2["ms_per_step"], "frames_per_step": 4 * nF, "workload": d2["config"]["workload"].split(";")[0],
                           "stages_ms": d2["config"]["stages_ms"]}
@@ -620,7 +637,7 @@ def main():
     #      configs[1] (1080p: ME with FULL / SUB_SAD search, transform chain 4..32 with quantize_b / quantize_fp at four q-indices) and configs[3] (4K 10-bit:
     #      HBD SAD / variance, the 64-point transform chain, the self-guided search and filter on 16-bit planes)
     also_10bit = config1_variants = config2_subpel = None
-    if world == 1 and not args.no_variants and not args.no_sweep and (args.width, args.height) == (3840, 2160):
+    if args.full and world == 1 and not args.no_variants and not args.no_sweep and (args.width, args.height) == (3840, 2160):
         import subprocess
         for which in ("10bit", "config1", "config2"):
             try:
@@ -638,7 +655,7 @@ def main():
     select_forms_ms = {}
     P0 = pipes[0]
     timing_list = list(stages) + ([("cdef_pick", "cdef_strength_select/steps_form")] if any(k == "cdef_pick" for k, _ in stages) and forced_form is None else [])
-    for k, name in timing_list:
+    for k, name in (timing_list if args.full else []):
         form = 0 if name.endswith("/steps_form") else select_form(1)
         if name.endswith("/steps_form"):
             ctx.check(L.svt_hip_set_cdef_select_form(ctx.h, 0))
@@ -670,7 +687,7 @@ def main():
     #      results (ME SAD / MV tables, CDEF distortion table, restoration search results, the restored picture) on a copy stream; uploads of batch
     #      i+1 and downloads of batch i-1 overlap the compute of batch i
     with_transfers = None
-    if not args.no_transfers and len(step_fns) >= 2:   # every rank at the same time when there are several: the host side (page-locked copies over PCIe) is what they share
+    if args.full and not args.no_transfers and len(step_fns) >= 2:   # every rank at the same time when there are several: the host side (page-locked copies over PCIe) is what they share
         def unpad(P):   # the un-padded views the transform / filter stages read: device-to-device, at the head of the frame's own chain (a kernel on the
             # copy stream would queue behind a whole step's launches: ROCm runs the streams on a few in-order hardware queues)
             P.d_cur[0].copy_(P.d_cur_p[P.F.pad:P.F.pad + P.F.h, P.F.pad:P.F.pad + P.F.w], non_blocking=True)
@@ -691,7 +708,7 @@ def main():
     # ---- parity spot check of what was just timed — the checker, not the product
     parity_ok = None
     F0 = frames[0]
-    if any(k == "me" for k, _ in stages):
+    if args.full and any(k == "me" for k, _ in stages):
         g_sad = P0.d_sad.cpu().numpy().view(np.uint32); g_mv = P0.d_mv.cpu().numpy().view(np.uint32)
         k8 = min(F0.sb_cols, 8)
         o_sad, o_mv = mc.oracle_frame(orc, F0.cur_y_p, F0.ref_y_p, F0.cur_y_p.shape[1], F0.pad, P0.sbs, 0, 0, k8)
@@ -707,7 +724,7 @@ def main():
             parity_ok = bool(parity_ok and np.array_equal(r_sad, g_sad) and np.array_equal(r_mv, g_mv))
     me_ok = parity_ok
     walk_stats = None
-    if any(k == "sgr_units" for k, _ in stages):   # diagnostics the search leaves at the start of its scratch: passes / points per walk, unfinished walks
+    if args.full and any(k == "sgr_units" for k, _ in stages):   # diagnostics the search leaves at the start of its scratch: passes / points per walk, unfinished walks
         st3 = [P0.d_scr[p][:128].cpu().numpy().view(np.uint32) for p in range(3)]
         nw = 16 * sum(P0.n_units)
         walk_stats = {"passes_per_walk": float(sum(int(s[0]) for s in st3)) / nw, "points_per_walk": float(sum(int(s[1]) for s in st3)) / nw,
@@ -745,21 +762,22 @@ def main():
 
     gate_detail = {}
     # ---- THE PARITY GATE: frame 0's chain once more, stage by stage, every stage's output against the reference's kernels run on the device's own
-    #      input of that stage (tools/parity_gate.py); the timed replays' final buffers must equal this pass's.  No number without it.
+    #      input of that stage (tools/parity_gate.py); the timed replays' final buffers must equal this pass's.  With --full, no number without it.
     gate = None
     full_chain = [k for k, _ in stages] == ["pyr", "hme", "me", "subpel", "enc_txfm", "dlf", "cdef_search", "cdef_pick", "cdef_apply", "sgr_units", "sgr_apply"]
-    if full_chain and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libsvtav1_ref_simd.so")):
+    if args.full and full_chain and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libsvtav1_ref_simd.so")):
         gate = run_parity_gate(E, P0, F0, stages, select_form, timed_final, orc, torch)
         gate_detail.update(gate["stages"])
         gate_detail["timed_step_outputs_equal_gated_pass"] = gate["timed_equal"]
         if gate["differences"]: gate_detail["gate_differences"] = gate["differences"]
         parity_ok = bool(parity_ok is not False and all(gate["stages"].values()) and gate["timed_equal"])
     else:
-        gate_detail["gate"] = "not run: " + ("a subset of the stages was selected" if not full_chain else "oracle/_ref/libsvtav1_ref_simd.so is not built")
+        gate_detail["gate"] = "not run: " + ("a plain run (--full runs the checks)" if not args.full else "a subset of the stages was selected" if not full_chain
+                                             else "oracle/_ref/libsvtav1_ref_simd.so is not built")
 
     # ---- CPU baseline: the reference's own kernels over the same job lists (or the oracle port), all hardware threads and one thread
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         stage_keys = [dict(key=k, name=n) for k, n in stages]
         CB0 = (E.pkg.ConvBlk * P0.nblk16).from_buffer_copy(P0.d_cb.cpu().numpy().tobytes())   # the job list the device built from frame 0's ME table
         jobs = dict(hme=P0.hme_host, conv=(CB0, P0.nblk16), unit=P0.US[0], cdef_mse=P0.d_mse.cpu().numpy().view(np.uint64), cdef_lambda=CDEF_LAMBDA,
@@ -778,7 +796,7 @@ def main():
     # parity ("bit-exact vs C ref"); the dispatched SIMD kernels are compared as well and reported
     parity_detail = {"me_85pu_vs_reference": me_ok, "sgr_walks_unfinished": None if walk_stats is None else walk_stats["unfinished"]}
     parity_detail.update(gate_detail)
-    if world == 1 and any(k == "cdef_pick" for k, _ in stages):
+    if args.full and world == 1 and any(k == "cdef_pick" for k, _ in stages):
         m = np.ascontiguousarray(P0.d_mse.cpu().numpy().view(np.uint64)).reshape(2, n_sb, 64)
         g_fin = P0.d_fin.cpu().numpy(); g_sel = P0.d_sel_gi.cpu().numpy()
         parity_detail["cdef_distortion_table_max"] = [int(m[0].max()), int(m[1].max())]
@@ -805,7 +823,7 @@ def main():
     out = {
         "metric": METRIC, "value": (nF * n_sb * args.steps * world / elapsed) if parity_ok is not False else None, "unit": "SB/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": bool(args.full),
         "launch": ("eager" if not use_graph else "hip_graph_replay") + f", {nF} frames per step, one forked stream per frame, "
                   f"steps rotate over {len(step_fns)} batches = {len(step_fns) * nF} distinct frames",
         "per_rank": {"ms_per_step": per_rank_ms, "sb_per_s_with_transfers": per_rank_with_transfers, "numa_node": per_rank_numa,
@@ -828,7 +846,7 @@ def main():
                    "me_waves_per_superblock": args.me_waves, "parity_spot_check": parity_ok, "parity_detail": parity_detail, "sgr_walk": walk_stats},
         "cpu_baseline": cpu,
     }
-    out["roofline"] = roofline(per_stage, stages, n_sb)
+    out["roofline"] = roofline(per_stage, stages, n_sb) if args.full else None   # built on the per-stage times of --full
     if isinstance(config2_subpel, dict) and "convolve_sr_16x16_blocks" in config2_subpel:   # the sub-line's kernels next to the step's stages (memory-bound: against HBM)
         for name, e in list(config2_subpel["convolve_sr_16x16_blocks"].items()) + [("upsampled_pred_variance_8_neighbours", config2_subpel["upsampled_pred_variance_8_neighbours"])]:
             out["roofline"]["stages"]["config2/" + name] = {k: e.get(k) for k in ("ms", "algorithmic_bytes", "algorithmic_GBps", "hbm_frac", "traffic_bytes")}
@@ -854,6 +872,55 @@ def final_outputs(P):
     return {"sad": P.d_sad.cpu().numpy().copy(), "mv": P.d_mv.cpu().numpy().copy(), "mse": P.d_mse.cpu().numpy().copy(), "sel": P.d_sel_gi.cpu().numpy().copy(),
             "ubest": [t.cpu().numpy().copy() for t in P.d_ubest], "ubx": [t.cpu().numpy().copy() for t in P.d_ubx], "rest": [_interior(P, P.b_rest, p) for p in range(3)],
             "cdef_border": [t.cpu().numpy().copy() for t in P.b_cdef]}
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy files that --dump-outputs may write
+
+
+def _exact_float(a):
+    """a as float32 when that holds every value exactly, else as float64 (the integers of these outputs all fit 53 bits)"""
+    f = a.astype(np.float32)
+    return f if np.array_equal(f.astype(a.dtype), a) else a.astype(np.float64)
+
+
+def dump_outputs(d, batch, args):
+    """--dump-outputs DIR: what the last timed step computed for each frame of its batch, i.e. what a caller of the step receives — the ME SAD / MV
+    tables, the CDEF distortion table, the frame's strength decision and every filter block's strengths, the restoration unit search's sets and xqd per
+    plane, the quantised coefficients and end-of-block positions of every transform block (job-list order), the restored picture — as
+    DIR/f<i>_<output>.npy (i = frame of the batch).  Values are stored as float32, or float64 where float32 would not hold them exactly.  If the whole
+    would exceed DUMP_LIMIT, every array above a common element count T (the largest power of two that fits) is replaced by T of its elements at
+    np.sort(np.random.default_rng(seed).choice(size, T, replace=False)) of the flattened array, seed = crc32 of the name: the same positions in every
+    run with the same arguments.  DIR/manifest.json lists shape, source dtype and sample of every array."""
+    import zlib
+    import torch
+    arrays = {}
+    for i, P in enumerate(batch):
+        fin = P.d_fin.cpu().numpy()
+        out = {"me_sad": P.d_sad, "me_mv": P.d_mv, "cdef_mse": P.d_mse, "cdef_block_strength_index": P.d_sel_gi, "cdef_strength_y": P.d_cy, "cdef_strength_uv": P.d_cuv,
+               "cdef_frame_decision": np.concatenate([fin[:4].view(np.int32), fin[8:40].view(np.int32), fin[40:72].view(np.int32)]),
+               "coeff": torch.cat([j["q"] for j in P.tx_jobs]), "eob": torch.cat([j["eob"] for j in P.tx_jobs])}
+        for p, pn in enumerate("yuv"):
+            out[f"sgr_set_{pn}"], out[f"sgr_xqd_{pn}"] = P.d_ubest[p], P.d_ubx[p]
+            out[f"restored_{pn}"] = _interior(P, P.b_rest, p)
+        for k, v in out.items():
+            arrays[f"f{i}_{k}"] = v if isinstance(v, np.ndarray) else v.cpu().numpy()
+    shapes = {k: (list(a.shape), str(a.dtype)) for k, a in arrays.items()}
+    arrays = {k: _exact_float(a) for k, a in arrays.items()}
+    T = 1 << 30
+    while sum(min(a.size, T) * a.itemsize + 256 for a in arrays.values()) > DUMP_LIMIT:   # + the .npy header
+        T //= 2
+    os.makedirs(d, exist_ok=True)
+    manifest = {"frames": [{"seed": P.F.seed, "width": P.F.w, "height": P.F.h} for P in batch], "steps": args.steps, "warmup": args.warmup, "arrays": {}}
+    for k, a in arrays.items():
+        sample = None
+        if a.size > T:
+            seed = zlib.crc32(k.encode())
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, T, replace=False))]
+            sample = {"count": T, "seed": seed}
+        np.save(os.path.join(d, k + ".npy"), a)
+        manifest["arrays"][k] = {"shape": shapes[k][0], "source_dtype": shapes[k][1], "saved_dtype": str(a.dtype), "sample": sample}
+    with open(os.path.join(d, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def run_parity_gate(E, P, F, stages, select_form, timed_final, orc, torch):
