@@ -951,6 +951,52 @@ int svt_hip_md_subpel_grid_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int
 int svt_hip_md_halfpel_grid_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus, const SvtHipMdPu *pus,
                                         int n_refs, const SvtHipMdRefPlane *refs, const uint32_t *d_mv, int bank, uint32_t *d_out);
 
+/* ------------------------------------------------------------------ intra prediction --------------------------------------------------------
+ * The AV1 luma intra predictors for a list of blocks in one launch: svt_aom_[highbd_]{dc,dc_left,dc_top,dc_128,v,h,smooth,smooth_v,smooth_h,paeth}_predictor_WxH_c
+ * (Common/Codec/EbIntraPrediction.c:863-968 and the size wrappers after them), dr_predictor / highbd_dr_predictor (:2260, :2374: zones 1 / 2 / 3, :246-345) and
+ * the edge conditioning build_intra_predictors / filter_intra_edge (:2545) do before them: filter_intra_edge_corner[_high] (:2288, :2427),
+ * svt_av1_filter_intra_edge[_high]_c (:88, :2403) and svt_av1_upsample_intra_edge[_high]_c (Common/C_DEFAULT/EbIntraPrediction_c.c:14-55).
+ *   d_edges : edge records, samples of pix_bytes each.  One record is what the reference keeps on its stack: 160 samples of "above" followed by 160 of "left"
+ *             (MAX_TX_SIZE * 2 + 32 each); element 16 of each is sample 0, element 15 the corner (sample -1).  A job names its record by the index of the record's
+ *             first sample (edge_off).  Records are read only: a job conditions a private copy, in the reference's order -- corner filter, edge filter of
+ *             "above", of "left", then up-sampling of "above", of "left" -- and predicts from that copy.
+ *   d_jobs  : device array.  Strengths and sample counts are the caller's (intra_edge_filter_strength / use_intra_edge_upsample and the n_px arithmetic of
+ *             build_intra_predictors are three-line functions of the block's position).  The filtered run of an edge is npx samples starting at sample -1
+ *             (start_m1 = 1, the corner itself passes through unfiltered as in the reference) or at sample 0; npx is clamped to 129, up_npx to 16.
+ *             A job whose tx_size (> 18), mode (> 12) or angle_delta (outside -3 .. 3) is out of range is skipped: nothing is written for it.
+ *   d_dst   : destination plane (pix_bytes per sample, stride in samples); a job writes its W x H block at (dst_x, dst_y).  Jobs must not overlap.
+ * pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10.  CfL, filter-intra, palette and intra block copy are not covered. */
+typedef struct {
+    uint32_t edge_off;            /* first sample of this job's edge record in d_edges */
+    int32_t  dst_x, dst_y;        /* top-left sample of the block in the destination plane */
+    uint8_t  tx_size;             /* TxSize 0..18: the block shape */
+    uint8_t  mode;                /* PredictionMode 0..12 (DC, V, H, D45, D135, D113, D157, D203, D67, SMOOTH, SMOOTH_V, SMOOTH_H, PAETH) */
+    int8_t   angle_delta;         /* -3..3 (x 3 degrees), directional modes only */
+    uint8_t  dc_have;             /* DC_PRED: bit 0 = left available, bit 1 = above available (dc_pred[left][above]) */
+    uint8_t  corner_filter;       /* 1: filter_intra_edge_corner before the edge filters */
+    uint8_t  strength_above, strength_left;   /* 0 = no edge filter, else 1..3 */
+    uint8_t  npx_above, npx_left; /* samples the edge filter is given (its sz), at most 129 */
+    uint8_t  start_m1;            /* 1: the filtered runs start at sample -1, else at sample 0 */
+    uint8_t  upsample_above, upsample_left;
+    uint8_t  up_npx_above, up_npx_left;       /* samples svt_av1_upsample_intra_edge is given (its sz), at most 16 */
+} SvtHipIntraJob;
+int svt_hip_intra_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_edges, const SvtHipIntraJob *d_jobs, int njobs, void *d_dst,
+                                    int dst_stride);
+/* open_loop_intra_search_mb (Encoder/Codec/EbMotionEstimation.c:3043-3155, called from the motion-estimation process when the look-ahead model is on) for every
+ * 16x16 macroblock of an 8-bit luma picture, one launch: neighbours from the SOURCE picture (update_neighbor_samples_array_open_loop_mb,
+ * Encoder/Codec/EbEncIntraPrediction.c:1201), for mode = DC_PRED .. mode_end the edges conditioned by filter_intra_edge (Common/Codec/EbIntraPrediction.c:2545), the
+ * prediction of intra_prediction_open_loop_mb (:2606), and the cost svt_aom_satd(svt_av1_wht_fwd_txfm(src - pred)) = the sum of the 256 absolute coefficients of
+ * the 16x16 DCT_DCT of the residual (Encoder/Codec/EbTransforms.c:3827).  The first mode with the smallest cost wins.
+ *   d_src    : sample (0, 0) of the picture; w, h multiples of 8 and at least 16; stride >= ceil16(w).  The plane must be readable over ceil16(w) x ceil16(h)
+ *              samples (a trailing 8-wide / 8-high macroblock is searched as a full 16x16 block over the picture's padding, as in the reference); nothing
+ *              outside that rectangle is read.
+ *   mode_end : 0 .. 12 (the reference uses 0, 8, 11, 12)
+ *   d_mode   : [mb_rows][mb_cols] OisMbResults.intra_mode, mb_cols = (w + 15) / 16, mb_rows = (h + 15) / 16, raster order
+ *   d_cost   : [mb_rows][mb_cols] OisMbResults.intra_cost.  It fits 32 bits with room: the coefficients are 8 x an orthonormal DCT of a residual within
+ *              +-255, so their absolute sum is below 16 * 8 * 255 * 16 < 2^20.
+ * Stream-ordered and asynchronous: no host synchronisation, no allocation. */
+int svt_hip_intra_ois_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int stride, int w, int h, int mode_end, uint8_t *d_mode, int32_t *d_cost);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -139,6 +139,17 @@ class DlfSearchPlane(C.Structure):
                 ("src_stride", C.c_int), ("d_edges_v", C.c_void_p), ("d_edges_h", C.c_void_p), ("units_w", C.c_int), ("units_h", C.c_int)]
 
 
+class IntraJob(C.Structure):
+    """SvtHipIntraJob (include/svt_hip.h)."""
+    _fields_ = [("edge_off", C.c_uint32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("tx_size", C.c_uint8), ("mode", C.c_uint8), ("angle_delta", C.c_int8),
+                ("dc_have", C.c_uint8), ("corner_filter", C.c_uint8), ("strength_above", C.c_uint8), ("strength_left", C.c_uint8), ("npx_above", C.c_uint8),
+                ("npx_left", C.c_uint8), ("start_m1", C.c_uint8), ("upsample_above", C.c_uint8), ("upsample_left", C.c_uint8), ("up_npx_above", C.c_uint8),
+                ("up_npx_left", C.c_uint8)]
+
+
+INTRA_EDGE_RECORD = 320   # samples of one edge record: 160 "above" + 160 "left", sample 0 at element 16 of each
+
+
 def tx_desc(x, y, tx_type):
     return (x & 0x3FFF) | ((y & 0x3FFF) << 14) | (tx_type << 28)
 
@@ -287,6 +298,8 @@ def lib():
     L.svt_hip_setup_rtcd.argtypes = [vp, vp]
     L.svt_hip_cdef_search_frame_dev.argtypes = [vp, i32, P3, I3, P3, I3, i32, i32, vp, i32, i32, vp, vp, vp]
     L.svt_hip_cdef_apply_frame_dev.argtypes = [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]
+    L.svt_hip_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
+    L.svt_hip_intra_ois_picture_dev.argtypes = [vp, u8p, i32, i32, i32, i32, u8p, vp]
     _lib = L
     return L
 
@@ -330,6 +343,36 @@ class Context:
     def free(self, *ptrs):
         for p in ptrs:
             self.L.svt_hip_free(self.h, p)
+
+    # ---- intra prediction
+    def intra_ois_picture(self, d_src, stride, w, h, mode_end=12):
+        """svt_hip_intra_ois_picture_dev on a resident 8-bit luma plane -> (mode [mb_rows][mb_cols] uint8, cost [mb_rows][mb_cols] int32) on the host."""
+        import numpy as np
+        mbw, mbh = (w + 15) // 16, (h + 15) // 16
+        d_mode, d_cost = self.empty(mbw * mbh), self.empty(mbw * mbh * 4)
+        try:
+            self.check(self.L.svt_hip_intra_ois_picture_dev(self.h, d_src, stride, w, h, mode_end, d_mode, d_cost), "intra_ois_picture")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_mode, (mbh, mbw), np.uint8), self.to_host(d_cost, (mbh, mbw), np.int32)
+        finally:
+            self.free(d_mode, d_cost)
+
+    def intra_predict_batch(self, edges, jobs, dst):
+        """svt_hip_intra_predict_batch_dev: `edges` a uint8 / uint16 array of edge records, `jobs` a ctypes array of IntraJob, `dst` the 2-D destination plane
+        (same dtype) the blocks are written into; `bd` follows the dtype's use (8 for uint8, 10 for uint16).  Returns the plane after the launch."""
+        import numpy as np
+        pix_bytes = edges.dtype.itemsize
+        assert dst.dtype == edges.dtype and dst.ndim == 2
+        d_e, d_j, d_d = self.to_device(edges), self.empty(max(C.sizeof(jobs), 4)), self.to_device(dst)
+        try:
+            if len(jobs):
+                self.check(self.L.svt_hip_memcpy_h2d(self.h, d_j, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
+            self.check(self.L.svt_hip_intra_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, d_e, d_j, len(jobs), d_d, dst.shape[1]),
+                       "intra_predict_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_d, dst.shape, dst.dtype)
+        finally:
+            self.free(d_e, d_j, d_d)
 
     def close(self):
         if self.h:

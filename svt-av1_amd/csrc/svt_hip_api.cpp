@@ -239,7 +239,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(intra) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -266,6 +266,33 @@ int svt_hip_timer_stop_ms(SvtHipCtx* c, float* ms) {
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));
     HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    return SVT_HIP_OK;
+}
+
+/* ---------------------------------------------------------------------------------------- intra */
+int svt_hip_intra_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_edges, const SvtHipIntraJob* d_jobs, int njobs, void* d_dst,
+                                    int dst_stride) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_edges || !d_jobs || !d_dst || njobs < 0 || (pix_bytes != 1 && pix_bytes != 2) || (bd != 8 && bd != 10) || (pix_bytes == 1 && bd != 8) ||
+        dst_stride <= 0) {
+        if (c) c->err = "svt_hip_intra_predict_batch_dev: bad argument";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (!njobs) return SVT_HIP_OK;
+    hipError_t e = (hipError_t)svt_hip_launch_intra_predict(c->stream, pix_bytes, bd, d_edges, d_jobs, njobs, d_dst, dst_stride);
+    if (e != hipSuccess) return fail(c, e, "intra predict launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_intra_ois_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int stride, int w, int h, int mode_end, uint8_t* d_mode, int32_t* d_cost) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_src || !d_mode || !d_cost || w < 16 || h < 16 || (w & 7) || (h & 7) || w > 65536 || h > 65536 || stride < ((w + 15) & ~15) || mode_end < 0 ||
+        mode_end > 12) {
+        if (c) c->err = "svt_hip_intra_ois_picture_dev: bad argument (w, h multiples of 8 and >= 16, stride >= ceil16(w), mode_end 0..12)";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    hipError_t e = (hipError_t)svt_hip_launch_intra_ois(c->stream, d_src, stride, w, h, mode_end, d_mode, d_cost);
+    if (e != hipSuccess) return fail(c, e, "intra ois launch");
     return SVT_HIP_OK;
 }
 
