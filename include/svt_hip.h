@@ -997,6 +997,63 @@ int svt_hip_intra_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const
  * Stream-ordered and asynchronous: no host synchronisation, no allocation. */
 int svt_hip_intra_ois_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int stride, int w, int h, int mode_end, uint8_t *d_mode, int32_t *d_cost);
 
+/* ------------------------------------------------------------------ TPL flow dispenser ------------------------------------------------------
+ * tpl_mc_flow_dispenser (Encoder/Codec/EbRateControlProcess.c:344-816) for one picture of the look-ahead window: for every 16x16 macroblock the inter cost
+ * (SATD of the 16x16 DCT_DCT of source - reference SOURCE at the ME vector) of every valid reference slot, the decision against the open-loop intra cost,
+ * svt_av1_quantize_fp + svt_av1_block_error + rate_estimator of the winning residual, the reconstruction (copy from the reference's reconstruction, or intra
+ * prediction from this picture's reconstruction, plus the inverse transform of the quantised residual), the second set of costs against that reconstruction,
+ * what result_model_store writes, and generate_padding of the reconstruction.  Inter macroblocks depend on no other macroblock of the picture and run in one
+ * launch; intra macroblocks read their left / above / above-left neighbours (and in column 0 the above-right one) and run in steps x + 2y, one launch per step.
+ *   refs[r]    : slot r = rf_idx of the reference's loop (0..3 list 0, 4..6 list 1); d_src == NULL = slot unused (tpl_ref0_count / tpl_ref1_count)
+ *   d_mv       : [7][n_mb] the ME vector of the macroblock's 16x16 PU per slot, (y_mv << 16) | (x_mv & 0xffff) in quarter samples as the ME kernels write it;
+ *                the block offset is (int16_t)(x_mv << 1) >> 3.  Only the rows of used slots are read.  n_mb = mb_cols * mb_rows, raster order.
+ *   d_ref_mask : [n_mb] bit r = is_me_data_valid for slot r.  d_mv and d_ref_mask may be NULL only when no slot is used.
+ *   d_ois_mode / d_ois_cost : the outputs of svt_hip_intra_ois_picture_dev on d_cur (may be NULL when use_ois == 0); a mode above 12 is treated as DC_PRED
+ *   d_cur      : sample (0,0) of the source luma, readable over ceil16(w) x ceil16(h)
+ *   d_recon    : sample (0,0) of this picture's TPL reconstruction: ceil16(w) x ceil16(h) is written, then the `pad` border around w x h is replicated.
+ *                Must not alias any d_rec.  Nothing outside (w + 2 pad) x (h + 2 pad) is written.
+ *   d_stats    : [n_mb]
+ *   d_scratch  : svt_hip_tpl_dispenser_scratch_bytes(w, h) bytes
+ * A block an MV would move outside the padded reference is clamped to [-pad, w + pad - 16] x [-pad, h + pad - 16] (the reference has no defined result there).
+ * 8-bit only (the reference runs TPL on the 8-bit pictures at every encoder bit depth).  Stream-ordered and asynchronous: no host synchronisation, no
+ * allocation, no read-back. */
+typedef struct {
+    const uint8_t *d_src;     /* sample (0,0) of this reference's SOURCE luma: read by the cost search */
+    const uint8_t *d_rec;     /* sample (0,0) of the picture the reconstruction copies from: that frame's TPL reconstruction when it is inside the sliding
+                                 window, else the same pointer as d_src */
+    int32_t src_stride, rec_stride;
+} SvtHipTplRef;
+
+typedef struct {
+    int32_t w, h;             /* luma size: multiples of 8, >= 16 */
+    int32_t pad;              /* valid border, in samples, around every reference plane and around d_recon (which receives it); >= 16 */
+    SvtHipQuantParams q;      /* variant 2, log_scale 0: round = y_round_fp, quant = y_quant_fp, dequant = y_dequant_qtx of the picture's qindex */
+    uint8_t use_ois;          /* 1 = intra mode / cost from d_ois_*; 0 = DC_PRED with cost INT64_MAX */
+    uint8_t add_residual;     /* 1 = inverse transform added where eob != 0 */
+    uint8_t rate;             /* !tpl_opt_flag: 0 = both rates are 0 */
+    uint8_t best_ref_only;    /* tpl_ctrls.get_best_ref: only the valid slot with the smallest 16x16 SAD is evaluated (get_best_reference) */
+} SvtHipTplParams;
+
+typedef struct {              /* what result_model_store writes for the macroblock: already divided by 16 and clamped to >= 1 */
+    int64_t srcrf_dist, recrf_dist, srcrf_rate, recrf_rate;
+    int16_t mv_row, mv_col;   /* TplStats.mv of the best reference (y_mv << 1, x_mv << 1), 0 when rf_idx == -1 */
+    int8_t  rf_idx;           /* best_rf_idx, -1 when no reference was evaluated (also set when intra won) */
+    uint8_t is_inter;         /* best_mode == NEWMV */
+    uint8_t mode;             /* the intra mode used when !is_inter */
+    uint8_t pad0;
+    uint16_t eob;             /* of the final (reconstruction) pass */
+    uint16_t pad1;
+} SvtHipTplMbStats;
+
+size_t svt_hip_tpl_dispenser_scratch_bytes(int w, int h);
+int svt_hip_tpl_dispenser_picture_dev(SvtHipCtx *ctx, const SvtHipTplParams *p, const uint8_t *d_cur, int cur_stride,
+                                      const SvtHipTplRef refs[7], const uint32_t *d_mv, const uint8_t *d_ref_mask,
+                                      const uint8_t *d_ois_mode, const int32_t *d_ois_cost,
+                                      uint8_t *d_recon, int recon_stride, SvtHipTplMbStats *d_stats, void *d_scratch);
+/* Measurement only (tools/tpl_time.py): which parts svt_hip_tpl_dispenser_picture_dev launches, bit 0 = phase A (inter search, decisions, inter macroblocks),
+ * bit 1 = phase B (the intra steps), bit 2 = the padding.  The default, 7, is the only value that computes the dispenser. */
+int svt_hip_tpl_set_phases(SvtHipCtx *ctx, int mask);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -147,6 +147,36 @@ class IntraJob(C.Structure):
                 ("up_npx_left", C.c_uint8)]
 
 
+class TplRef(C.Structure):
+    """SvtHipTplRef (include/svt_hip.h): device pointers to sample (0, 0)."""
+    _fields_ = [("d_src", C.c_void_p), ("d_rec", C.c_void_p), ("src_stride", C.c_int32), ("rec_stride", C.c_int32)]
+
+
+class TplParams(C.Structure):
+    """SvtHipTplParams (include/svt_hip.h)."""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("pad", C.c_int32), ("q", QuantParams), ("use_ois", C.c_uint8), ("add_residual", C.c_uint8),
+                ("rate", C.c_uint8), ("best_ref_only", C.c_uint8)]
+
+
+class TplMbStats(C.Structure):
+    """SvtHipTplMbStats (include/svt_hip.h)."""
+    _fields_ = [("srcrf_dist", C.c_int64), ("recrf_dist", C.c_int64), ("srcrf_rate", C.c_int64), ("recrf_rate", C.c_int64), ("mv_row", C.c_int16),
+                ("mv_col", C.c_int16), ("rf_idx", C.c_int8), ("is_inter", C.c_uint8), ("mode", C.c_uint8), ("pad0", C.c_uint8), ("eob", C.c_uint16),
+                ("pad1", C.c_uint16)]
+
+
+TPL_MAX_REFS = 7   # MAX_PA_ME_MV: slots 0..3 list 0, 4..6 list 1
+
+
+def tpl_stats_grid(stats, is_720p_or_larger):
+    """result_model_store's replication (EbRateControlProcess.c:148-161): the per-macroblock records `stats` ([mb_rows][mb_cols] structured array) spread over
+    the picture's tpl_stats grid: one cell per 16x16 samples at 720p and above (the array as it is), one per 8x8 below (every record in a 2x2 square), i.e.
+    [rows][aligned16_width >> shift] with shift = 3 + is_720p_or_larger."""
+    import numpy as np
+    rep = 1 if is_720p_or_larger else 2
+    return np.repeat(np.repeat(stats, rep, axis=0), rep, axis=1)
+
+
 INTRA_EDGE_RECORD = 320   # samples of one edge record: 160 "above" + 160 "left", sample 0 at element 16 of each
 
 
@@ -300,6 +330,10 @@ def lib():
     L.svt_hip_cdef_apply_frame_dev.argtypes = [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]
     L.svt_hip_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
     L.svt_hip_intra_ois_picture_dev.argtypes = [vp, u8p, i32, i32, i32, i32, u8p, vp]
+    L.svt_hip_tpl_dispenser_scratch_bytes.argtypes = [i32, i32]
+    L.svt_hip_tpl_dispenser_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_tpl_set_phases.argtypes = [vp, i32]
+    L.svt_hip_tpl_dispenser_picture_dev.argtypes = [vp, C.POINTER(TplParams), u8p, i32, C.POINTER(TplRef), vp, u8p, u8p, vp, u8p, i32, vp, vp]
     _lib = L
     return L
 
@@ -373,6 +407,34 @@ class Context:
             return self.to_host(d_d, dst.shape, dst.dtype)
         finally:
             self.free(d_e, d_j, d_d)
+
+    # ---- TPL flow dispenser
+    def tpl_dispenser_picture(self, params, d_cur, cur_stride, refs, d_mv, d_ref_mask, d_ois_mode, d_ois_cost, d_recon, recon_stride):
+        """svt_hip_tpl_dispenser_picture_dev on resident planes and tables: `params` a TplParams, `refs` a sequence of up to 7 TplRef (missing slots unused).
+        The reconstruction (border included) stays on the device at d_recon; returns the statistics as a structured numpy array [mb_rows][mb_cols] whose
+        fields are TplMbStats'."""
+        import numpy as np
+        mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
+        arr = (TplRef * TPL_MAX_REFS)()
+        for i, r in enumerate(refs):
+            arr[i] = r
+        d_stats = self.empty(mbw * mbh * C.sizeof(TplMbStats))
+        d_scratch = self.empty(self.L.svt_hip_tpl_dispenser_scratch_bytes(params.w, params.h))
+        try:
+            self.check(self.L.svt_hip_tpl_dispenser_picture_dev(self.h, C.byref(params), d_cur, cur_stride, arr, d_mv, d_ref_mask, d_ois_mode, d_ois_cost,
+                                                                 d_recon, recon_stride, d_stats, d_scratch), "tpl_dispenser_picture")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_stats, (mbh, mbw), np.dtype(TplMbStats))
+        finally:
+            self.free(d_stats, d_scratch)
+
+    def tpl_recon_to_host(self, d_recon, recon_stride, w, h, pad):
+        """The padded reconstruction tpl_dispenser_picture left at d_recon (sample (0, 0)): [h + 2 pad][w + 2 pad] uint8."""
+        import numpy as np
+        out = np.empty((h + 2 * pad, w + 2 * pad), np.uint8)
+        top_left = C.c_void_p(d_recon.value - pad * recon_stride - pad)
+        self.check(self.L.svt_hip_memcpy2d_d2h(self.h, out.ctypes.data_as(C.c_void_p), out.shape[1], top_left, recon_stride, out.shape[1], out.shape[0]), "d2h 2d")
+        return out
 
     def close(self):
         if self.h:

@@ -63,6 +63,37 @@ template <typename F> IPD int edge_upsample_at(F p, int sz, int idx, int bd) {
     return clip_px((s + 8) >> 4, bd);
 }
 
+// ------------------------------------------------------------------------------------------------ open-loop macroblock neighbours
+// Sample `idx` (-1 .. 31) of the above (which = 0) or left (which = 1) edge of the macroblock at (x, y): update_neighbor_samples_array_open_loop_mb in
+// closed form, every quirk kept (EbEncIntraPrediction.c:1201-1280); update_neighbor_samples_array_open_loop_mb_recon (:1282) is the same body on a
+// reconstruction plane (tpl.hip).  Reads nothing left of column 0, above row 0, right of column w - 1 or below row h - 1.
+IPD int ois_neighbor(const uint8_t* __restrict__ src, int stride, int w, int h, int x, int y, int which, int idx) {
+    const int cnt_l = min(32, h - y), cnt_a = min(32, w - x);
+    const ptrdiff_t st = stride;
+    const uint8_t* p = src + (ptrdiff_t)y * st + x;
+    // the left column as the x != 0 branch leaves it: rows beyond the picture keep the 129 fill, the lower half repeats sample 15
+    auto left_col = [&](int i) -> int { i = min(i, 15); return i < cnt_l ? (int)p[i * st - 1] : 129; };
+    if (x != 0 && y != 0) {
+        if (idx < 0) return p[-st - 1];
+        if (which) return left_col(idx);
+        const int i = min(idx, 15);   // the unknown top-right half repeats sample 15
+        return i < cnt_a ? (int)p[i - st] : 127;
+    }
+    if (x != 0) {   // y == 0: the above row (corner included) is one replicated sample of the left column
+        if (which) return idx < 0 ? (int)p[-1] : left_col(idx);
+        return idx < cnt_a ? left_col(32 - cnt_a) : 127;
+    }
+    if (y != 0) {   // x == 0: the left column (corner included) is the sample above the block, the above row is read over its clipped length
+        const int v = p[-st];
+        if (which) return idx < cnt_l ? v : 129;
+        return idx < 0 ? v : (idx < cnt_a ? (int)p[idx - st] : 127);
+    }
+    return idx < 0 ? 128 : (which ? 129 : 127);
+}
+
+// intra_edge_filter_strength(16, 16, delta, 0): block width + height = 32
+IPD int ois_strength(int delta) { const int d = abs(delta); return d >= 32 ? 3 : (d >= 4 ? 2 : (d >= 1 ? 1 : 0)); }
+
 // ------------------------------------------------------------------------------------------------ predictors
 // What one block's prediction needs besides the edges; uniform over the block.
 struct PredParams {

@@ -19,6 +19,7 @@ struct SvtHipCtx {
     hipEvent_t  ev0 = nullptr, ev1 = nullptr;
     int         select_form = -1;   // svt_hip_set_cdef_select_form
     hipEvent_t  ev_sel_in = nullptr, ev_sel_out = nullptr;   // hand-over to and from the device's selection stream (svt_hip_cdef_strength_select_dev)
+    int         tpl_phases = 7;     // svt_hip_tpl_set_phases
     int         me_waves = 4;   // 256 threads per SB: measured best on MI355X (tools/me_time.py)
     int         me_big = 1;     // also launch the strip-walking instance for search areas above 65 536 candidates
     void*       scratch = nullptr;   // library-owned device scratch (16-bit Wiener statistics, self-guided unit search), grown on demand
@@ -240,7 +241,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     return SVT_HIP_OK;
 }
 #define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(intra) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
-    X(tfilter) X(txfm2d) X(warp) X(wiener)
+    X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
 #undef X
@@ -293,6 +294,43 @@ int svt_hip_intra_ois_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int stride
     }
     hipError_t e = (hipError_t)svt_hip_launch_intra_ois(c->stream, d_src, stride, w, h, mode_end, d_mode, d_cost);
     if (e != hipSuccess) return fail(c, e, "intra ois launch");
+    return SVT_HIP_OK;
+}
+
+/* ---------------------------------------------------------------------------------- TPL dispenser */
+/* one decision byte per macroblock (phase A -> the step launches), rounded up to a cache line */
+size_t svt_hip_tpl_dispenser_scratch_bytes(int w, int h) {
+    if (w <= 0 || h <= 0) return 256;
+    return (((size_t)((w + 15) / 16) * (size_t)((h + 15) / 16) + 255) & ~(size_t)255) + 256;
+}
+
+int svt_hip_tpl_dispenser_picture_dev(SvtHipCtx* c, const SvtHipTplParams* p, const uint8_t* d_cur, int cur_stride, const SvtHipTplRef refs[7],
+                                      const uint32_t* d_mv, const uint8_t* d_ref_mask, const uint8_t* d_ois_mode, const int32_t* d_ois_cost, uint8_t* d_recon,
+                                      int recon_stride, SvtHipTplMbStats* d_stats, void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    bool bad = !c || !p || !d_cur || !refs || !d_recon || !d_stats || !d_scratch;
+    if (!bad) {
+        const int w16 = (p->w + 15) & ~15;
+        bad = p->w < 16 || p->h < 16 || (p->w & 7) || (p->h & 7) || p->w > 65536 || p->h > 65536 || p->pad < 16 || p->pad > 65536 || cur_stride < w16 ||
+              recon_stride < w16 || p->q.variant != 2 || p->q.log_scale != 0 || (p->use_ois && (!d_ois_mode || !d_ois_cost));
+        for (int r = 0; r < 7 && !bad; r++)
+            if (refs[r].d_src) bad = !refs[r].d_rec || refs[r].d_rec == d_recon || refs[r].src_stride < w16 || refs[r].rec_stride < w16 || !d_mv || !d_ref_mask;
+    }
+    if (bad) {
+        if (c) c->err = "svt_hip_tpl_dispenser_picture_dev: bad argument (w, h multiples of 8 and >= 16, strides >= ceil16(w), pad >= 16, q.variant 2, q.log_scale 0)";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    hipError_t e = (hipError_t)svt_hip_launch_tpl_dispenser(c->stream, p, d_cur, cur_stride, refs, d_mv, d_ref_mask, d_ois_mode, d_ois_cost, d_recon, recon_stride,
+                                                            d_stats, (uint8_t*)d_scratch, c->tpl_phases);
+    if (e != hipSuccess) return fail(c, e, "tpl dispenser launch");
+    if (c->tpl_phases & 4) e = (hipError_t)svt_hip_launch_generate_padding(c->stream, d_recon, 1, recon_stride, p->w, p->h, p->pad, p->pad);
+    if (e != hipSuccess) return fail(c, e, "tpl dispenser padding launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_tpl_set_phases(SvtHipCtx* c, int mask) {
+    if (!c || mask < 0 || mask > 7) return SVT_HIP_ERR_BAD_ARG;
+    c->tpl_phases = mask;
     return SVT_HIP_OK;
 }
 

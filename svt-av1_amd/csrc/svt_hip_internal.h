@@ -147,6 +147,10 @@ int svt_hip_launch_sgr_apply(hipStream_t st, int pix_bytes, int bd, const void* 
 /* intra.hip */
 int svt_hip_launch_intra_ois(hipStream_t st, const uint8_t* src, int stride, int w, int h, int mode_end, uint8_t* mode, int32_t* cost);
 int svt_hip_launch_intra_predict(hipStream_t st, int pix_bytes, int bd, const void* edges, const SvtHipIntraJob* jobs, int njobs, void* dst, int dst_stride);
+/* tpl.hip */
+int svt_hip_launch_tpl_dispenser(hipStream_t st, const SvtHipTplParams* p, const uint8_t* cur, int cur_stride, const SvtHipTplRef* refs, const uint32_t* mv,
+                                 const uint8_t* ref_mask, const uint8_t* ois_mode, const int32_t* ois_cost, uint8_t* recon, int recon_stride,
+                                 SvtHipTplMbStats* stats, uint8_t* decision, int phases);
 /* per-call forms (percall.hip, cdef.hip, deblock.hip) */
 int svt_hip_launch_quantize_blocks(hipStream_t st, const int32_t* coeff, int n, int nblk, const SvtHipQuantParams* qp, const int16_t* iscan, int32_t* qcoeff,
                                    int32_t* dqcoeff, uint16_t* eob);
