@@ -327,7 +327,7 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
 }
 
 // ------------------------------------------------------------------------------- search, luma ---
-template <typename PIX, bool DEDUPE_OFF = false>
+template <typename PIX>
 __global__ void __launch_bounds__(256)
 cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* __restrict__ src, int src_stride, int w, int h,
                         const uint8_t* __restrict__ skip8, int pri_damping, int cs, uint64_t* __restrict__ mse,
@@ -372,7 +372,7 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
         int first = 0;
 #pragma unroll
         for (int pi = 0; pi < 16; pi++) {
-            const bool fresh = DEDUPE_OFF || pi <= 1 || t_of[pi] != t_of[pi - 1];   // index 0 filters along direction 0 (EbCdef.c:371 `t ? dir : 0` tests the frame-header strength): it never shares a row, even when index 1 is adjusted to 0
+            const bool fresh = pi <= 1 || t_of[pi] != t_of[pi - 1];   // index 0 filters along direction 0 (EbCdef.c:371 `t ? dir : 0` tests the frame-header strength): it never shares a row, even when index 1 is adjusted to 0
             if (fresh) {
                 first = pi;
 #pragma unroll
@@ -547,13 +547,8 @@ template <typename PIX>
 int search_t(hipStream_t st, const void* const rec[3], const int rs[3], const void* const src[3], const int ss[3], int w, int h,
              const uint8_t* skip8, int pri_damping, int cs, uint64_t* mse, uint8_t* dir_buf, int32_t* var_buf) {
     const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
-    static const bool dedupe_off = getenv("SVT_HIP_CDEF_DEDUPE") && !atoi(getenv("SVT_HIP_CDEF_DEDUPE"));   // A/B: every primary index combined and stored (round 3)
-    if (dedupe_off)
-        hipLaunchKernelGGL((cdef_search_luma_kernel<PIX, true>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rs[0], (const PIX*)src[0], ss[0], w, h,
-                           skip8, pri_damping, cs, mse, dir_buf, var_buf);
-    else
-        hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rs[0], (const PIX*)src[0], ss[0], w, h,
-                           skip8, pri_damping, cs, mse, dir_buf, var_buf);
+    hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rs[0], (const PIX*)src[0], ss[0], w, h,
+                       skip8, pri_damping, cs, mse, dir_buf, var_buf);
     hipLaunchKernelGGL((cdef_search_chroma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[1], (const PIX*)rec[2], rs[1],
                        (const PIX*)src[1], (const PIX*)src[2], ss[1], w, h, skip8, pri_damping, cs, mse + (size_t)nfb * 64, dir_buf);
     return (int)hipGetLastError();

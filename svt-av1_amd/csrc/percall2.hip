@@ -1035,9 +1035,7 @@ extern "C" int svt_hip_launch_strength_select_multi(hipStream_t st, int n_pics, 
     }
     const char* early_env = getenv("SVT_HIP_CDEF_SELECT_EARLY");   // read per call: 0 = every chain runs its 5 nb steps (the reference's loop as written); tests compare both
     const int early = !(early_env && !atoi(early_env));
-    static int forced = -1;   // debug: SVT_HIP_CDEF_SELECT_SLICES
-    if (forced < 0) { const char* e = getenv("SVT_HIP_CDEF_SELECT_SLICES"); forced = e ? atoi(e) : 0; }
-    int slices = forced > 0 ? forced : (sb_count + 31) / 32;
+    int slices = (sb_count + 31) / 32;
     slices = slices < 1 ? 1 : (slices > kJointMaxSlices ? kJointMaxSlices : slices);
     for (int p0 = 0; p0 < n_pics; p0 += kJointMaxPics) {
         const int np = min(kJointMaxPics, n_pics - p0);
@@ -1060,9 +1058,6 @@ extern "C" int svt_hip_launch_strength_select_multi(hipStream_t st, int n_pics, 
         }
     }
     return (int)hipGetLastError();
-}
-extern "C" int svt_hip_launch_strength_select(hipStream_t st, const uint64_t* mse0, const uint64_t* mse1, int sb_count, int start_gi, int end_gi, void* state) {
-    return svt_hip_launch_strength_select_multi(st, 1, &mse0, &mse1, sb_count, start_gi, end_gi, &state, 0);
 }
 extern "C" int svt_hip_launch_sgr_flt_proj(hipStream_t st, int pix_bytes, const void* src, int ss, const void* dat, int ds, const int32_t* f0, int f0s, const int32_t* f1, int f1s,
                                            int w, int h, int r0, int r1, int mode, int xq0, int xq1, long long* acc, int32_t* xq_out) {

@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <string.h>
 #include "svt_hip_internal.h"
 
 #ifdef SVT_SGR_NT
@@ -36,8 +35,7 @@ __device__ __forceinline__ int4 sgr_ld4_nt(const void* p) { const sgr_v4i v = __
 
 namespace {
 
-constexpr int kStreamCand = 10;  // the streamed form keeps one accumulator per candidate in registers
-constexpr int kMaxCand = 16;     // capacity of the per-pass candidate list (the launch's `cap` <= this is the number actually used)
+constexpr int kMaxCand = 16;    // capacity of the per-pass candidate list (the launch's `cap` <= this is the number actually used)
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 struct WalkPlane {   // one plane's arguments of a walk launch
     const uint32_t* pairs; const int16_t* sd; const int64_t* sums; size_t dplane;
@@ -100,31 +98,8 @@ __device__ void solve_and_encode(const long long* sums, int size, int ep, int xq
 // finer_search_pixel_proj_error replayed on the cache.  Returns true when the walk finished on exact errors only.
 // Executed by ALL 64 lanes of wave 0 with identical values (uniform control flow): the scalar walk logic runs as before, but the two
 // searches it performs over and over — "is this point in the cache?", "is it already wanted?" — compare 64 entries at a time across the
-// lanes (a ballot) instead of looping over them.  Parameter-set constants are arithmetic (no table loads).  The store of evaluated and wanted
-// points is a policy: LdsStore keeps them in the workgroup's LDS (streamed form), RegStore in the registers of the walking wave (resident form).
-struct LdsStore {
-    WalkLds& L; int lane, n_cache, nw, cap;
-    __device__ LdsStore(WalkLds& l, int ln, int cp) : L(l), lane(ln), n_cache(l.n_cache), nw(0), cap(cp) {}
-    __device__ bool lookup(int x, int y, long long& e) const {
-        for (int base = 0; base < n_cache; base += 64) {
-            const int  i = base + lane;
-            const bool hit = i < n_cache && L.cx[i] == x && L.cy[i] == y;
-            const unsigned long long m = __ballot(hit);
-            if (m) { e = L.ce[base + __ffsll((long long)m) - 1]; return true; }
-        }
-        return false;
-    }
-    __device__ void want(int x, int y) {
-        const bool dup = __ballot(lane < nw && ((volatile int*)L.wx)[lane] == x && ((volatile int*)L.wy)[lane] == y) != 0;   // kMaxCand <= 64; lane 0 wrote the list
-        if (!dup && nw < cap) { if (lane == 0) { L.wx[nw] = x; L.wy[nw] = y; } nw++; }
-    }
-    __device__ void finish(bool exact, int q0, int q1, double err) {
-        if (lane == 0) {
-            L.n_want = nw;
-            if (exact) { L.res_x = q0; L.res_y = q1; L.res_err = (long long)err; }
-        }
-    }
-};
+// lanes (a ballot) instead of looping over them.  Parameter-set constants are arithmetic (no table loads).  Evaluated and wanted points live in the
+// registers of the walking wave (RegStore).
 // lane i of bank b holds evaluated point 64 b + i: a lookup is one compare + ballot + two v_readlane per bank in use, no memory on the serial path
 constexpr int kBanks = kCache / 64;
 __device__ __forceinline__ int point_key(int x, int y) { return (x + 128) | ((y + 128) << 8); }   // taps lie in [-96, 95]
@@ -171,31 +146,7 @@ __device__ __forceinline__ void walk_begin(WalkState& W, const int start[2]) { W
 // the quadratic model, collecting up to K.cap unknown points.  Returns true when the walk finished on exact errors only (W.q0, W.q1, W.err = result).
 struct ModelSums { double H00, H01, H11, C0, C1; };   // the five projection sums of the (unit, set), read from memory once per walk
 __device__ __forceinline__ ModelSums load_model(const long long* sums) { return ModelSums{(double)sums[0], (double)sums[1], (double)sums[2], (double)sums[3], (double)sums[4]}; }
-// HEDGE (opt-in instance): what the OTHER outcome of a speculative decision would probe next is asked for as well.  A pass costs ~44 k cycles whatever it evaluates
-// (it streams the part of the unit that is not resident) and a point ~2 k (profiles/r03/sgr_walk_cand_sweep.txt), while half of the decisions near the optimum are
-// decided by rounding noise the model cannot see (tools/sgr_walk_sim.c: 2.97 -> 2.20 passes per walk with 16 points per pass).  These two helpers restate the walk's
-// state transitions for that look-ahead only; whatever they return changes which points are evaluated, never the result.
-__device__ __forceinline__ void walk_apply(WalkState& A, bool accept, int c0, int c1) {
-    bool again = false;
-    if (accept) { A.q0 = c0; A.q1 = c1; if (!A.up) A.moved = 1; again = A.s == 2; }
-    if (!again) {
-        if (!A.up) { if (A.moved) A.p = 2; else A.up = 1; }
-        else { A.p++; A.up = 0; A.moved = 0; }
-    }
-}
-__device__ __forceinline__ bool walk_peek(WalkState A, bool has0, bool has1, int& c0, int& c1) {
-    for (int guard = 0; guard < 12 && A.s >= 1; guard++) {
-        if (A.p >= 2) { A.s >>= 1; A.p = 0; A.up = 0; A.moved = 0; continue; }
-        if (A.p == 0 ? !has0 : !has1) { A.p++; A.up = 0; A.moved = 0; continue; }
-        const int tmin = A.p == 0 ? -96 : -32, tmax = A.p == 0 ? 31 : 95;
-        const int qp = A.p == 0 ? A.q0 : A.q1, d = A.up ? A.s : -A.s;
-        if (A.up ? qp + A.s <= tmax : qp - A.s >= tmin) { c0 = A.p == 0 ? A.q0 + d : A.q0; c1 = A.p == 0 ? A.q1 : A.q1 + d; return true; }
-        walk_apply(A, false, 0, 0);
-    }
-    return false;
-}
-template <class Store, bool HEDGE = false>
-__device__ bool replay(Store& K, WalkState& W, int ep, const ModelSums& MS) {
+__device__ bool replay(RegStore& K, WalkState& W, int ep, const ModelSums& MS) {
     const bool   has0 = ep < 10 || ep >= 14, has1 = ep < 14;
     const double H00 = MS.H00, H01 = MS.H01, H11 = MS.H11, C0 = MS.C0, C1 = MS.C1;
     auto model = [&](int x, int y) {
@@ -231,13 +182,6 @@ __device__ bool replay(Store& K, WalkState& W, int ep, const ModelSums& MS) {
         if (T.up ? qp + T.s <= tmax : qp - T.s >= tmin) {
             const int c0 = T.p == 0 ? T.q0 + d : T.q0, c1 = T.p == 0 ? T.q1 : T.q1 + d;
             const double err2 = value(c0, c1);
-            if (HEDGE && spec && K.nw < K.cap) {   // the other outcome's next probe
-                WalkState A = T;
-                walk_apply(A, err2 > T.err, c0, c1);
-                int a0, a1;
-                long long e;
-                if (walk_peek(A, has0, has1, a0, a1) && !K.lookup(a0, a1, e)) K.want(a0, a1);
-            }
             if (!(err2 > T.err)) { T.q0 = c0; T.q1 = c1; T.err = err2; if (!T.up) T.moved = 1; again = T.s == 2; }
         }
         if (!again) {
@@ -271,7 +215,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     return v;
 }
 
-// grid: (units, 16); block 256.  pairs: [16] planes of (flt0 - u) | (flt1 - u) << 16 (plane `ep`; sets 11 / 12 / 13 read the plane of 2 / 5 / 8 — their
+// pairs: [16] planes of (flt0 - u) | (flt1 - u) << 16 (plane `ep`; sets 11 / 12 / 13 read the plane of 2 / 5 / 8 — their
 // xq0 is 0, so the r0 half does not matter), sd: one int16 plane of dat - src.
 // Publishing a walk's result to the workgroup that finishes the unit: write-through (agent-scope) stores, drained, then the arrival count; the reader uses
 // agent-scope loads.  A __threadfence() pair here meant an L2 write-back + invalidate per walk (thousands per picture), which also cost the kernels of other
@@ -296,136 +240,20 @@ __device__ __forceinline__ void pick_unit_best(const int32_t* xqd_out, const lon
     }
 }
 
-template <int BD>
-__global__ void __launch_bounds__(256)
-sgr_walk_kernel(const uint32_t* __restrict__ pairs, const int16_t* __restrict__ sd, int dstride, size_t dplane,
-                const long long* __restrict__ sums, int pw, int ph, int unit_size, int units_x, int units_y, int voff, uint32_t ep_mask,
-                int32_t* __restrict__ xqd_out, long long* __restrict__ err_out, uint32_t* __restrict__ counters, uint8_t* __restrict__ best_ep,
-                int32_t* __restrict__ best_xqd, uint32_t* __restrict__ stats, int cap) {
-    __shared__ WalkLds L;
-    const int unit = blockIdx.x, ep = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (!((ep_mask >> ep) & 1)) return;
-    // the unit's rectangle: foreach_rest_unit_in_tile (Common/Codec/EbRestoration.c:1369-1411)
-    const int uj = unit % units_x, ui = unit / units_x;
-    const int x0 = uj * unit_size, w = uj == units_x - 1 ? pw - x0 : unit_size;
-    const int y0 = ui * unit_size, h = ui == units_y - 1 ? ph - y0 : unit_size;
-    const int v0 = max(y0 - voff, 0), v1 = (y0 + h < ph) ? y0 + h - voff : y0 + h;
-    const bool has0 = ep < 10 || ep >= 14, has1 = ep < 14;
-    const int  ce = ep == 11 ? 2 : (ep == 12 ? 5 : (ep == 13 ? 8 : ep));
-    const uint32_t* __restrict__ PP = pairs + (size_t)ce * dplane;
-    const long long* S = sums + ((size_t)unit * 16 + ep) * 5;
-
-    int start[2] = {0, 0};
-    if (wave == 0) {   // all lanes of wave 0 carry the same values
-        solve_and_encode(S, w * (v1 - v0), ep, start);
-        if (lane == 0) {
-            L.n_cache = 0; L.done = 0; L.last = 0; L.n_want = 0;
-            L.res_x = start[0]; L.res_y = start[1]; L.res_err = -1;
-        }
-    }
-    __syncthreads();
-    const int cw = (w + 7) >> 3, nchunk = cw * (v1 - v0);
-    int n_pass = 0, n_eval = 0;
-    for (int pass = 0; pass < kPassBudget; pass++) {
-        if (wave == 0) {
-            LdsStore K(L, lane, ((volatile int&)L.n_cache) >= kThrottle ? 1 : cap);
-            WalkState W0; walk_begin(W0, start);   // the streamed form re-decides the whole walk every pass
-            const ModelSums MS0 = load_model(S);
-            const bool fin = replay(K, W0, ep, MS0);
-            if (lane == 0) L.done = fin ? 1 : 0;
-            __builtin_amdgcn_wave_barrier();
-            if (lane < kStreamCand) {   // svt_decode_xq (Common/Codec/EbRestoration.c:707-718); entries past n_want are not read
-                const int x = L.wx[lane], y = L.wy[lane];
-                L.xq0[lane] = has0 ? x : 0;
-                L.xq1[lane] = !has1 ? 0 : (has0 ? 128 - x - y : 128 - y);
-            }
-        }
-        __syncthreads();
-        if (L.done) break;
-        const int nc = L.n_want;
-        n_pass++; n_eval += nc;
-        int xq[kStreamCand];   // both taps scaled by 32 and packed for v_dot2_i32_i16 (|32 xq| <= 8192)
-        long long acc[kStreamCand];
-#pragma unroll
-        for (int c = 0; c < kStreamCand; c++) {
-            xq[c] = c < nc ? (int)(((uint32_t)(L.xq0[c] * 32) & 0xFFFFu) | ((uint32_t)(L.xq1[c] * 32) << 16)) : 0;
-            acc[c] = 0;
-        }
-        // ---- one pass over the unit: e = ((dat - src) << 11 | rounding) + xq0 (flt0 - u) + xq1 (flt1 - u)) >> 11   (svt_av1_{lowbd,highbd}_pixel_proj_error, :174-316).
-        // Everything is scaled by 32 so that the >> 11 becomes "take the high half": one v_dot2_i32_i16 forms a pixel's sum, v_perm_b32 packs the high halves
-        // of two of them, a second v_dot2_i32_i16 squares and accumulates both errors.
-        for (int k = tid; k < nchunk; k += 256) {
-            const int row = k / cw, cx = k - row * cw;
-            const size_t off = (size_t)(v0 + row) * dstride + x0 + 8 * cx;
-            const int4 a0 = *(const int4*)(PP + off), a1 = *(const int4*)(PP + off + 4);
-            const int4 s = *(const int4*)(sd + off);
-            const int  n = min(8, w - 8 * cx);
-            int pr[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, bs[8];
-            const int sw[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) { bs[2 * i] = (sw[i] << 16) + 32768; bs[2 * i + 1] = (int)((uint32_t)sw[i] & 0xFFFF0000u) + 32768; }   // 32 x (((dat - src) << 11) + 2^10)
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                if (i >= n) { pr[i] = 0; bs[i] = 0; }   // columns past the unit: e = 0
-#pragma unroll
-            for (int c = 0; c < kMaxCand; c++) {
-                if (c < nc) {   // workgroup-uniform
-                    const s16x2 q = __builtin_bit_cast(s16x2, xq[c]);
-                    int p = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i += 2) {
-                        const int t0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pr[i]), q, bs[i], false);
-                        const int t1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pr[i + 1]), q, bs[i + 1], false);
-                        const int ee = (int)__builtin_amdgcn_perm((uint32_t)t1, (uint32_t)t0, 0x07060302u);   // (t0 >> 16) | (t1 & 0xffff0000): the two errors, int16 each
-                        p = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, ee), __builtin_bit_cast(s16x2, ee), p, false);   // |e| < 2^13 at bit depth 10: eight squares stay below 2^31
-                    }
-                    acc[c] += p;
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < kMaxCand; c++)
-            if (c < nc) {
-                const long long t = wave_sum_i64(acc[c]);
-                if (lane == 0) L.part[wave][c] = t;
-            }
-        __syncthreads();
-        if (tid == 0) {
-            for (int c = 0; c < nc && L.n_cache < kCache; c++) {
-                L.cx[L.n_cache] = L.wx[c]; L.cy[L.n_cache] = L.wy[c];
-                L.ce[L.n_cache] = L.part[0][c] + L.part[1][c] + L.part[2][c] + L.part[3][c];
-                L.n_cache++;
-            }
-        }
-        __syncthreads();
-    }
-    // ---- results, and the unit's best set once all of its sets are in: search_selfguided_restoration :661-665 (first set with the smallest error)
-    if (tid == 0) {
-        publish_walk(xqd_out, err_out, (size_t)unit * 16 + ep, L.res_x, L.res_y, L.done ? L.res_err : -1);   // -1: walk not finished within the pass budget (cannot happen, see kThrottle; callers treat it as a failure)
-        atomicAdd(&stats[0], (uint32_t)n_pass); atomicAdd(&stats[1], (uint32_t)n_eval); if (!L.done) atomicAdd(&stats[2], 1u);   // diagnostics
-        const uint32_t arrived = atomicAdd(&counters[unit], 1u) + 1u;
-        if (arrived == (uint32_t)__popc(ep_mask)) pick_unit_best(xqd_out, err_out, unit, ep_mask, best_ep, best_xqd);
-    }
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------------------------------------
-// The same search with the unit RESIDENT on the compute unit: one 1024-thread workgroup per (unit, set).  Waves 1-15 load the unit's difference planes
-// once — the (flt0 - u, flt1 - u) words into registers (9 chunks of 8 pixels per thread x 960 threads = 69 120 pixels, a whole 256 x 256 unit), dat - src
-// into 135 KB of LDS — and every later pass of the walk is arithmetic on resident data; wave 0 holds no pixels and runs the solve and the replay (its
-// registers are the replay's: the two roles are separate code paths that meet at the workgroup barriers, so neither spills).  The streamed form above
-// re-reads 6 bytes per pixel and pass (3.3 passes per walk on coded content): 4 GB per 4K frame against 1.2 GB here.  Units larger than 69 120 pixels
-// (the last row / column may be up to 1.5 x the unit size) keep the excess in memory and stream it per pass like the form above.  Per candidate and
+// The walk kernel: one 512-thread workgroup per (unit, set), part of the unit RESIDENT on the compute unit.  Waves 1-7 (kWalkD = 448 data threads) load
+// kWalkJ = 7 chunks of eight samples each once -- the (flt0 - u, flt1 - u) words into registers, dat - src into LDS: 7 x 448 chunks = 38 % of a 256 x 256 unit --
+// and stream the rest of the unit on every pass, chunk-outer with kWalkNA = 8 candidate accumulators; wave 0 holds no pixels and runs the solve and the replay
+// (its registers are the replay's: the two roles are separate code paths that meet at the workgroup barriers, so neither spills).  Two workgroups share a compute
+// unit: one workgroup's loads and replays overlap the other's evaluation (a compute unit streams only ~10 B per cycle from HBM).  A unit that fits the resident
+// slots as a whole (every chroma unit of a 4:2:0 picture, small edge units) is evaluated candidate by candidate on resident data alone.  Per candidate and
 // pixel pair: 2 v_dot2_i32_i16 (weighted sum, rounding constant as the accumulator), v_perm_b32 (high halves), v_pk_add_i16 (+ dat - src),
-// v_dot2_i32_i16 (square-accumulate).
-constexpr int kResT = 1024, kResJ = 9;   // full residency: threads, resident chunks per data thread
-// The HYBRID instance (T = 512, J = 7, NA = 8): two workgroups share a compute unit, each keeps 7 x 448 chunks (38 % of a 256 x 256 unit) resident and
-// streams the rest of the unit on every pass, chunk-outer with NA candidate accumulators — one workgroup's loads and replays overlap the other's
-// evaluation (a compute unit streams only ~10 B per cycle from HBM, and with full residency nothing else can run beside the 1024 threads).
-template <int T, int J>
-struct ResLdsT {
+// v_dot2_i32_i16 (square-accumulate).  The forms this one was measured against (streamed, fully resident with 1024 threads, sixteen hedged candidates, 256-thread
+// workgroups, two chunks in flight, the draining 10-bit instance) are described with their results in docs/design/retired-variants.md.
+constexpr int kWalkT = 512, kWalkD = kWalkT - 64, kWalkJ = 7, kWalkNA = 8;   // threads, data threads, resident chunks per data thread, candidates per streaming pass
+struct ResLds {
     WalkLds W;
-    int4    sd[J * (T - 64)];   // [chunk slot][data thread]: eight dat - src values
+    int4    sd[kWalkJ * kWalkD];   // [chunk slot][data thread]: eight dat - src values
 };
 
 // Eight pixels of one candidate: 20 vector instructions, written out because the order matters on this pipeline — a dot product's result may
@@ -491,33 +319,8 @@ __device__ __forceinline__ void eval_chunk_f(const int4& a0, const int4& a1, con
         : [a0] "v"(a0.x), [a1] "v"(a0.y), [a2] "v"(a0.z), [a3] "v"(a0.w), [a4] "v"(a1.x), [a5] "v"(a1.y), [a6] "v"(a1.z), [a7] "v"(a1.w), [c0] "v"(c[0]), [c1] "v"(c[1]),
           [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]), [c5] "v"(c[5]), [c6] "v"(c[6]), [c7] "v"(c[7]), [q] "s"(q), [sel] "s"(sel));
 }
-// One accumulator per candidate (the 16-candidate instance: |e| < 2^10 at bit depth 8 and a thread sees < 400 samples of the largest unit, so 2^20 x 400 < 2^31):
-// the four squaring dots chain through p (a dot may feed the next dot's accumulator back to back).
-__device__ __forceinline__ void eval_chunk_f1(const int4& a0, const int4& a1, const int (&c)[8], int q, int sel, int& p) {
-    int t0, t1, t2, t3, t4, t5, t6, t7;
-    asm volatile(
-        "v_dot2_i32_i16 %[t0], %[a0], %[q], %[c0]\n\t"
-        "v_dot2_i32_i16 %[t1], %[a1], %[q], %[c1]\n\t"
-        "v_dot2_i32_i16 %[t2], %[a2], %[q], %[c2]\n\t"
-        "v_dot2_i32_i16 %[t3], %[a3], %[q], %[c3]\n\t"
-        "v_dot2_i32_i16 %[t4], %[a4], %[q], %[c4]\n\t"
-        "v_dot2_i32_i16 %[t5], %[a5], %[q], %[c5]\n\t"
-        "v_dot2_i32_i16 %[t6], %[a6], %[q], %[c6]\n\t"
-        "v_dot2_i32_i16 %[t7], %[a7], %[q], %[c7]\n\t"
-        "v_perm_b32 %[t0], %[t1], %[t0], %[sel]\n\t"
-        "v_perm_b32 %[t2], %[t3], %[t2], %[sel]\n\t"
-        "v_perm_b32 %[t4], %[t5], %[t4], %[sel]\n\t"
-        "v_perm_b32 %[t6], %[t7], %[t6], %[sel]\n\t"
-        "v_dot2_i32_i16 %[p], %[t0], %[t0], %[p]\n\t"
-        "v_dot2_i32_i16 %[p], %[t2], %[t2], %[p]\n\t"
-        "v_dot2_i32_i16 %[p], %[t4], %[t4], %[p]\n\t"
-        "v_dot2_i32_i16 %[p], %[t6], %[t6], %[p]"
-        : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7), [p] "+v"(p)
-        : [a0] "v"(a0.x), [a1] "v"(a0.y), [a2] "v"(a0.z), [a3] "v"(a0.w), [a4] "v"(a1.x), [a5] "v"(a1.y), [a6] "v"(a1.z), [a7] "v"(a1.w), [c0] "v"(c[0]), [c1] "v"(c[1]),
-          [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]), [c5] "v"(c[5]), [c6] "v"(c[6]), [c7] "v"(c[7]), [q] "v"(q), [sel] "s"(sel));
-}
-// eval_chunk_f1 with the candidate's taps in a SCALAR register (each instruction still reads one scalar operand only) -- the packed walk's form: ONE int32 accumulator
-// per candidate (|e| <= 1010 at bit depth 8 and a data thread of the 512-thread instances sees <= 42 chunks = 336 samples: 336 x 2^20 < 2^31), the four squaring dots
+// eval_chunk_f with the candidate's taps in a SCALAR register (each instruction still reads one scalar operand only) and ONE int32 accumulator
+// per candidate -- the packed walk's form (|e| <= 1010 at bit depth 8 and a data thread of the 512-thread instances sees <= 42 chunks = 336 samples: 336 x 2^20 < 2^31), the four squaring dots
 // chain through it (a dot may feed the next dot's accumulator back to back).  Against eval_chunk_f: sixteen vector registers fewer per pass.
 __device__ __forceinline__ void eval_chunk_f1s(const int4& a0, const int4& a1, const int (&c)[8], int q, int sel, int& p) {
     int t0, t1, t2, t3, t4, t5, t6, t7;
@@ -559,18 +362,14 @@ __device__ __forceinline__ void mask_chunk(int4& a0, int4& a1, int4& s, int n) {
 //   |e| <= ((96 + 256) D + 2^10) >> 11  +  (2^bd - 1)  =  3 019 + 1 023 = 4 042 at bit depth 10 (1 010 at 8),   e^2 <= 16 337 764 < 2^24 (< 2^20).
 // A v_dot2_i32_i16 accumulator wraps modulo 2^32, so READ AS UNSIGNED it holds floor((2^32 - 1) / 16 337 764) = 262 squares at bit depth 10.  The largest restoration
 // unit is 383 x 383 samples (1.5 x 256 rounds to two units; foreach_rest_unit_in_tile, EbRestoration.c:1369-1411) = 48 x 383 chunks of eight: a data thread of the
-// 512-thread instances (448 data threads) sees <= 42 chunks = 336 squares, 168 per accumulator of the two-accumulator forms -> NO 64-bit drain inside a pass at either
-// bit depth (round 3 emptied the 10-bit accumulators every third chunk on the looser |e| < 2^13).  One-accumulator forms (sixteen candidates) and the 256-thread
-// instances (192 data threads: 96 chunks) exceed 262 squares at bit depth 10: they keep the periodic drain (DRAIN).  tests/test_sgr_gpu.py::test_search_units_largest_unit_extreme_content.
-template <int BD, int kT, int kJ, int NA, int PF = 1, bool DRAIN = false>   // NA > 8 (opt-in instance): one accumulator per candidate, and the walker also asks for the other outcome's next probe; NA = 0: every candidate walks the resident chunks (and re-streams the excess of an over-sized unit) on its own; PF = streamed chunks in flight ahead of the one being evaluated
-__global__ void __launch_bounds__(kT, (kT == 512 ? 4 : 1))   // the hybrid instances are built for two workgroups per compute unit: 128 registers
+// kernel (448 data threads) sees <= 42 chunks = 336 squares, 168 per accumulator -> NO 64-bit drain inside a pass at either bit depth, and the two bit depths run the
+// same code (BD only names the instance).  tests/test_sgr_gpu.py::test_search_units_largest_unit_extreme_content.
+template <int BD>
+__global__ void __launch_bounds__(kWalkT, 4)   // built for two workgroups per compute unit: 128 registers
 sgr_walk_resident_kernel(const WalkPic a) {
-    constexpr int kResT = kT, kResJ = kJ, kResD = kT - 64;
-    constexpr bool HEDGE = NA > 8;                        // the sixteen-candidate instance's walker hedges its requests
-    constexpr bool ONE_ACC = NA > 8 || (DRAIN && PF != 2);   // one int32 accumulator per candidate: the sixteen-candidate instance (bit depth 8: a thread's squares fit), and the draining instances
-    static_assert(NA <= 8 || BD == 8, "sixteen int32 accumulators hold a thread's squares at bit depth 8 only");
-    static_assert(BD == 8 || DRAIN || kT >= 512, "bit depth 10 without drains: <= 42 chunks per data thread (see above)");
-    __shared__ ResLdsT<kT, kJ> R;
+    static_assert(BD == 8 || BD == 10, "the accumulator ranges above are those of bit depths 8 and 10");
+    static_assert(kWalkD * 42 >= 48 * 383, "<= 42 chunks per data thread: no drain (see above)");
+    __shared__ ResLds R;
     WalkLds& L = R.W;
     // the planes of a picture share one launch (grid.z): one tail instead of three.  Scalar copies of the plane's arguments (a reference into the
     // kernel-argument struct with a run-time index would force a private copy of the whole struct)
@@ -601,7 +400,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
     // a list of kCache exact (d, dat - src) entries, and a unit with more of them than that is evaluated sample by sample like the two-filter sets (decided after the
     // streaming pass; SVT_HIP_SGR_WALK_HIST_W narrows W so that tests reach the list and the fall-back).
     constexpr int kHistWMax = (int)(sizeof(R.sd) / 16) - 1 < 3071 ? (int)(sizeof(R.sd) / 16) - 1 : 3071;   // bins d + W, 0 <= . <= 2 W, in the storage of R.sd
-    const bool try_hist = NA > 0 && !(has0 && has1) && a.hist_w >= 0;   // workgroup-uniform
+    const bool try_hist = !(has0 && has1) && a.hist_w >= 0;   // workgroup-uniform
     const int  W = min(kHistWMax, a.hist_w);
 
     if (wave == 0) {
@@ -618,7 +417,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
         // a unit that is resident as a whole (every chroma unit of a 4:2:0 picture, small edge units) evaluates a candidate at ~1/8 of the cost of a streamed one
         // and needs no per-candidate accumulators: its passes take up to kMaxCand points, which lets most of its walks finish after ONE evaluation pass (two
         // replays instead of three: the serial replay is more than half of such a walk)
-        const bool whole = NA > 0 && ((w + 7) >> 3) * (v1 - v0) <= kResJ * kResD;
+        const bool whole = ((w + 7) >> 3) * (v1 - v0) <= kWalkJ * kWalkD;
         K.wkey = -1; K.lane = lane; K.n_cache = 0; K.nw = 0; K.cap = whole ? kMaxCand : cap; K.res_x = start[0]; K.res_y = start[1]; K.res_err = -1;
         bool hist = false;
         if (try_hist) { if (lane == 0) L.ovf_n = 0; __syncthreads(); }   // H: the data waves have cleared the histogram, the list is empty
@@ -632,7 +431,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
             const unsigned long long r0 = __builtin_readcyclecounter();
             __builtin_amdgcn_s_setprio(3);   // the replay is the serial part of the walk: it goes ahead of the other workgroup's evaluation waves on this SIMD
             K.cap = K.n_cache >= kThrottle ? 1 : cap0;
-            fin = replay<RegStore, HEDGE>(K, WS, ep, MS);
+            fin = replay(K, WS, ep, MS);
             __builtin_amdgcn_s_setprio(0);
             c_replay += __builtin_readcyclecounter() - r0;
             if (try_hist && pass == 0) {   // H2: the unit has been streamed (this first replay ran beside it); from the next pass on a histogram walk asks for sixteen points
@@ -663,7 +462,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
                 if (c >= 0 && c < nc) {
                     long long e = 0;
 #pragma unroll
-                    for (int v = 1; v < kResT / 64; v++) e += L.part[v][c];
+                    for (int v = 1; v < kWalkT / 64; v++) e += L.part[v][c];
                     K.key[b] = k; K.err[b] = e;
                 }
             }
@@ -691,7 +490,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
         unsigned long long* H = (unsigned long long*)&R.sd[0];
         // (a private copy of the histogram per data wave was measured and bought nothing: streaming the unit, not the atomics, is what this phase costs)
         const int nb = 2 * W + 1;
-        for (int b = t; b < nb; b += kResD) H[b] = 0ull;
+        for (int b = t; b < nb; b += kWalkD) H[b] = 0ull;
         __syncthreads();   // H
         // ---- the unit, once: one atomic per sample (the next chunk's loads are issued before this chunk's atomics)
         unsigned long long r2 = 0;
@@ -704,7 +503,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
         };
         if (k < nchunk) fetch(k, a0, a1, s4);
         while (k < nchunk) {
-            const int kn = k + kResD;
+            const int kn = k + kWalkD;
             int4 b0 = make_int4(0, 0, 0, 0), b1 = b0, t4 = b0;
             if (kn < nchunk) fetch(kn, b0, b1, t4);
             const int cx = k % cw, n = min(8, w - 8 * cx);
@@ -735,7 +534,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
                 for (int c = 0; c < nc; c++) {
                     const int xq = has0 ? L.xq0[c] : L.xq1[c];
                     long long acc = 0;
-                    for (int b = t; b < nb; b += kResD) {
+                    for (int b = t; b < nb; b += kWalkD) {
                         const unsigned long long h = H[b];
                         const int nd = (int)(h >> 40);
                         if (nd) {
@@ -744,7 +543,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
                             acc += (long long)nd * (q * q) + 2ll * q * Rd;   // nd q^2 < 2^18 x 2^17.2, |q Rd| < 2^8.6 x 2^28: int64
                         }
                     }
-                    for (int o = t; o < n_ovf; o += kResD) {   // a listed sample: n = 1, R = its dat - src (|xq d| < 2^8 x 2^14.1: 23 bits)
+                    for (int o = t; o < n_ovf; o += kWalkD) {   // a listed sample: n = 1, R = its dat - src (|xq d| < 2^8 x 2^14.1: 23 bits)
                         const int q = (xq * L.cx[o] + 1024) >> 11;
                         acc += (long long)q * q + 2ll * q * L.cy[o];
                     }
@@ -757,24 +556,24 @@ sgr_walk_resident_kernel(const WalkPic a) {
         }
     }
     // The resident part of the unit: ALL of its loads are issued before the first one is consumed.  (Round 2 .. 4 loaded chunk j under `if (k < nchunk)` and wrote its
-    // dat - src to LDS right away: a load under a condition is a branch, the LDS write behind it waits for it, and the kResJ chunks' loads ran one after the other —
-    // kResJ memory round trips, the "40 k-cycle load of a unit" of DESIGN 4.5.)  Chunks past the end load the last chunk's address and are zeroed afterwards.
-    int4 pa[kResJ], pb[kResJ], ps[kResJ];
+    // dat - src to LDS right away: a load under a condition is a branch, the LDS write behind it waits for it, and the kWalkJ chunks' loads ran one after the other —
+    // kWalkJ memory round trips, the "40 k-cycle load of a unit" of DESIGN 4.5.)  Chunks past the end load the last chunk's address and are zeroed afterwards.
+    int4 pa[kWalkJ], pb[kWalkJ], ps[kWalkJ];
 #pragma unroll
-    for (int j = 0; j < kResJ; j++) {
-        const int k = min(t + j * kResD, max(nchunk - 1, 0));
+    for (int j = 0; j < kWalkJ; j++) {
+        const int k = min(t + j * kWalkD, max(nchunk - 1, 0));
         const int row = k / cw, cx = k - row * cw;
         const size_t off = (size_t)(v0 + row) * dstride + x0 + 8 * cx;
         pa[j] = SGR_LD4(PP + off); pb[j] = SGR_LD4(PP + off + 4);
         ps[j] = *(const int4*)(sd + off);
     }
 #pragma unroll
-    for (int j = 0; j < kResJ; j++) {
-        const int k = t + j * kResD;
+    for (int j = 0; j < kWalkJ; j++) {
+        const int k = t + j * kWalkD;
         const int kc = min(k, max(nchunk - 1, 0)), row = kc / cw, cx = kc - row * cw;
         const int n = k < nchunk ? w - 8 * cx : 0;
         if (n < 8) mask_chunk(pa[j], pb[j], ps[j], n);
-        R.sd[j * kResD + t] = ps[j];   // read back by this thread only
+        R.sd[j * kWalkD + t] = ps[j];   // read back by this thread only
     }
     int rnd, sel;
     asm volatile("s_mov_b32 %0, 0x8000\n\ts_mov_b32 %1, 0x07060302" : "=s"(rnd), "=s"(sel));   // opaque: kept in scalar registers
@@ -784,57 +583,23 @@ sgr_walk_resident_kernel(const WalkPic a) {
         const int nc = L.n_want;
         const int qv = lane < nc ? (int)(((uint32_t)(L.xq0[lane] * 32) & 0xFFFFu) | ((uint32_t)(L.xq1[lane] * 32) << 16)) : 0;   // lane c: both taps of candidate c, scaled by 32 (|32 xq| <= 8192)
         const unsigned long long e0 = __builtin_readcyclecounter();
-        bool hybrid_done = false;
-        if constexpr (NA > 0) if (nchunk > kResJ * kResD) {
-            hybrid_done = true;
-            // ---- hybrid: the streamed part of the unit first (its loads are in flight while the resident part is evaluated), one pass over it for all
-            // candidates; per candidate two int32 accumulators (bit depth 8: |e| < 2^10, < 160 samples per thread) or one int32 accumulator emptied into a 64-bit sum every third chunk (bit depth 10)
-            int pp0[NA], pp1[NA]; long long acc[NA];
-            int qq[NA];
+        if (nchunk > kWalkJ * kWalkD) {
+            // ---- the streamed part of the unit first (its loads are in flight while the resident part is evaluated), one pass over it for all
+            // candidates; per candidate two int32 accumulators (read as unsigned: the ranges above)
+            // (acc stays 0: nothing drains into it.  It and the unreachable loop marked below are what is left of the retired forms in this kernel: without them the
+            // compiler emits other code -- the operand order of the final add; 24 instead of 40 bytes of scratch -- and the measured machine code is kept as it
+            // is, tools/isa_diff.py.  Removing them is a change of its own, with a measurement.)
+            int pp0[kWalkNA], pp1[kWalkNA]; long long acc[kWalkNA];
+            int qq[kWalkNA];
 #pragma unroll
-            for (int c = 0; c < NA; c++) { pp0[c] = pp1[c] = 0; acc[c] = 0; qq[c] = __builtin_amdgcn_readlane(qv, c); }
-            int k = t + kResJ * kResD;
+            for (int c = 0; c < kWalkNA; c++) { pp0[c] = pp1[c] = 0; acc[c] = 0; qq[c] = __builtin_amdgcn_readlane(qv, c); }
+            int k = t + kWalkJ * kWalkD;
             int4 a0 = make_int4(0, 0, 0, 0), a1 = a0, s4 = a0;
-            auto fetch = [&](int kk, int4& x0v, int4& x1v, int4& sv) {
-                const int row = kk / cw, cx = kk - row * cw;
-                const size_t off = (size_t)(v0 + row) * dstride + x0 + 8 * cx;
-                x0v = SGR_LD4(PP + off); x1v = SGR_LD4(PP + off + 4); sv = SGR_LD4(sd + off);
-                const int n = w - 8 * cx;
-                if (n < 8) mask_chunk(x0v, x1v, sv, n);
-            };
-            if (PF == 2 && k < nchunk) fetch(k, a0, a1, s4);
-            // bit depth 10: |e| < 2^13, eight squares per chunk: the candidate's int32 accumulator holds kDrain = 3 chunks (3 x 2^29 < 2^31) before it is emptied into
-            // its 64-bit sum -- every third streamed chunk, once more before the resident slots, every third of those, and at the end
-            constexpr int kDrain = 3;
-            auto drain = [&]() {
-                dot_drain();
-#pragma unroll
-                for (int c = 0; c < NA; c++)
-                    if (c < nc) { acc[c] += (long long)(uint32_t)pp0[c] + (long long)(uint32_t)pp1[c]; pp0[c] = pp1[c] = 0; }
-            };
-            if constexpr (PF == 2) {   // two chunks in flight: a compute unit's streaming rate is set by the bytes it has outstanding
-                int4 b0 = make_int4(0, 0, 0, 0), b1 = b0, t4 = b0;
-                if (k + kResD < nchunk) fetch(k + kResD, b0, b1, t4);
-                while (k < nchunk) {
-                    const int kn2 = k + 2 * kResD;
-                    int4 c0 = make_int4(0, 0, 0, 0), c1 = c0, u4 = c0;
-                    if (kn2 < nchunk) fetch(kn2, c0, c1, u4);
-                    int sx[8]; expand_sd(s4, sx);
-#pragma unroll
-                    for (int c = 0; c < NA; c++)
-                        if (c < nc) {
-                            if (ONE_ACC) eval_chunk_f1(a0, a1, sx, qq[c], sel, pp0[c]); else eval_chunk_f(a0, a1, sx, qq[c], sel, pp0[c], pp1[c]);
-                            if (DRAIN) { dot_drain(); acc[c] += (long long)(uint32_t)pp0[c] + (long long)(uint32_t)pp1[c]; pp0[c] = pp1[c] = 0; }
-                        }
-                    a0 = b0; a1 = b1; s4 = t4; b0 = c0; b1 = c1; t4 = u4; k += kResD;
-                }
-            } else {
-            // The streamed chunks of this thread are k, k + kResD, ...: (row, column chunk) and the byte offset advance by constants (one wrap test) instead of a
+            // The streamed chunks of this thread are k, k + kWalkD, ...: (row, column chunk) and the byte offset advance by constants (one wrap test) instead of a
             // division and 64-bit address arithmetic per chunk; the loop is unrolled over two register sets, so a prefetched chunk is consumed where it landed.
             // (Round 5's loop spent ~80 instructions per chunk around the 17 per candidate: division 17, addresses 10, zeroing and copying the prefetch buffers 32,
             // forming the accumulators 12 -- profiles/r06/NOTES.md.)
-            int since = 0;
-            const int d_row = kResD / cw, d_cx = kResD - d_row * cw;                       // wave-uniform
+            const int d_row = kWalkD / cw, d_cx = kWalkD - d_row * cw;                       // wave-uniform
             const uint32_t d_off = (uint32_t)(d_row * dstride + 8 * d_cx), d_wrap = (uint32_t)(dstride - 8 * cw);
             int cx = k % cw;
             uint32_t off = (uint32_t)((v0 + k / cw) * dstride + x0 + 8 * cx);             // samples from the plane's origin: < 2^24
@@ -852,64 +617,52 @@ sgr_walk_resident_kernel(const WalkPic a) {
                     // this chunk landed an iteration ago; its first use comes BEFORE the next chunk's loads are issued, so the wait for it does not cover them
                     if (ragged && na < 8) mask_chunk(a0, a1, s4, na);
                     int sx[8]; expand_sd(s4, sx);
-                    k += kResD; advance();
+                    k += kWalkD; advance();
                     const bool more = k < nchunk;
                     int4 b0, b1, t4; int nb = 8;
                     if (more) fetch2(b0, b1, t4, nb);   // next chunk's loads before this chunk's arithmetic
 #pragma unroll
-                    for (int c = 0; c < NA; c++)
-                        if (c < nc) {
-                            if (ONE_ACC) eval_chunk_f1(a0, a1, sx, qq[c], sel, pp0[c]); else eval_chunk_f(a0, a1, sx, qq[c], sel, pp0[c], pp1[c]);
-                        }
-                    if (DRAIN && ++since == kDrain) { drain(); since = 0; }
+                    for (int c = 0; c < kWalkNA; c++)
+                        if (c < nc) eval_chunk_f(a0, a1, sx, qq[c], sel, pp0[c], pp1[c]);
                     if (!more) break;
                     a0 = b0; a1 = b1; s4 = t4; na = nb;
                 }
             }
-            if (DRAIN && since) drain();
-            }
             // ---- the resident chunks, slot by slot for all candidates (one LDS read of dat - src per slot)
 #pragma unroll
-            for (int j = 0; j < kResJ; j++) {
-                if (j * kResD < nchunk) {
-                    const int4 sc = R.sd[j * kResD + t];
+            for (int j = 0; j < kWalkJ; j++) {
+                if (j * kWalkD < nchunk) {
+                    const int4 sc = R.sd[j * kWalkD + t];
                     int sx[8]; expand_sd(sc, sx);
 #pragma unroll
-                    for (int c = 0; c < NA; c++)
-                        if (c < nc) {
-                            if (ONE_ACC) eval_chunk_f1(pa[j], pb[j], sx, qq[c], sel, pp0[c]); else eval_chunk_f(pa[j], pb[j], sx, qq[c], sel, pp0[c], pp1[c]);
-                            if (DRAIN && PF == 2) { dot_drain(); acc[c] += (long long)(uint32_t)pp0[c] + (long long)(uint32_t)pp1[c]; pp0[c] = pp1[c] = 0; }
-                        }
-                    if (DRAIN && PF != 2 && (j + 1) % kDrain == 0 && j + 1 < kResJ) drain();
+                    for (int c = 0; c < kWalkNA; c++)
+                        if (c < nc) eval_chunk_f(pa[j], pb[j], sx, qq[c], sel, pp0[c], pp1[c]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
             dot_drain();
 #pragma unroll
-            for (int c = 0; c < NA; c++)
+            for (int c = 0; c < kWalkNA; c++)
                 if (c < nc) {
                     const long long sum = wave_sum_u48(acc[c] + (long long)(uint32_t)pp0[c] + (long long)(uint32_t)pp1[c]);   // the accumulators are read as unsigned (see the ranges above)
                     if (lane == 0) L.part[wave][c] = sum;
                 }
-        }
-        if (!hybrid_done)   // the unit is resident as a whole (or this is the fully resident instance): candidate by candidate over the resident chunks
-        for (int c = 0; c < nc; c++) {
+        } else for (int c = 0; c < nc; c++) {   // the unit is resident as a whole: candidate by candidate over the resident chunks
             const int q = __builtin_amdgcn_readlane(qv, c);
-            long long acc = 0;
             int p0 = 0, p1 = 0;
             int4 sn = R.sd[t];
 #pragma unroll
-            for (int j = 0; j < kResJ; j++) {   // dat - src of the next chunk is fetched while this one is evaluated; the fence keeps the scheduler from
-                if (j * kResD < nchunk) {       // hoisting all nine LDS reads (36 registers on top of the 72 resident ones); unused slots (small units) are skipped
+            for (int j = 0; j < kWalkJ; j++) {   // dat - src of the next chunk is fetched while this one is evaluated; the fence keeps the scheduler from
+                if (j * kWalkD < nchunk) {       // hoisting all seven LDS reads (28 registers on top of the 56 resident ones); unused slots (small units) are skipped
                     const int4 sc = sn;
-                    if (j + 1 < kResJ) sn = R.sd[(j + 1) * kResD + t];
+                    if (j + 1 < kWalkJ) sn = R.sd[(j + 1) * kWalkD + t];
                     eval_chunk(pa[j], pb[j], sc, q, rnd, sel, p0, p1);
-                    if (DRAIN) { dot_drain(); acc += (long long)(uint32_t)p0 + (long long)(uint32_t)p1; p0 = p1 = 0; }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (!DRAIN) { dot_drain(); acc += (long long)(uint32_t)p0 + (long long)(uint32_t)p1; p0 = p1 = 0; }   // <= 9 resident chunks: 36 squares per accumulator
-            for (int k = t + kResJ * kResD; k < nchunk; k += kResD) {   // the part of an over-sized unit that is not resident
+            dot_drain();   // <= 7 resident chunks: 28 squares per accumulator
+            long long acc = (long long)(uint32_t)p0 + (long long)(uint32_t)p1; p0 = p1 = 0;
+            for (int k = t + kWalkJ * kWalkD; k < nchunk; k += kWalkD) {   // unreachable (nchunk <= kWalkJ * kWalkD here), see acc above
                 const int row = k / cw, cx = k - row * cw;
                 const size_t off = (size_t)(v0 + row) * dstride + x0 + 8 * cx;
                 int4 a0 = SGR_LD4(PP + off), a1 = SGR_LD4(PP + off + 4), s = SGR_LD4(sd + off);
@@ -1019,7 +772,7 @@ sgr_walk_packed_kernel(const WalkPic a) {
             const unsigned long long r0 = __builtin_readcyclecounter();
             __builtin_amdgcn_s_setprio(3);
             K.cap = K.n_cache >= kThrottle ? 1 : cap0;
-            fin = replay<RegStore, false>(K, WS, ep, MS);
+            fin = replay(K, WS, ep, MS);
             __builtin_amdgcn_s_setprio(0);
             c_replay += __builtin_readcyclecounter() - r0;
             if (try_hist && pass == 0) {   // H2
@@ -1249,27 +1002,14 @@ sgr_walk_packed_kernel(const WalkPic a) {
 
 extern "C" size_t svt_hip_sgr_walk_state_bytes(int n_units) { return sizeof(uint32_t) * (size_t)n_units; }   // arrival counter per unit
 
-// planes[i]: the arguments of svt_hip_launch_sgr_walk for plane i; one launch for all of them (resident / hybrid forms), one per plane (streamed form)
+// one launch for all planes (grid.z); both forms take kWalkNA points per streaming pass
 extern "C" int svt_hip_launch_sgr_walk_multi(hipStream_t st, int bd, int n_planes, const SvtHipSgrWalkPlane* planes) {
     if (n_planes < 1 || n_planes > kWalkMaxPlanes) return (int)hipErrorInvalidValue;
-    // SVT_HIP_SGR_WALK = stream | resident | hybrid selects the form (A/B measurements, tools/hbd_time.py); default: hybrid
-    static const char* form_env = getenv("SVT_HIP_SGR_WALK");
-    const bool stream_form = form_env && !strcmp(form_env, "stream"), resident_form = form_env && !strcmp(form_env, "resident");
-    static const int  cap_env = getenv("SVT_HIP_SGR_WALK_CAND") ? atoi(getenv("SVT_HIP_SGR_WALK_CAND")) : 0;
-    constexpr int kHybT = 512, kHybJ = 7, kHybNA = 8;
-    constexpr int kHybNA10 = 7;   // bit depth 10, DRAINING instances (256-thread forms, and SVT_HIP_SGR_WALK_NA10=7 for A/B runs: the round-3 default): an int32 accumulator + a 64-bit sum per candidate; 7 spill 20 registers outside the loops and still win (MI355X, configs[3] unit search: 5: 2.02-2.03, 6: 1.95, 7: 1.90 ms; 8 spill 51).  The default since round 4 is the bit-depth-8 form itself (eight candidates, two accumulators, no drains: the range argument above sgr_walk_resident_kernel)
-    static const bool hyb16 = form_env && !strcmp(form_env, "hybrid16");   // opt-in: sixteen points per pass (one accumulator each) + hedged requests, bit depth 8
-    static const int na10_env = getenv("SVT_HIP_SGR_WALK_NA10") ? atoi(getenv("SVT_HIP_SGR_WALK_NA10")) : 0;   // A/B: 7 = the draining seven-candidate instance of round 3
-    static const bool small_form = form_env && (!strcmp(form_env, "hybrid256") || !strcmp(form_env, "hybrid256j"));
-    const int na10 = (na10_env == kHybNA10 || small_form) ? kHybNA10 : kHybNA;
-    const int cap_max = stream_form ? kStreamCand : (resident_form ? kMaxCand : (bd == 8 ? (hyb16 ? 16 : kHybNA) : na10));
-    const int cap = cap_env >= 1 && cap_env <= cap_max ? cap_env : (stream_form ? kStreamCand : (resident_form ? 12 : cap_max));   // candidates per pass
-    static const bool hist_off = getenv("SVT_HIP_SGR_WALK_HIST") && !atoi(getenv("SVT_HIP_SGR_WALK_HIST"));   // A/B: one-filter sets evaluated sample by sample like the others (round 3)
     WalkPic a = {};
-    a.cap = cap;
+    a.cap = kWalkNA;
     const char* hw_env = getenv("SVT_HIP_SGR_WALK_HIST_W");   // read per launch: tests/test_sgr_gpu.py narrows the window to send part of a plane's units down the sample-by-sample path
-    a.hist_w = hist_off ? -1 : (hw_env ? atoi(hw_env) : 1 << 30);
-    static const char* clk_env = getenv("SVT_HIP_SGR_WALK_CLOCKS");   // diagnostics, off by default since round 6 (the phase clocks cost 1.2 % of the stage: 0.923 -> 0.912 ms per 4K frame); =1: stats[24..30]
+    a.hist_w = hw_env ? atoi(hw_env) : 1 << 30;
+    static const char* clk_env = getenv("SVT_HIP_SGR_WALK_CLOCKS");   // diagnostics, off by default since round 6 (the phase clocks cost 1.2 % of the stage: 0.923 -> 0.912 ms per 4K frame); =1: stats[24..30] (tools/hbd_time.py)
     a.clocks = clk_env && clk_env[0] == '1';
     int max_units = 0;
     for (int i = 0; i < n_planes; i++) {
@@ -1282,64 +1022,13 @@ extern "C" int svt_hip_launch_sgr_walk_multi(hipStream_t st, int bd, int n_plane
         if ((P.esc != nullptr) != (planes[0].esc != nullptr)) return (int)hipErrorInvalidValue;   // one form per launch
         max_units = nu > max_units ? nu : max_units;
     }
-    if (planes[0].esc) {   // packed difference words (bit depth 8, sgr.hip STORE == 2): 512 threads, 7 chunks per data thread in registers + 5 in LDS, eight points per pass
+    const dim3 grid(max_units, 16, n_planes);
+    if (planes[0].esc) {   // packed difference words (bit depth 8, sgr.hip STORE == 2): 7 resident chunks per data thread become 5 in registers (the count that does not spill) + 5 in LDS
         if (bd != 8) return (int)hipErrorInvalidValue;
-        static const char* pk_env = getenv("SVT_HIP_SGR_WALK_PACKED");   // A/B: "j6l5", "j7l5": more resident chunks per data thread in registers (they spill)
-        a.cap = cap_env >= 1 && cap_env <= kHybNA ? cap_env : kHybNA;
-        dim3 grid(max_units, 16, n_planes);
-        if (pk_env && !strcmp(pk_env, "j7l5")) hipLaunchKernelGGL((sgr_walk_packed_kernel<512, 7, 5, kHybNA>), grid, dim3(512), 0, st, a);
-        else if (pk_env && !strcmp(pk_env, "j6l5")) hipLaunchKernelGGL((sgr_walk_packed_kernel<512, 6, 5, kHybNA>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((sgr_walk_packed_kernel<512, 5, 5, kHybNA>), grid, dim3(512), 0, st, a);   // five in registers: the form that does not spill (six: 28 registers, seven: 44)
-        return (int)hipGetLastError();
-    }
-    if (stream_form) {
-        for (int i = 0; i < n_planes; i++) {
-            const WalkPlane& W = a.p[i];
-            dim3 grid(W.units_x * W.units_y, 16);
-#define WALK_ARGS W.pairs, W.sd, W.dstride, W.dplane, (const long long*)W.sums, W.pw, W.ph, W.unit_size, W.units_x, W.units_y, W.voff, W.ep_mask, W.xqd_out, (long long*)W.err_out, W.counters, W.best_ep, W.best_xqd, W.stats, cap
-            if (bd == 8) hipLaunchKernelGGL((sgr_walk_kernel<8>), grid, dim3(256), 0, st, WALK_ARGS);
-            else hipLaunchKernelGGL((sgr_walk_kernel<10>), grid, dim3(256), 0, st, WALK_ARGS);
-#undef WALK_ARGS
-        }
-        return (int)hipGetLastError();
-    }
-    dim3 grid(max_units, 16, n_planes);
-    static const bool hyb256 = form_env && !strcmp(form_env, "hybrid256"), hyb256j = form_env && !strcmp(form_env, "hybrid256j");
-    static const bool hybpf5 = form_env && !strcmp(form_env, "hybridpf5");
-    if (hyb16 && bd == 8) {   // experiment (MI355X, profiles/r03/sgr_walk_hybrid16_ab.txt: 2.03 instead of 2.79 passes, 15.2 instead of 10.9 points per walk; stage 1.012 -> 0.993 ms, four-frame step 8.61 -> 8.76 ms: not the default)
-        hipLaunchKernelGGL((sgr_walk_resident_kernel<8, kHybT, kHybJ, 16>), grid, dim3(kHybT), 0, st, a);
-        return (int)hipGetLastError();
-    }
-    if (hybpf5 && bd == 8) {   // experiment (MI355X: 1.190 vs 1.163 ms, no gain): five resident chunks instead of seven, two streamed chunks in flight
-        hipLaunchKernelGGL((sgr_walk_resident_kernel<8, kHybT, 5, kHybNA, 2>), dim3(max_units, 16, n_planes), dim3(kHybT), 0, st, a);
-        return (int)hipGetLastError();
-    }
-    if (hyb256 || hyb256j) {   // experiment: four smaller workgroups per compute unit (one walker + three data waves each)
-        if (hyb256) {
-            if (bd == 8) hipLaunchKernelGGL((sgr_walk_resident_kernel<8, 256, kHybJ, kHybNA>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((sgr_walk_resident_kernel<10, 256, kHybJ, kHybNA10, 1, true>), grid, dim3(256), 0, st, a);
-        } else {
-            if (bd == 8) hipLaunchKernelGGL((sgr_walk_resident_kernel<8, 256, 9, kHybNA>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((sgr_walk_resident_kernel<10, 256, 9, kHybNA10, 1, true>), grid, dim3(256), 0, st, a);
-        }
-        return (int)hipGetLastError();
-    }
-    if (resident_form) {
-        if (bd == 8) hipLaunchKernelGGL((sgr_walk_resident_kernel<8, kResT, kResJ, 0>), grid, dim3(kResT), 0, st, a);
-        else hipLaunchKernelGGL((sgr_walk_resident_kernel<10, kResT, kResJ, 0>), grid, dim3(kResT), 0, st, a);
-    } else {
-        if (bd == 8) hipLaunchKernelGGL((sgr_walk_resident_kernel<8, kHybT, kHybJ, kHybNA>), grid, dim3(kHybT), 0, st, a);
-        else if (na10 == kHybNA10) hipLaunchKernelGGL((sgr_walk_resident_kernel<10, kHybT, kHybJ, kHybNA10, 1, true>), grid, dim3(kHybT), 0, st, a);
-        else hipLaunchKernelGGL((sgr_walk_resident_kernel<10, kHybT, kHybJ, kHybNA>), grid, dim3(kHybT), 0, st, a);
-    }
+        hipLaunchKernelGGL((sgr_walk_packed_kernel<kWalkT, 5, 5, kWalkNA>), grid, dim3(kWalkT), 0, st, a);
+    } else if (bd == 8) hipLaunchKernelGGL(sgr_walk_resident_kernel<8>, grid, dim3(kWalkT), 0, st, a);
+    else hipLaunchKernelGGL(sgr_walk_resident_kernel<10>, grid, dim3(kWalkT), 0, st, a);
     return (int)hipGetLastError();
-}
-extern "C" int svt_hip_launch_sgr_walk(hipStream_t st, int bd, const uint32_t* pairs, const int16_t* sd, int dstride, size_t dplane, const int64_t* sums,
-                                       const int64_t* d2, void* states, int pw, int ph, int unit_size, int units_x, int units_y, int ss_y, uint32_t ep_mask,
-                                       int32_t* xqd_out, int64_t* err_out, uint8_t* best_ep, int32_t* best_xqd, uint32_t* stats) {
-    (void)d2;
-    const SvtHipSgrWalkPlane P = {pairs, sd, sums, states, dplane, dstride, pw, ph, unit_size, units_x, units_y, ss_y, ep_mask, xqd_out, err_out, best_ep, best_xqd, stats, nullptr, nullptr};
-    return svt_hip_launch_sgr_walk_multi(st, bd, 1, &P);
 }
 
 SVT_HIP_TU_PROBE(sgr_walk)

@@ -138,9 +138,6 @@ typedef struct {
     const void* esc; const uint32_t* esc_cnt;   /* non-NULL: `pairs` holds the PACKED words of sgr_search8_kernel<.., 2> (bit depth 8), esc / esc_cnt its escape lists; sd is unused */
 } SvtHipSgrWalkPlane;
 int svt_hip_launch_sgr_walk_multi(hipStream_t st, int bd, int n_planes, const SvtHipSgrWalkPlane* planes);
-int svt_hip_launch_sgr_walk(hipStream_t st, int bd, const uint32_t* pairs, const int16_t* sd, int dstride, size_t dplane, const int64_t* sums, const int64_t* d2,
-                            void* states, int pw, int ph, int unit_size, int units_x, int units_y, int ss_y, uint32_t ep_mask, int32_t* xqd_out, int64_t* err_out,
-                            uint8_t* best_ep, int32_t* best_xqd, uint32_t* stats);
 int svt_hip_launch_sgr_apply(hipStream_t st, int pix_bytes, int bd, const void* dgd, int stride, void* dst, int dst_stride, int pw, int ph,
                              int unit_size, int units_x, int units_y, int ss_y, const void* dbl, int dbl_stride, const uint8_t* unit_ep,
                              const int32_t* unit_xqd, const int16_t* unit_wiener);
@@ -181,7 +178,6 @@ int svt_hip_launch_search_one_dual(hipStream_t st, const uint64_t* mse0, const u
 size_t svt_hip_joint_state_bytes(void);
 int svt_hip_launch_cdef_finish(hipStream_t st, const uint64_t* mse0, const uint64_t* mse1, int sb_count, const void* state, unsigned long long lambda, const int* sb_fb, void* out,
                                int* sel_gi, uint8_t* fb_y, uint8_t* fb_uv);
-int svt_hip_launch_strength_select(hipStream_t st, const uint64_t* mse0, const uint64_t* mse1, int sb_count, int start_gi, int end_gi, void* state);
 int svt_hip_launch_strength_select_multi(hipStream_t st, int n_pics, const uint64_t* const* mse0, const uint64_t* const* mse1, int sb_count, int start_gi, int end_gi,
                                          void* const* states, int resident);
 int svt_hip_launch_joint_strength_search(hipStream_t st, const uint64_t* mse0, const uint64_t* mse1, int sb_count, int* lev0, int* lev1, int nb, int start_gi, int end_gi,

@@ -327,8 +327,7 @@ tf_noise_kernel(const PIX* __restrict__ src, int width, int height, int stride, 
 template <typename PIX>
 int launch_filter(hipStream_t st, const TfArgs& a, int w, int h, int ss_x, int ss_y) {
     const dim3 grid(w / 32, h / 32), block(256);
-    static const char* div_env = getenv("SVT_HIP_TF_DIV");   // "ieee": the IEEE divisions everywhere (A/B runs, tools/tf_time.py)
-    const bool fast = recip_ok(a.den[0]) && recip_ok(a.den[1]) && recip_ok(a.den[2]) && recip_ok(a.dist_thr) && !(div_env && !strcmp(div_env, "ieee"));
+    const bool fast = recip_ok(a.den[0]) && recip_ok(a.den[1]) && recip_ok(a.den[2]) && recip_ok(a.dist_thr);
 #define TF_LAUNCH(SX, SY) do { if (fast) hipLaunchKernelGGL((tf_filter_kernel<PIX, SX, SY, true>), grid, block, 0, st, a); \
                                else hipLaunchKernelGGL((tf_filter_kernel<PIX, SX, SY, false>), grid, block, 0, st, a); } while (0)
     if (ss_x == 1 && ss_y == 1) TF_LAUNCH(1, 1);
