@@ -318,7 +318,8 @@ int svt_hip_dlf_search_levels_picture_dev(SvtHipCtx *ctx, int n_planes, const Sv
  *             gi = pri*4 + sec_idx of the full search (pcs->mse_seg, CDEF_FULL_SEARCH); the reduced
  *             pick methods are subsets of these 64 entries (get_cdef_filter_strengths,
  *             Common/Codec/EbDefinitions.h:1696).  Entries of all-skip filter blocks are not written.
- *   d_dir/d_var [nfb][64] scratch/outputs: direction and variance of every 8x8 block (svt_cdef_find_dir).
+ *   d_dir/d_var [nfb][64] scratch/outputs: direction and variance of every 8x8 block (svt_cdef_find_dir); 0 for a
+ *             skipped block and outside the picture.
  * Replaces svt_cdef_find_dir, svt_cdef_filter_block, svt_copy_rect8_8bit_to_16bit,
  * svt_compute_cdef_dist_{8bit,16bit} (common_dsp_rtcd.h:1032-1037, aom_dsp_rtcd.c:97-98). */
 int svt_hip_cdef_search_frame_dev(SvtHipCtx *ctx, int pix_bytes, const void *const d_rec[3], const int rec_stride[3],

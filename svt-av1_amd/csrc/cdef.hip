@@ -344,7 +344,10 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
     // svt_sb_all_skip (EbEncCdef.c:222): nothing to do, table entry stays untouched
     int any = 0;
     for (int b = lane; b < 64; b += 64) { const int by = b >> 3, bx = b & 7; if (by < nby && bx < nbx && !skip8[(8 * fbr + by) * c8 + 8 * fbc + bx]) any = 1; }
-    if (!__any(any)) return;
+    if (!__any(any)) {   // (direction / variance of its blocks are 0 like those of any skipped block: the two outputs are defined everywhere)
+        if (tid < 64 && dir_out) { dir_out[fb * 64 + tid] = 0; var_out[fb * 64 + tid] = 0; }
+        return;
+    }
     stage_tile(tile, TS, rec, rec_stride, w, h, 64 * fbc, 64 * fbr, 64, 64, tid, 256);
     __syncthreads();
     const int damping = pri_damping + cs;  // pli == 0 (EbCdef.c:306-307)

@@ -93,3 +93,104 @@ def test_search_1080p_band(hip, orc):
     exp = cc.orc_search(orc, rec, src, 8, skip8, 4, fb_begin=7 * nh, fb_end=8 * nh)
     assert np.array_equal(got[:, 7 * nh:8 * nh], exp[:, 7 * nh:8 * nh])
     assert got[0].any() and got[1].any()
+
+
+# ------------------------------------------------------------------------------------------------ direction-chart content
+# cdef_common.make_chart_frame: every direction, flat blocks, exact cost ties, 0 / max next to the picture edge, anti-correlated and identical
+# source regions, an all-skip and a one-live-block filter block (what the frames cover is asserted by tests/test_cdef_chart_cpu.py)
+def gpu_search_dirs(hip, rec, src, bd, skip8, pri_damping):
+    """gpu_search plus the search's direction / variance outputs as [nfb][64]; they start as a sentinel."""
+    h, w = rec[0].shape
+    nfb = ((h + 63) // 64) * ((w + 63) // 64)
+    d_rec = [hip.to_device(p) for p in rec]; d_src = [hip.to_device(p) for p in src]
+    d_skip = hip.to_device(skip8)
+    d_mse = hip.to_device(np.zeros((2, nfb, 64), np.uint64))
+    d_dir = hip.to_device(np.full(nfb * 64, 0xEE, np.uint8)); d_var = hip.to_device(np.full(nfb * 64, -7, np.int32))
+    hip.check(hip.L.svt_hip_cdef_search_frame_dev(hip.h, rec[0].itemsize, P3(*[p.value for p in d_rec]), I3(*[p.shape[1] for p in rec]),
+                                                 P3(*[p.value for p in d_src]), I3(*[p.shape[1] for p in src]), w, h, d_skip, pri_damping, bd,
+                                                 d_mse, d_dir, d_var), "cdef search")
+    mse = hip.to_host(d_mse, (2, nfb, 64), np.uint64)
+    dirs = hip.to_host(d_dir, (nfb, 64), np.uint8); var = hip.to_host(d_var, (nfb, 64), np.int32)
+    hip.free(*d_rec, *d_src, d_skip, d_mse, d_dir, d_var)
+    return mse, dirs, var
+
+
+def expected_dirs(orc, luma, bd, skip8):
+    """[nfb][64] direction / variance the search has to report: orc_cdef_find_dir for a live block, 0 for a skipped block and outside the picture."""
+    r8, c8 = skip8.shape
+    nv, nh = (r8 + 7) // 8, (c8 + 7) // 8
+    o_dir, o_var = cc.orc_find_dir_frame(orc, luma, bd)
+    e_dir = np.zeros((nv, nh, 8, 8), np.int64); e_var = np.zeros((nv, nh, 8, 8), np.int64)
+    for by in range(r8):
+        for bx in range(c8):
+            if not skip8[by, bx]:
+                e_dir[by // 8, bx // 8, by % 8, bx % 8] = o_dir[by, bx]; e_var[by // 8, bx // 8, by % 8, bx % 8] = o_var[by, bx]
+    return e_dir.reshape(nv * nh, 64), e_var.reshape(nv * nh, 64)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("size", cc.CHART_SIZES)
+def test_search_table_chart(hip, orc, bd, size):
+    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED)
+    e_dir, e_var = expected_dirs(orc, rec[0], bd, skip8)
+    dead = cc.all_skip_fbs(skip8)
+    assert dead or size[0] < 192
+    for damping in (3, 4, 5, 6):
+        exp = cc.orc_search(orc, rec, src, bd, skip8, damping)
+        got, g_dir, g_var = gpu_search_dirs(hip, rec, src, bd, skip8, damping)
+        assert np.array_equal(got[0], exp[0]), ("Y", bd, damping, np.argwhere(got[0] != exp[0])[:5])
+        assert np.array_equal(got[1], exp[1]), ("UV", bd, damping, np.argwhere(got[1] != exp[1])[:5])
+        for fb in dead:
+            assert not got[:, fb].any()                     # rows of all-skip filter blocks stay untouched
+        assert np.array_equal(g_dir, e_dir), ("dir", bd, damping, np.argwhere(g_dir != e_dir)[:5])
+        assert np.array_equal(g_var, e_var), ("var", bd, damping, np.argwhere(g_var != e_var)[:5])
+    assert got[0].any() and got[1].any() and e_dir.any() and e_var.any()
+
+
+def test_search_table_chart_vs_reference(hip, ref):
+    """A second expectation that does not pass through the oracle: the reference's own svt_cdef_filter_fb + compute_cdef_dist*, per filter block
+    (208 x 144: cdef_common.ref_search_fb cannot stage an 8-sample-wide last filter block)."""
+    for bd, damping in ((8, 3), (8, 6), (10, 4), (10, 5)):
+        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED)
+        got = gpu_search(hip, rec, src, bd, skip8, damping)
+        for fb in range(12):
+            r = cc.ref_search_fb(ref, rec, src, bd, skip8, fb // 4, fb % 4, damping)
+            if r is None:
+                assert not got[:, fb].any()
+                continue
+            assert np.array_equal(r[0], got[0, fb]) and np.array_equal(r[1], got[1, fb]), (bd, damping, fb)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("size", cc.CHART_SIZES)
+def test_apply_frame_chart(hip, orc, bd, size):
+    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED)
+    h, w = rec[0].shape
+    nfb = ((h + 63) // 64) * ((w + 63) // 64)
+    strides = I3(*[p.shape[1] for p in rec])
+    d_in = [hip.to_device(p) for p in rec]; d_src = [hip.to_device(p) for p in src]
+    d_skip = hip.to_device(skip8)
+    sentinel = [np.full_like(p, 77) for p in rec]
+    for damping in (3, 4, 5, 6):
+        ys, uvs = cc.chart_strengths(nfb, damping)          # another filter block gets each strength pair at every damping
+        exp = cc.orc_apply(orc, rec, bd, skip8, ys, uvs, damping)
+        d_ys, d_uvs = hip.to_device(ys), hip.to_device(uvs)
+        # directions recomputed by the apply
+        d_out = [hip.to_device(p) for p in sentinel]; d_dir = hip.empty(nfb * 64)
+        hip.check(hip.L.svt_hip_cdef_apply_frame_dev(hip.h, rec[0].itemsize, P3(*[p.value for p in d_in]), P3(*[p.value for p in d_out]), strides, w, h,
+                                                    d_skip, d_ys, d_uvs, damping, bd, d_dir, None), "cdef apply")
+        # directions / variances handed over from the strength search on the same picture
+        d_mse, d_dir2, d_var = hip.to_device(np.zeros((2, nfb, 64), np.uint64)), hip.empty(nfb * 64), hip.empty(nfb * 64 * 4)
+        hip.check(hip.L.svt_hip_cdef_search_frame_dev(hip.h, rec[0].itemsize, P3(*[p.value for p in d_in]), I3(*[p.shape[1] for p in rec]),
+                                                     P3(*[p.value for p in d_src]), I3(*[p.shape[1] for p in src]), w, h, d_skip, damping, bd,
+                                                     d_mse, d_dir2, d_var), "cdef search")
+        d_out2 = [hip.to_device(p) for p in sentinel]
+        hip.check(hip.L.svt_hip_cdef_apply_frame_dev(hip.h, rec[0].itemsize, P3(*[p.value for p in d_in]), P3(*[p.value for p in d_out2]), strides, w, h,
+                                                    d_skip, d_ys, d_uvs, damping, bd, d_dir2, d_var), "cdef apply (reuse)")
+        for pli in range(3):
+            assert (exp[pli] != rec[pli]).any(), (bd, damping, pli)
+            for form, d_o in (("recomputed", d_out), ("reuse", d_out2)):
+                got = hip.to_host(d_o[pli], rec[pli].shape, rec[pli].dtype)
+                assert np.array_equal(got, exp[pli]), (form, bd, damping, pli, np.argwhere(got != exp[pli])[:5])
+        hip.free(*d_out, *d_out2, d_ys, d_uvs, d_dir, d_dir2, d_var, d_mse)
+    hip.free(*d_in, *d_src, d_skip)

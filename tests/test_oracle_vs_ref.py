@@ -466,6 +466,44 @@ def test_cdef_search_filter_block_level(orc, ref):
                 assert np.array_equal(r[1], mse[1, fbr * nh + fbc]), ("UV", bd, fbr, fbc)
 
 
+def test_cdef_search_chart(orc, ref):
+    """The same on the direction chart (cdef_common.make_chart_frame: every direction, flat blocks, exact cost ties, saturated samples at the picture
+    edge, anti-correlated source), dampings 3-6.  208 x 144: ref_search_fb cannot stage an 8-sample-wide last filter block."""
+    for bd in (8, 10):
+        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED)
+        for damping in (3, 4, 5, 6):
+            mse = cc.orc_search(orc, rec, src, bd, skip8, damping)
+            seen = 0
+            for fb in range(12):
+                r = cc.ref_search_fb(ref, rec, src, bd, skip8, fb // 4, fb % 4, damping)
+                if r is None:
+                    assert not mse[:, fb].any()
+                    continue
+                seen += 1
+                assert np.array_equal(r[0], mse[0, fb]), ("Y", bd, damping, fb)
+                assert np.array_equal(r[1], mse[1, fb]), ("UV", bd, damping, fb)
+            assert seen == 11
+
+
+def test_cdef_apply_chart(orc, ref):
+    """orc_cdef_apply_frame vs svt_cdef_filter_fb driven like svt_av1_cdef_frame (cdef_common.ref_apply_fb) on the direction chart: strengths 0 / 0,
+    luma off / chroma on, chroma off / luma on, 63 / 63 and secondary index 3 each meet another filter block at every damping."""
+    pairs = set()
+    for bd in (8, 10):
+        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED)
+        for damping in (3, 4, 5, 6):
+            ys, uvs = cc.chart_strengths(12, damping)
+            pairs |= set(zip(ys.tolist(), uvs.tolist()))
+            exp = cc.orc_apply(orc, rec, bd, skip8, ys, uvs, damping)
+            got = [p.copy() for p in rec]
+            for fb in range(12):
+                cc.ref_apply_fb(ref, rec, got, bd, skip8, fb // 4, fb % 4, int(ys[fb]), int(uvs[fb]), damping)
+            for pli in range(3):
+                assert (got[pli] != rec[pli]).any()
+                assert np.array_equal(got[pli], exp[pli]), (bd, damping, pli, np.argwhere(got[pli] != exp[pli])[:5])
+    assert {(0, 0), (63, 63), (3, 3)} <= pairs and any(y == 0 and uv for y, uv in pairs) and any(uv == 0 and y for y, uv in pairs)
+
+
 # ----------------------------------------------------------------------- sub-pel convolve / variance
 class _IFP(C.Structure):
     _fields_ = [("filter_ptr", C.c_void_p), ("taps", C.c_uint16), ("subpel_shifts", C.c_uint16), ("interp_filter", C.c_uint8)]

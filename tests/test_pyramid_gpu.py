@@ -64,3 +64,59 @@ def test_sad_loop_batch(hip, pkg, orc):
     assert np.array_equal(hip.to_host(d_sad, (n,), np.uint32), e_sad)
     assert np.array_equal(hip.to_host(d_xy, (n, 2), np.int16), e_xy)
     hip.free(d_src, d_ref, d_S, d_sad, d_xy)
+
+
+# (bw, bh, sa_w, sa_h, row_step): every lane-split factor P of sad_loop_fast (1, 2, 4, 8), both LDS stride choices, multi-tile windows, row_step 2;
+# the last two put the un-split 32-wide and a 64-row 16-wide block on a full tile (the longest runs between two flushes of the packed partial sums)
+SATURATED_SHAPES = [(16, 16, 16, 16, 1), (16, 16, 64, 64, 1), (32, 32, 16, 16, 1), (32, 32, 40, 24, 2), (64, 64, 8, 5, 1), (64, 64, 64, 64, 1),
+                    (64, 64, 16, 16, 2), (16, 16, 240, 60, 1), (32, 32, 64, 64, 1), (16, 64, 64, 64, 1)]
+
+
+def test_sad_loop_saturated(hip, pkg, orc):
+    """Source block all 0 against a window all 255 (and the mirror image): every absolute difference is 255, the largest a packed 16-bit partial SAD
+    can meet before it is flushed.  Three searches per shape and polarity: nothing planted (all candidates tie at 255 * bw * bh / row_step, the first
+    wins), a whole matching block planted in the last tile of the window (unique minimum 0), one matching sample planted where only the last
+    candidate sees it (unique minimum one 255 short of saturation)."""
+    rng = np.random.default_rng(9)
+    SW, RW = 80, 328                                   # plane strides (multiples of 4: the fast path)
+    jobs, e_flat = [], []
+    src = [rng.integers(0, 256, (len(SATURATED_SHAPES) * 3 * 72, SW), dtype=np.uint8) for _ in range(2)]
+    ref = [rng.integers(0, 256, (len(SATURATED_SHAPES) * 3 * 136, RW), dtype=np.uint8) for _ in range(2)]
+    for si, (bw, bh, saw, sah, rs) in enumerate(SATURATED_SHAPES):
+        rows = bh // rs
+        for variant in range(3):
+            k = 3 * si + variant
+            sx, sy, rx, ry = 3 + k % 5, 72 * k + 2, 1 + k % 7, 136 * k + 3          # byte-misaligned on both sides
+            for pol in (0, 1):                          # 0: source 0 / window 255, 1: the mirror image
+                lo, hi = (0, 255) if pol == 0 else (255, 0)
+                src[pol][sy:sy + bh, sx:sx + bw] = lo
+                win = ref[pol][ry:ry + sah + bh - 1, rx:rx + saw + bw - 1]
+                win[:] = hi
+                if variant == 1:                        # candidate (cx, cy) in the last 64 x 64 tile, not its last one
+                    cx, cy = max(saw - 2, 0), max(sah - 2, 0)
+                    win[cy:cy + bh, cx:cx + bw] = lo
+                elif variant == 2:                      # the window's last sampled sample: only candidate (saw - 1, sah - 1) reads it
+                    win[sah - 1 + (rows - 1) * rs, saw + bw - 2] = lo
+            jobs.append(pkg.SadLoop(sx, sy, rx, ry, bw, bh, saw, sah, rs, 0))
+            e_flat.append((255 * bw * rows, 0, 0) if variant == 0 else (0, cx, cy) if variant == 1 else (255 * (bw * rows - 1), saw - 1, sah - 1))
+    n = len(jobs)
+    S = (pkg.SadLoop * n)(*jobs)
+    d_S = hip.to_device(np.frombuffer(bytes(S), np.uint8))
+    for pol in (0, 1):
+        e_sad = np.zeros(n, np.uint32); e_xy = np.zeros((n, 2), np.int16)
+        for i, j in enumerate(jobs):
+            rs = j.row_step
+            best = C.c_uint64(0); xc = C.c_int16(-3); yc = C.c_int16(-4)
+            orc.orc_sad_loop(C.c_void_p(src[pol].ctypes.data + j.src_y * SW + j.src_x), SW * rs, C.c_void_p(ref[pol].ctypes.data + j.ref_y * RW + j.ref_x),
+                             RW * rs, j.bh // rs, j.bw, C.byref(best), C.byref(xc), C.byref(yc), RW, C.c_int16(j.sa_w), C.c_int16(j.sa_h))
+            e_sad[i] = best.value; e_xy[i] = (xc.value, yc.value)
+        # the oracle is not the only witness: the planted content fixes every result in closed form
+        assert e_sad.tolist() == [e[0] for e in e_flat] and e_xy.tolist() == [[e[1], e[2]] for e in e_flat], pol
+        d_src, d_ref = hip.to_device(src[pol]), hip.to_device(ref[pol])
+        d_sad, d_xy = hip.empty(n * 4), hip.to_device(np.tile(np.array([-3, -4], np.int16), (n, 1)))
+        hip.check(hip.L.svt_hip_sad_loop_batch_dev(hip.h, d_src, SW, d_ref, RW, d_S, n, d_sad, d_xy))
+        g_sad, g_xy = hip.to_host(d_sad, (n,), np.uint32), hip.to_host(d_xy, (n, 2), np.int16)
+        assert np.array_equal(g_sad, e_sad), (pol, [(SATURATED_SHAPES[i // 3], i % 3, int(g_sad[i]), int(e_sad[i])) for i in np.flatnonzero(g_sad != e_sad)[:6]])
+        assert np.array_equal(g_xy, e_xy), (pol, [(SATURATED_SHAPES[i // 3], i % 3, g_xy[i].tolist(), e_xy[i].tolist()) for i in np.flatnonzero((g_xy != e_xy).any(axis=1))[:6]])
+        hip.free(d_src, d_ref, d_sad, d_xy)
+    hip.free(d_S)

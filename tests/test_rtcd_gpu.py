@@ -11,6 +11,7 @@ import os
 
 from conftest import ROOT, ptr
 import txfm_common as tc
+import cdef_common as cc
 
 pytestmark = pytest.mark.gpu
 
@@ -469,6 +470,28 @@ def test_per_call_forms_vs_reference_c(rtcd, ref):
                         for fn, o in ((ref.svt_cdef_filter_block_c, e), (rtcd.svt_cdef_filter_block, g)):
                             fn(_vp(o) if d8 else None, None if d8 else _vp(o), 12, _vp(stage, off), pri, sec, de, pd, sd, bsize, cs)
                         assert np.array_equal(e, g), ("filter_block", cs, y, x, bsize, pri, sec, d8)
+        # ... and one cell of every direction-chart kind (cdef_common.chart_cell: the eight directions as full-range stripes and as random levels, exact
+        # 1/7, 2/6, 3/5 cost ties, flat cells, checkerboards, impulses), once inside the noise and once with CDEF_VERY_LARGE on its left and top
+        dirs_seen = set()
+        for kind, cell in cc.chart_kind_cells(8 + cs):   # (a generator of its own: the draws of the sections below stay what they were)
+            for (y, x) in ((20, 40), (5, 6)):
+                img = stage.copy(); img[y:y + 8, x:x + 8] = cell.astype(np.uint16)
+                off = (y * 144 + x) * 2
+                ve, vg = C.c_int32(), C.c_int32()
+                de = ref.svt_cdef_find_dir_c(_vp(img, off), 144, C.byref(ve), cs); dg = rtcd.svt_cdef_find_dir(_vp(img, off), 144, C.byref(vg), cs)
+                assert (de, ve.value) == (dg, vg.value), ("find_dir", cs, kind, y, x)
+                if kind[0] in ("bin", "lvl"): assert de == kind[1], (kind, de)       # constant along d: d reaches the upper bound of every cost
+                if kind[0] == "tie": assert de == kind[1] and (ve.value == 0) == (de == 2), (kind, de)    # cost[d] == cost[8 - d]: the lower index wins (2 / 6 are orthogonal: var 0)
+                if kind[0] == "flat": assert (de, ve.value) == (0, 0), kind
+                dirs_seen.add(de)
+                d8 = cs == 0
+                for bsize in (0, 3):
+                    for (pri, sec, pd, sd) in ((0, 0, 3, 3), (4 << cs, 2 << cs, 6 + cs, 5 + cs), (15 << cs, 4 << cs, 5 + cs, 5 + cs), (0, 1 << cs, 4 + cs, 3 + cs), (7 << cs, 0, 3 + cs, 3 + cs)):
+                        e = np.zeros((8, 12), np.uint8 if d8 else np.uint16); g = e.copy()
+                        for fn, o in ((ref.svt_cdef_filter_block_c, e), (rtcd.svt_cdef_filter_block, g)):
+                            fn(_vp(o) if d8 else None, None if d8 else _vp(o), 12, _vp(img, off), pri, sec, de, pd, sd, bsize, cs)
+                        assert np.array_equal(e, g), ("filter_block", cs, kind, y, x, bsize, pri, sec)
+        assert dirs_seen == set(range(8))
     # --- residual
     for dt, fr, fh in ((np.uint8, ref.svt_residual_kernel8bit_c, rtcd.svt_residual_kernel8bit), (np.uint16, ref.svt_residual_kernel16bit_c, rtcd.svt_residual_kernel16bit)):
         a = rng.integers(0, 256 if dt == np.uint8 else 1024, (70, 90)).astype(dt); b = rng.integers(0, 256 if dt == np.uint8 else 1024, (70, 100)).astype(dt)
