@@ -145,3 +145,99 @@ def oracle_edges(orc, f, w, h, lf, pad_right=0, pad_bottom=0, sb_size=64):
         orc.orc_dlf_build_edges(ptr(summ), cols, rows, plane, ss, ss, pw, ph, fw, fh, ptr(ev), ptr(eh))
         edges.append((ev, eh))
     return summ, edges, lvl
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------------
+# Inputs of the pixel-domain SSE / SAD / variance reducers at the edges of their forms (block_sse_kernel, block_sse_rows_kernel, plane_sse_kernel, the
+# block SAD / variance kernels).  The GPU tests and tests/test_reducers_ref_cpu.py build their inputs from these functions, so what the CPU test proves
+# about the inputs holds for the GPU runs.
+SSE_LIST_THRESHOLD = 2048      # svt_hip_launch_block_sse: lists of up to this many pairs take the row-sliced form, longer ones one wave per pair
+SSE_SMALL_W, SSE_SMALL_H = (1, 4, 7, 8, 33, 64, 128), (1, 4, 5, 16, 128)
+SSE_A_SHAPE, SSE_B_SHAPE = (800, 840), (810, 900)
+# restoration-unit rectangles as the loop-filter bridge builds them (up to 1.5 x a 256-sample unit, the 8-row stripe offset on top): (a_x, a_y, b_x, b_y, w, h).
+# Heights above 256 take the rows form's second trip, widths above 64 its lane loop; 257 / 300 / 33 / 41 are no multiple of a wave's 8 rows; odd columns.
+SSE_RECTS = [(17, 200, 40, 150, 384, 392), (401, 3, 333, 500, 320, 257), (455, 300, 601, 100, 70, 300), (839, 400, 0, 0, 1, 300), (3, 700, 811, 9, 65, 33),
+             (451, 750, 515, 760, 384, 41)]
+SSE_RECT_IDENTICAL = (600, 320, 701, 405, 70, 300)      # b holds a copy of a here: SSE 0
+SSE_RECT_SATURATED = (0, 0, 1, 8, 384, 392)             # a all 0, b all max: SSE w * h * max^2 > 2^32 at every depth
+
+
+def numpy_sse(a, b, pairs):
+    """sum (a - b)^2 of every pair in int64: the plain restatement next to the oracle's orc_plane_sse"""
+    return np.array([int(((a[ay:ay + h, ax:ax + w].astype(np.int64) - b[by:by + h, bx:bx + w].astype(np.int64)) ** 2).sum()) for (ax, ay, bx, by, w, h) in pairs], np.uint64)
+
+
+def oracle_sse(a, b, pairs):
+    orc = oracle()
+    orc.orc_plane_sse.restype = C.c_uint64
+    sa, sb = a.shape[1], b.shape[1]
+    return np.array([orc.orc_plane_sse(a.itemsize, C.c_void_p(a.ctypes.data + (ay * sa + ax) * a.itemsize), sa, C.c_void_p(b.ctypes.data + (by * sb + bx) * b.itemsize), sb, w, h)
+                     for (ax, ay, bx, by, w, h) in pairs], np.uint64)
+
+
+_sse_cases = {}
+
+
+def sse_case(bd):
+    """-> dict: planes a / b (bd 8: uint8; 10, 12: uint16 holding bd-bit values), and the pair lists of tests/test_distortion_gpu.py with their expected sums
+    (`exp_*`, the oracle's, asserted equal to numpy's):
+      small       2051 small blocks (just above the threshold, not a multiple of 4: the list form's last workgroup holds three pairs)
+      rects       the restoration-unit rectangles + the identical pair + the saturated pair (8 pairs: the rows form)
+      long        the rectangles inside the small blocks (2059 pairs: the list form on 150 000-sample blocks)
+    Built once per depth and shared; nobody writes to it."""
+    if bd in _sse_cases: return _sse_cases[bd]
+    rng = np.random.default_rng(220 + bd)
+    mx = (1 << bd) - 1
+    dt = np.uint8 if bd == 8 else np.uint16
+    a = rng.integers(0, mx + 1, SSE_A_SHAPE).astype(dt); b = rng.integers(0, mx + 1, SSE_B_SHAPE).astype(dt)
+    ax, ay, bx, by, w, h = SSE_RECT_SATURATED
+    a[ay:ay + h, ax:ax + w] = 0; b[by:by + h, bx:bx + w] = mx
+    ax, ay, bx, by, w, h = SSE_RECT_IDENTICAL
+    b[by:by + h, bx:bx + w] = a[ay:ay + h, ax:ax + w]
+    small = []
+    for i in range(SSE_LIST_THRESHOLD + 3):
+        w = SSE_SMALL_W[i % len(SSE_SMALL_W)] if i < 35 else int(rng.choice(SSE_SMALL_W))       # every width x height at least once
+        h = SSE_SMALL_H[i // len(SSE_SMALL_W)] if i < 35 else int(rng.choice(SSE_SMALL_H))
+        small.append((int(rng.integers(0, a.shape[1] - w + 1)), int(rng.integers(0, a.shape[0] - h + 1)),
+                      int(rng.integers(0, b.shape[1] - w + 1)), int(rng.integers(0, b.shape[0] - h + 1)), w, h))
+    rects = SSE_RECTS[:3] + [SSE_RECT_IDENTICAL] + SSE_RECTS[3:] + [SSE_RECT_SATURATED]
+    long_ = small[:1000] + rects + small[1000:]
+    case = dict(bd=bd, max=mx, a=a, b=b, small=small, rects=rects, long=long_, rects_at=1000)
+    for name in ("small", "rects", "long"):
+        for (ax, ay, bx, by, w, h) in case[name]:      # the kernels check no bounds: the lists must stay inside the planes
+            assert 0 <= ax and ax + w <= a.shape[1] and 0 <= ay and ay + h <= a.shape[0] and 0 <= bx and bx + w <= b.shape[1] and 0 <= by and by + h <= b.shape[0]
+        exp = oracle_sse(a, b, case[name])
+        assert np.array_equal(exp, numpy_sse(a, b, case[name])), name
+        case["exp_" + name] = exp
+    for v in case.values():
+        if isinstance(v, np.ndarray): v.setflags(write=False)
+    _sse_cases[bd] = case
+    return case
+
+
+def blk_pairs(pairs):
+    """the list as the bytes of an SvtHipBlkPair array"""
+    P = (pkg.BlkPair * len(pairs))(*[pkg.BlkPair(*p) for p in pairs])
+    return np.frombuffer(bytes(P), np.uint8)
+
+
+PLANE_SSE_SATURATED_SIZES = ((333, 77), (1030, 17))    # 1030: two column groups of 1024, the second 6 samples wide; 77 / 17 rows: a ragged last group of 8
+
+
+def saturated_planes(mx, w, h):
+    """test_plane_sse's planes (offset origins (3, 2) / (5, 1), random surroundings) with the compared w x h region all 0 in a and all mx in b
+    -> a, b, the closed form w * h * mx^2.  A lane of plane_sse_kernel then sums 8 * 4 * mx^2 (2^29 at 12 bits) into its u32 partial."""
+    rng = np.random.default_rng(mx + w)
+    dt = np.uint8 if mx < 256 else np.uint16
+    a = rng.integers(0, mx + 1, (h + 5, w + 9)).astype(dt); b = rng.integers(0, mx + 1, (h + 3, w + 20)).astype(dt)
+    a[2:2 + h, 3:3 + w] = 0; b[1:1 + h, 5:5 + w] = mx
+    return a, b, w * h * mx * mx
+
+
+def saturated_block_pair(bd):
+    """test_block_sad_and_variance's extra pair: a 128 x 128 block lying wholly on all-max (plane a, 256 x 320) against all-0 (plane b, 256 x 352) content
+    -> (rows, columns) of the region in a and in b, the pair, closed forms (sad, variance, sse).  The 10-bit sse is svt_aom_highbd_10_variance's
+    ROUND_POWER_OF_TWO(sse, 4)."""
+    mx = (1 << bd) - 1
+    sse = mx * mx * 16384
+    return (slice(128, 256), slice(192, 320)), (slice(128, 256), slice(224, 352)), (192, 128, 224, 128, 128, 128), (mx * 16384, 0, sse if bd == 8 else (sse + 8) >> 4)

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import ptr
 import txfm_common as tc
+import me_common as mc
 
 pytestmark = pytest.mark.gpu
 W, H, BD = 3840, 2160, 10
@@ -176,3 +177,25 @@ def test_hbd_windowed_search(hip, pkg, orc):
     hip.free(d_c, d_r, d_S, d_sad, d_xy)
     assert np.array_equal(g_sad, e_sad) and np.array_equal(g_xy, e_xy), np.argwhere(g_sad != e_sad)[:5]
     assert (e_xy[0] == (0, 0)).all() and e_sad.min() < 0xffffff
+
+
+@pytest.mark.parametrize("mx", [1023, 4095])
+def test_hbd_windowed_search_saturated(hip, orc, mx):
+    """Block all 0 against a window all mx and the mirror image, at 10 and 12 bits: a 12-bit 64 x 64 block gives 0xfff000, 4095 short of the reference's
+    initial best 0xffffff.  The LDS form (block 16 / 32 / 48 / 64 wide, areas 8 x 1, 64 x 64, 24 x 40, dword-aligned and odd-column sources) and the
+    generic form (row_step 2, area widths 9 and 5, an 8 x 8 block, a 72-wide area); per shape nothing planted (the first candidate wins the tie), a
+    matching block (0 there), one matching sample that only the last candidate reads.  Kernel = oracle = closed form."""
+    assert all(mc.sad16_takes_lds_form(*s[:5]) for s in mc.SAD16_LDS_SHAPES) and not any(mc.sad16_takes_lds_form(*s[:5]) for s in mc.SAD16_GENERIC_SHAPES)
+    for pol in (0, 1):
+        src, ref, S, closed = mc.saturated_sad16(mx, pol)
+        n = len(S)
+        e_sad, e_xy = mc.oracle_sad16(orc, src, ref, S)
+        c_sad, c_xy = np.array([c[0] for c in closed], np.uint32), np.array([c[1:] for c in closed], np.int16)
+        assert np.array_equal(e_sad, c_sad) and np.array_equal(e_xy, c_xy), pol
+        d_c, d_r, d_S = hip.to_device(src), hip.to_device(ref), hip.to_device(np.frombuffer(bytes(S), np.uint8).copy())
+        d_sad, d_xy = hip.to_device(np.zeros(n, np.uint32)), hip.to_device(np.full((n, 2), -7, np.int16))
+        hip.check(hip.L.svt_hip_sad_loop16_batch_dev(hip.h, d_c, src.shape[1], d_r, ref.shape[1], d_S, n, d_sad, d_xy), "sad loop 16")
+        g_sad, g_xy = hip.to_host(d_sad, (n,), np.uint32), hip.to_host(d_xy, (n, 2), np.int16)
+        hip.free(d_c, d_r, d_S, d_sad, d_xy)
+        assert np.array_equal(g_sad, e_sad), (pol, [(mc.SAD16_SHAPES[i // 3], i % 3, hex(g_sad[i]), hex(e_sad[i])) for i in np.flatnonzero(g_sad != e_sad)[:6]])
+        assert np.array_equal(g_xy, e_xy), (pol, [(mc.SAD16_SHAPES[i // 3], i % 3, g_xy[i].tolist(), e_xy[i].tolist()) for i in np.flatnonzero((g_xy != e_xy).any(axis=1))[:6]])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ptr
+import dlf_common as dc
 
 pytestmark = pytest.mark.gpu
 
@@ -60,8 +61,10 @@ def test_block_sad_and_variance(hip, pkg, orc, bd):
     dt = np.uint8 if bd == 8 else np.uint16
     a = rng.integers(0, 1 << bd, (256, 320)).astype(dt); b = rng.integers(0, 1 << bd, (256, 352)).astype(dt)
     a[:64, :64] = (1 << bd) - 1; b[:64, :64] = 0; b[64:128, :64] = a[64:128, :64]
+    ra, rb, sat_pair, sat_closed = dc.saturated_block_pair(bd)      # a 128 x 128 block wholly on all-max against all-0 content: the last pair
+    a[ra] = (1 << bd) - 1; b[rb] = 0
     sizes = [(4, 4), (8, 8), (16, 16), (16, 32), (32, 16), (64, 64), (8, 32), (64, 16), (128, 128), (4, 16)]
-    n = 120
+    n = 121
     pairs = (pkg.BlkPair * n)(); e_sad = np.zeros(n, np.uint32); e_var = np.zeros(n, np.uint32); e_sse = np.zeros(n, np.uint32)
     orc.orc_nxm_sad.restype = C.c_uint32; orc.orc_sad_16b.restype = C.c_uint32
     orc.orc_variance.restype = C.c_uint32; orc.orc_variance_hbd10.restype = C.c_uint32
@@ -69,6 +72,7 @@ def test_block_sad_and_variance(hip, pkg, orc, bd):
         w, h = sizes[i % len(sizes)]
         ax, ay = (0, 0) if i < 10 else (int(rng.integers(0, 320 - w)), int(rng.integers(0, 256 - h)))
         bx, by_ = (0, 0 if i % 2 == 0 else 64) if i < 10 else (int(rng.integers(0, 352 - w)), int(rng.integers(0, 256 - h)))
+        if i == n - 1: ax, ay, bx, by_, w, h = sat_pair
         pairs[i] = pkg.BlkPair(ax, ay, bx, by_, w, h)
         pa = C.c_void_p(a.ctypes.data + (ay * 320 + ax) * a.itemsize); pb = C.c_void_p(b.ctypes.data + (by_ * 352 + bx) * b.itemsize)
         s = C.c_uint32(0)
@@ -86,6 +90,7 @@ def test_block_sad_and_variance(hip, pkg, orc, bd):
     assert np.array_equal(hip.to_host(d_s, (n,), np.uint32), e_sad)
     assert np.array_equal(hip.to_host(d_v, (n,), np.uint32), e_var)
     assert np.array_equal(hip.to_host(d_e, (n,), np.uint32), e_sse)
+    assert (int(e_sad[-1]), int(e_var[-1]), int(e_sse[-1])) == sat_closed       # the oracle agrees with the closed form, so the kernel does too
     hip.free(d_a, d_b, d_p, d_s, d_v, d_e)
 
 

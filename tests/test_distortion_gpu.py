@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ptr
+import dlf_common as dc
 
 pytestmark = pytest.mark.gpu
 
@@ -47,3 +48,57 @@ def test_block_sse(hip, pkg, orc, bd):
     hip.check(hip.L.svt_hip_block_sse_batch_dev(hip.h, a.itemsize, d_a, 420, d_b, 400, d_p, n, d_o))
     assert np.array_equal(hip.to_host(d_o, (n,), np.uint64), exp)
     hip.free(d_a, d_b, d_p, d_o)
+
+
+def _block_sse(hip, d_a, a, d_b, b, pairs):
+    """svt_hip_block_sse_batch_dev on `pairs`, the output buffer pre-filled with 0xA5 bytes (a pair's sum must not depend on what the buffer held)"""
+    n = len(pairs)
+    d_p, d_o = hip.to_device(dc.blk_pairs(pairs)), hip.to_device(np.full(n * 8, 0xA5, np.uint8))
+    hip.check(hip.L.svt_hip_block_sse_batch_dev(hip.h, a.itemsize, d_a, a.shape[1], d_b, b.shape[1], d_p, n, d_o))
+    got = hip.to_host(d_o, (n,), np.uint64)
+    hip.free(d_p, d_o)
+    return got
+
+
+def _mismatch(got, exp, pairs):
+    return [(int(i), pairs[i], int(got[i]), int(exp[i])) for i in np.flatnonzero(got != exp)[:6]]
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_block_sse_both_forms(hip, bd):
+    """One list of 2051 small blocks through the list form (block_sse_kernel: one wave per pair, a last workgroup of three pairs) and its first 2048
+    entries through the rows form (block_sse_rows_kernel); n = 2049 puts a single pair into the last workgroup.  Every run equals the oracle and numpy,
+    the shared entries are identical between the forms."""
+    c = dc.sse_case(bd)
+    T = dc.SSE_LIST_THRESHOLD
+    pairs, exp = c["small"], c["exp_small"]
+    assert len(pairs) == T + 3
+    d_a, d_b = hip.to_device(c["a"]), hip.to_device(c["b"])
+    full = _block_sse(hip, d_a, c["a"], d_b, c["b"], pairs)
+    rows = _block_sse(hip, d_a, c["a"], d_b, c["b"], pairs[:T])
+    one = _block_sse(hip, d_a, c["a"], d_b, c["b"], pairs[:T + 1])
+    hip.free(d_a, d_b)
+    assert np.array_equal(full[-3:], exp[-3:]), _mismatch(full[-3:], exp[-3:], pairs[-3:])      # the short final workgroup
+    assert np.array_equal(full, exp), _mismatch(full, exp, pairs)
+    assert np.array_equal(rows, exp[:T]), _mismatch(rows, exp[:T], pairs)
+    assert np.array_equal(one, exp[:T + 1]), _mismatch(one, exp[:T + 1], pairs)
+    assert np.array_equal(full[:T], rows) and np.array_equal(one[:T], rows)
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_block_sse_restoration_rectangles(hip, bd):
+    """Restoration-unit rectangles as the loop-filter bridge passes them (up to 384 x 392, odd columns, heights that are no multiple of 8), as a short list
+    (rows form: its second trip of 256 rows, widths above 64) and inside a list of 2059 pairs (list form on 150 000-sample blocks).  The identical pair
+    reads 0 although the buffer was pre-filled, the all-0 against all-max pair reads w * h * max^2 > 2^32."""
+    c = dc.sse_case(bd)
+    d_a, d_b = hip.to_device(c["a"]), hip.to_device(c["b"])
+    short = _block_sse(hip, d_a, c["a"], d_b, c["b"], c["rects"])
+    long_ = _block_sse(hip, d_a, c["a"], d_b, c["b"], c["long"])
+    hip.free(d_a, d_b)
+    assert np.array_equal(short, c["exp_rects"]), _mismatch(short, c["exp_rects"], c["rects"])
+    assert np.array_equal(long_, c["exp_long"]), _mismatch(long_, c["exp_long"], c["long"])
+    zi, si = c["rects"].index(dc.SSE_RECT_IDENTICAL), c["rects"].index(dc.SSE_RECT_SATURATED)
+    sat = 384 * 392 * c["max"] ** 2
+    assert sat > 1 << 32
+    for got in (short, long_[c["rects_at"]:c["rects_at"] + len(c["rects"])]):
+        assert int(got[zi]) == 0 and int(got[si]) == sat

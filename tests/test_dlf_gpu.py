@@ -89,6 +89,18 @@ def test_plane_sse(hip, orc, bd):
         got = int(hip.to_host(d_s, (1,), np.uint64)[0])
         hip.free(d_a, d_b, d_s)
         assert got == exp, (bd, w, h, got, exp)
+    # all 0 against all max: a lane's u32 partial holds 8 * 4 * max^2 (2^29 at 12 bits); two column groups, a ragged last row group
+    for mx in ((255,) if bd == 8 else (1023, 4095)):
+        for (w, h) in dc.PLANE_SSE_SATURATED_SIZES:
+            a, b, closed = dc.saturated_planes(mx, w, h)
+            exp = orc.orc_plane_sse(a.itemsize, C.c_void_p(a.ctypes.data + (2 * a.shape[1] + 3) * a.itemsize), a.shape[1],
+                                    C.c_void_p(b.ctypes.data + (1 * b.shape[1] + 5) * b.itemsize), b.shape[1], w, h)
+            d_a, d_b, d_s = hip.to_device(a), hip.to_device(b), hip.empty(8)
+            hip.check(hip.L.svt_hip_plane_sse_dev(hip.h, a.itemsize, C.c_void_p(d_a.value + (2 * a.shape[1] + 3) * a.itemsize), a.shape[1],
+                                                  C.c_void_p(d_b.value + (1 * b.shape[1] + 5) * b.itemsize), b.shape[1], w, h, d_s), "sse")
+            got = int(hip.to_host(d_s, (1,), np.uint64)[0])
+            hip.free(d_a, d_b, d_s)
+            assert got == exp == closed == w * h * mx * mx, (mx, w, h, got, exp, closed)
 
 
 @pytest.mark.parametrize("bd,mode", [(8, 1), (8, 3), (10, 3)])

@@ -68,6 +68,43 @@ def test_waves_per_sb_variants(hip, orc):
         _run(hip, orc, cur, refp, w, h, 64, 64, 0)
 
 
+def _saturated(hip, orc, window, sub, strip=False):
+    pad = mc.synth.PAD
+    for pol in (0, 1):
+        for variant in range(3):
+            cur_p, ref_p, stride, sbs, (c_sad, c_mv), closed_for = mc.saturated_case(orc, window, variant, pol, sub, strip)
+            o_sad, o_mv = mc.saturated_oracle(orc, window, variant, pol, sub, strip)
+            g_sad, g_mv = mc.hip_frame(hip, cur_p, ref_p, stride, pad, sbs, sub)
+            tag = (window, pol, variant)
+            assert np.array_equal(g_sad, o_sad), (tag, [(i, pu, hex(g_sad[i, pu]), hex(o_sad[i, pu])) for i, pu in np.argwhere(g_sad != o_sad)[:6]])
+            assert np.array_equal(g_mv, o_mv), (tag, [(i, pu, hex(g_mv[i, pu]), hex(o_mv[i, pu])) for i, pu in np.argwhere(g_mv != o_mv)[:6]])
+            for i in closed_for:
+                assert np.array_equal(g_sad[i], c_sad[i]) and np.array_equal(g_mv[i], c_mv[i]), (tag, i)
+            if variant == 1:       # the planted superblock: a unique 0 of the 64x64 PU at the last candidate
+                d = sbs[0]
+                assert g_sad[0, 0] == 0 and g_mv[0, 0] == mc.mv_word(d.x_origin + d.width - 1, d.y_origin + d.height - 1), tag
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("sub", [0, 1])
+def test_me_saturated(hip, orc, sub, waves):
+    """Source superblock all 0 against a window all 255 and the mirror image: every packed 16-bit partial sum at its largest (16x16 PUs: 256 * 255 = 0xFF00,
+    keys 0xFF00xxxx just under the initial 0xFFFFFFFF; SUB: 4 * 8 * 255 * 2 per 8x8).  Nothing planted / a matching superblock / one matching sample at
+    the last candidate, for one group, one tile, several ragged tiles and the narrow kernel, at every wave count.  Kernel = oracle = closed form."""
+    try:
+        hip.check(hip.L.svt_hip_me_set_waves_per_sb(hip.h, waves))
+        for window in mc.SATURATED_WINDOWS:
+            _saturated(hip, orc, window, sub)
+    finally:
+        hip.check(hip.L.svt_hip_me_set_waves_per_sb(hip.h, 4))      # the context's default
+
+
+@pytest.mark.parametrize("sub", [0, 1])
+def test_me_saturated_strip(hip, orc, sub):
+    """The same content on one 336 x 200 window (67 200 candidates: the strip-walking instance, the last candidate in its second strip)."""
+    _saturated(hip, orc, mc.SATURATED_STRIP_WINDOW, sub, strip=True)
+
+
 def test_1080p_row_band_vs_oracle_and_properties(hip, orc):
     """Full 1080p frame on the GPU; the oracle checks one SB row band bit-exactly (it needs
     ~18 ms/SB), the rest through size-independent properties: SAD(64x64) equals the sum of its four
