@@ -966,7 +966,8 @@ int svt_hip_md_halfpel_grid_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, in
  *             (start_m1 = 1, the corner itself passes through unfiltered as in the reference) or at sample 0; npx is clamped to 129, up_npx to 16.
  *             A job whose tx_size (> 18), mode (> 12) or angle_delta (outside -3 .. 3) is out of range is skipped: nothing is written for it.
  *   d_dst   : destination plane (pix_bytes per sample, stride in samples); a job writes its W x H block at (dst_x, dst_y).  Jobs must not overlap.
- * pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10.  CfL, filter-intra, palette and intra block copy are not covered. */
+ * pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10.  Chroma-from-luma and filter-intra have entry points of their own below; palette and intra block copy are
+ * not covered. */
 typedef struct {
     uint32_t edge_off;            /* first sample of this job's edge record in d_edges */
     int32_t  dst_x, dst_y;        /* top-left sample of the block in the destination plane */
@@ -983,6 +984,47 @@ typedef struct {
 } SvtHipIntraJob;
 int svt_hip_intra_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_edges, const SvtHipIntraJob *d_jobs, int njobs, void *d_dst,
                                     int dst_stride);
+/* Chroma-from-luma (UV_CFL_PRED) for a list of 4:2:0 chroma blocks in one launch: svt_cfl_luma_subsampling_420_{lbd,hbd} -> svt_subtract_average ->
+ * svt_cfl_predict_{lbd,hbd} (Common/Codec/EbIntraPrediction.c:349-402, Common/C_DEFAULT/cfl_c.c), as cfl_prediction / av1_cost_calc_cfl compose them
+ * (Encoder/Codec/EbProductCodingLoop.c:2723-3230).  Per job: the 2W x 2H luma area at (luma_x, luma_y) is read, (a + b + c + d) << 1 per chroma sample, the block
+ * average (sum + W H / 2) >> log2(W H) subtracted, and for each selected plane clip(pred + ROUND_POWER_OF_TWO_SIGNED(alpha_q3 * ac, 6), bd) written at
+ * (dst_x, dst_y).  pred is the sample already in the chroma plane at that position (the in-place form: the reference passes pred == dst), or, with dc_from_edges,
+ * the DC predictor of the plane's edge record -- the dc_pred[left][above] selection of mode 0 of svt_hip_intra_predict_batch_dev -- so that a CfL block is one launch.
+ *   d_luma  : the luma plane the areas are read from (pix_bytes per sample, stride in samples); areas of different jobs may overlap
+ *   d_edges : edge records in the layout of svt_hip_intra_predict_batch_dev; read only by jobs with dc_from_edges (edge_off[0] Cb, edge_off[1] Cr)
+ *   d_cb / d_cr : the two chroma planes, one stride.  One of them may be NULL: that plane is then written by no job, whatever plane_mask says.
+ *   d_ac    : NULL, or [njobs][32][32] int16: job i's pred_buf_q3 after the average subtraction, its W x H corner at row stride 32 (CFL_BUF_LINE); nothing else
+ *             of the slot is written
+ * 4:2:0 only.  A job whose tx_size is not one of the 14 shapes with both sides <= 32 (CFL_SUB_AVG_FN), or with an |alpha_q3| above 16, writes nothing.  Jobs must
+ * not overlap in the chroma planes.  pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10.  Stream-ordered and asynchronous: no host synchronisation, no
+ * allocation, no read-back. */
+typedef struct {
+    int32_t  luma_x, luma_y;      /* top-left sample of the 2W x 2H luma area (rounded by the caller the way cfl_prediction does) */
+    int32_t  dst_x, dst_y;        /* top-left sample of the block in both chroma planes */
+    uint32_t edge_off[2];         /* dc_from_edges: first sample of the Cb / Cr edge record in d_edges */
+    int8_t   alpha_q3[2];         /* -16..16 for Cb / Cr (cfl_idx_to_alpha); 0 is legal */
+    uint8_t  tx_size;             /* TxSize of the chroma block, both sides <= 32 */
+    uint8_t  plane_mask;          /* bit 0 = Cb, bit 1 = Cr */
+    uint8_t  dc_from_edges;       /* 0: pred is what the chroma plane holds; 1: pred is the DC predictor of the edge record */
+    uint8_t  dc_have;             /* dc_from_edges: bit 0 = left available, bit 1 = above available */
+    uint8_t  reserved[2];
+} SvtHipCflJob;
+int svt_hip_cfl_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_luma, int luma_stride, const void *d_edges, const SvtHipCflJob *d_jobs,
+                                  int njobs, void *d_cb, void *d_cr, int chroma_stride, int16_t *d_ac);
+/* Filter-intra (use_filter_intra: the five recursive 4x2-patch predictors FILTER_DC, FILTER_V, FILTER_H, FILTER_D157, FILTER_PAETH) for a list of blocks in one
+ * launch: svt_av1_filter_intra_predictor_c (Common/C_DEFAULT/filterintra_c.c) / highbd_filter_intra_predictor (Common/Codec/EbIntraPrediction.c:2492).  The edge
+ * record is the one of svt_hip_intra_predict_batch_dev; a job reads above[-1 .. W - 1] and left[0 .. H - 1] of it, unconditioned, and writes its W x H block at
+ * (dst_x, dst_y) of d_dst.  A job with mode > 4, tx_size > 18 or a 64-sample side writes nothing.  Jobs must not overlap.  pix_bytes 1 with bd 8, or pix_bytes 2
+ * with bd 8 / 10.  Stream-ordered and asynchronous. */
+typedef struct {
+    uint32_t edge_off;            /* first sample of this job's edge record in d_edges */
+    int32_t  dst_x, dst_y;        /* top-left sample of the block in the destination plane */
+    uint8_t  tx_size;             /* TxSize, both sides <= 32 */
+    uint8_t  mode;                /* FilterIntraMode 0..4 */
+    uint8_t  reserved[2];
+} SvtHipFilterIntraJob;
+int svt_hip_filter_intra_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_edges, const SvtHipFilterIntraJob *d_jobs, int njobs, void *d_dst,
+                                           int dst_stride);
 /* open_loop_intra_search_mb (Encoder/Codec/EbMotionEstimation.c:3043-3155, called from the motion-estimation process when the look-ahead model is on) for every
  * 16x16 macroblock of an 8-bit luma picture, one launch: neighbours from the SOURCE picture (update_neighbor_samples_array_open_loop_mb,
  * Encoder/Codec/EbEncIntraPrediction.c:1201), for mode = DC_PRED .. mode_end the edges conditioned by filter_intra_edge (Common/Codec/EbIntraPrediction.c:2545), the

@@ -147,6 +147,17 @@ class IntraJob(C.Structure):
                 ("up_npx_left", C.c_uint8)]
 
 
+class CflJob(C.Structure):
+    """SvtHipCflJob (include/svt_hip.h)."""
+    _fields_ = [("luma_x", C.c_int32), ("luma_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("edge_off", C.c_uint32 * 2), ("alpha_q3", C.c_int8 * 2),
+                ("tx_size", C.c_uint8), ("plane_mask", C.c_uint8), ("dc_from_edges", C.c_uint8), ("dc_have", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class FilterIntraJob(C.Structure):
+    """SvtHipFilterIntraJob (include/svt_hip.h)."""
+    _fields_ = [("edge_off", C.c_uint32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("tx_size", C.c_uint8), ("mode", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
 class TplRef(C.Structure):
     """SvtHipTplRef (include/svt_hip.h): device pointers to sample (0, 0)."""
     _fields_ = [("d_src", C.c_void_p), ("d_rec", C.c_void_p), ("src_stride", C.c_int32), ("rec_stride", C.c_int32)]
@@ -330,6 +341,8 @@ def lib():
     L.svt_hip_cdef_apply_frame_dev.argtypes = [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]
     L.svt_hip_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
     L.svt_hip_intra_ois_picture_dev.argtypes = [vp, u8p, i32, i32, i32, i32, u8p, vp]
+    L.svt_hip_cfl_predict_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp]
+    L.svt_hip_filter_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
     L.svt_hip_tpl_dispenser_scratch_bytes.argtypes = [i32, i32]
     L.svt_hip_tpl_dispenser_scratch_bytes.restype = C.c_size_t
     L.svt_hip_tpl_set_phases.argtypes = [vp, i32]
@@ -407,6 +420,82 @@ class Context:
             return self.to_host(d_d, dst.shape, dst.dtype)
         finally:
             self.free(d_e, d_j, d_d)
+
+    def _upload_plane(self, plane):
+        """A 2-D plane that may be an offset / strided view (unit stride along a row) of a C-contiguous array: that array is uploaded whole.
+        -> (device pointer of the array, device pointer of the view's sample (0, 0), row stride in samples, the array)."""
+        import numpy as np
+        root = plane
+        while isinstance(root.base, np.ndarray):
+            root = root.base
+        assert plane.ndim == 2 and root.flags.c_contiguous and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
+        d = self.to_device(root)
+        return d, C.c_void_p(d.value + plane.ctypes.data - root.ctypes.data), plane.strides[0] // plane.itemsize, root
+
+    def _download_plane(self, d_root, root, plane):
+        """The view `plane` of `root` as the device now holds it (a view of a fresh copy of the whole array: what lies around the view comes along)."""
+        import numpy as np
+        host = self.to_host(d_root, root.shape, root.dtype)
+        off = plane.ctypes.data - root.ctypes.data
+        return np.ndarray(plane.shape, plane.dtype, host, off, plane.strides)
+
+    def _upload_jobs(self, jobs):
+        d = self.empty(max(C.sizeof(jobs), 4))
+        if len(jobs):
+            self.check(self.L.svt_hip_memcpy_h2d(self.h, d, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
+        return d
+
+    def cfl_predict_batch(self, luma, edges, jobs, cb, cr, want_ac=False):
+        """svt_hip_cfl_predict_batch_dev: `luma` the 2-D luma plane, `edges` a flat array of edge records, `jobs` a ctypes array of CflJob, `cb` / `cr` the 2-D chroma
+        planes (one of them may be None), all uint8 (bd 8) or all uint16 (bd 10); planes may be offset / strided views, the two chroma planes with one row stride.
+        Returns (cb, cr) after the launch -- views like the ones given, None for a plane not given -- and with `want_ac` also the [njobs][32][32] int16 AC
+        buffer; `want_ac` may be that buffer's initial content instead of True."""
+        import numpy as np
+        pix_bytes = luma.dtype.itemsize
+        planes = [p for p in (cb, cr) if p is not None]
+        assert planes and all(p.dtype == luma.dtype for p in planes) and edges.dtype == luma.dtype
+        held = []
+        try:
+            d_l, p_l, s_l, _ = self._upload_plane(luma); held.append(d_l)
+            d_e = self.to_device(edges); held.append(d_e)
+            d_j = self._upload_jobs(jobs); held.append(d_j)
+            up = []
+            for p in (cb, cr):
+                up.append(self._upload_plane(p) if p is not None else (None, None, 0, None))
+                if p is not None: held.append(up[-1][0])
+            strides = {u[2] for u in up if u[0] is not None}
+            assert len(strides) == 1, "the two chroma planes share one stride"
+            d_ac = None
+            if want_ac is not False:
+                ac0 = np.zeros((len(jobs), 32, 32), np.int16) if want_ac is True else np.ascontiguousarray(want_ac, np.int16)
+                assert ac0.shape == (len(jobs), 32, 32)
+                d_ac = self.to_device(ac0); held.append(d_ac)
+            self.check(self.L.svt_hip_cfl_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, p_l, s_l, d_e, d_j, len(jobs), up[0][1], up[1][1],
+                                                             strides.pop(), d_ac), "cfl_predict_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out = tuple(self._download_plane(u[0], u[3], p) if p is not None else None for u, p in zip(up, (cb, cr)))
+            if d_ac is not None:
+                out += (self.to_host(d_ac, ac0.shape, np.int16),)
+            return out
+        finally:
+            self.free(*held)
+
+    def filter_intra_predict_batch(self, edges, jobs, dst):
+        """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D
+        destination plane of the same dtype (may be an offset / strided view); bd 8 for uint8, 10 for uint16.  Returns the plane after the launch."""
+        pix_bytes = edges.dtype.itemsize
+        assert dst.dtype == edges.dtype
+        held = []
+        try:
+            d_e = self.to_device(edges); held.append(d_e)
+            d_j = self._upload_jobs(jobs); held.append(d_j)
+            d_d, p_d, s_d, root = self._upload_plane(dst); held.append(d_d)
+            self.check(self.L.svt_hip_filter_intra_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, d_e, d_j, len(jobs), p_d, s_d),
+                       "filter_intra_predict_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self._download_plane(d_d, root, dst)
+        finally:
+            self.free(*held)
 
     # ---- TPL flow dispenser
     def tpl_dispenser_picture(self, params, d_cur, cur_stride, refs, d_mv, d_ref_mask, d_ois_mode, d_ois_cost, d_recon, recon_stride):

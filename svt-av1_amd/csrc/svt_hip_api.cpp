@@ -240,7 +240,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(intra) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -294,6 +294,34 @@ int svt_hip_intra_ois_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int stride
     }
     hipError_t e = (hipError_t)svt_hip_launch_intra_ois(c->stream, d_src, stride, w, h, mode_end, d_mode, d_cost);
     if (e != hipSuccess) return fail(c, e, "intra ois launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_cfl_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_luma, int luma_stride, const void* d_edges, const SvtHipCflJob* d_jobs, int njobs,
+                                  void* d_cb, void* d_cr, int chroma_stride, int16_t* d_ac) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_luma || !d_edges || !d_jobs || (!d_cb && !d_cr) || njobs < 0 || (pix_bytes != 1 && pix_bytes != 2) || (bd != 8 && bd != 10) ||
+        (pix_bytes == 1 && bd != 8) || luma_stride <= 0 || chroma_stride <= 0) {
+        if (c) c->err = "svt_hip_cfl_predict_batch_dev: bad argument";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (!njobs) return SVT_HIP_OK;
+    hipError_t e = (hipError_t)svt_hip_launch_cfl_predict(c->stream, pix_bytes, bd, d_luma, luma_stride, d_edges, d_jobs, njobs, d_cb, d_cr, chroma_stride, d_ac);
+    if (e != hipSuccess) return fail(c, e, "cfl predict launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_filter_intra_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_edges, const SvtHipFilterIntraJob* d_jobs, int njobs, void* d_dst,
+                                           int dst_stride) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_edges || !d_jobs || !d_dst || njobs < 0 || (pix_bytes != 1 && pix_bytes != 2) || (bd != 8 && bd != 10) || (pix_bytes == 1 && bd != 8) ||
+        dst_stride <= 0) {
+        if (c) c->err = "svt_hip_filter_intra_predict_batch_dev: bad argument";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (!njobs) return SVT_HIP_OK;
+    hipError_t e = (hipError_t)svt_hip_launch_filter_intra_predict(c->stream, pix_bytes, bd, d_edges, d_jobs, njobs, d_dst, dst_stride);
+    if (e != hipSuccess) return fail(c, e, "filter-intra predict launch");
     return SVT_HIP_OK;
 }
 

@@ -144,6 +144,10 @@ int svt_hip_launch_sgr_apply(hipStream_t st, int pix_bytes, int bd, const void* 
 /* intra.hip */
 int svt_hip_launch_intra_ois(hipStream_t st, const uint8_t* src, int stride, int w, int h, int mode_end, uint8_t* mode, int32_t* cost);
 int svt_hip_launch_intra_predict(hipStream_t st, int pix_bytes, int bd, const void* edges, const SvtHipIntraJob* jobs, int njobs, void* dst, int dst_stride);
+/* intra_cfl.hip */
+int svt_hip_launch_cfl_predict(hipStream_t st, int pix_bytes, int bd, const void* luma, int luma_stride, const void* edges, const SvtHipCflJob* jobs, int njobs, void* cb,
+                               void* cr, int chroma_stride, int16_t* ac);
+int svt_hip_launch_filter_intra_predict(hipStream_t st, int pix_bytes, int bd, const void* edges, const SvtHipFilterIntraJob* jobs, int njobs, void* dst, int dst_stride);
 /* tpl.hip */
 int svt_hip_launch_tpl_dispenser(hipStream_t st, const SvtHipTplParams* p, const uint8_t* cur, int cur_stride, const SvtHipTplRef* refs, const uint32_t* mv,
                                  const uint8_t* ref_mask, const uint8_t* ois_mode, const int32_t* ois_cost, uint8_t* recon, int recon_stride,
