@@ -1097,6 +1097,65 @@ int svt_hip_tpl_dispenser_picture_dev(SvtHipCtx *ctx, const SvtHipTplParams *p, 
  * bit 1 = phase B (the intra steps), bit 2 = the padding.  The default, 7, is the only value that computes the dispenser. */
 int svt_hip_tpl_set_phases(SvtHipCtx *ctx, int mask);
 
+/* ------------------------------------------------------------------ global motion: warp error and parameter refinement -----------------------
+ * The source-only arithmetic of compute_global_motion (Encoder/Codec/EbGlobalMotionEstimation.c:171-405) after the model fit: the warp error of
+ * integer models and the coordinate descent over their parameters.  8-bit luma, no subsampling (the reference calls this path with EB_8BIT only, :339-340).
+ * Planes: d_* points at sample (0, 0), any stride >= width, any base offset; width and height >= 8, not necessarily multiples of 8; nothing outside
+ * [0, width) x [0, height) of a plane is read (the warp clamps to the reference plane's edges as the reference does).  The source is w x h; a reference
+ * plane has its own width / height / stride (they bound the clamp; the error is always summed over the source's w x h).
+ * Corner detection, correspondences, RANSAC, gm_get_params_cost / svt_av1_is_enough_erroradvantage and the high-bit-depth twins stay on the host. */
+typedef struct {
+    int32_t mat[6];                     /* EbWarpedMotionParams::wmmat[0..5] as svt_warp_plane uses them */
+    int16_t alpha, beta, gamma, delta;  /* its shear parameters */
+    int32_t valid;                      /* what svt_get_shear_params returned; 0 = the warp error is 1 and nothing is warped */
+} SvtHipGmModel;
+typedef struct {
+    const uint8_t *d_plane;
+    int32_t width, height, stride, reserved;
+} SvtHipGmRef;
+typedef struct {
+    int32_t ref;                        /* index into the table of reference planes */
+    int32_t wmtype;                     /* 0 IDENTITY (initial error only), 1 TRANSLATION, 2 ROTZOOM, 3 AFFINE */
+    int32_t wmmat[8];
+    int32_t n_refinements;              /* 0 .. SVT_HIP_GM_MAX_REFINEMENTS; 0 = initial error only */
+    int32_t reserved;
+    int64_t best_frame_error;           /* INT64_MAX = none */
+} SvtHipGmJob;
+typedef struct {
+    int32_t wmmat[8];                   /* after the final force_wmtype */
+    int32_t wmtype;                     /* get_wmtype of them; -1 = the job was refused (ref / wmtype / n_refinements out of range), nothing else is set */
+    int32_t probes;                     /* warp errors the reference evaluates on this walk (what the replay consumed, not what speculation computed) */
+    int64_t best_error;
+    int32_t rounds;                     /* device rounds (error launch + step launch) the job took */
+    int32_t invalid_probes;             /* of `probes`, how many had invalid shear parameters (error 1) */
+} SvtHipGmResult;
+#define SVT_HIP_GM_MAX_REFS 8
+#define SVT_HIP_GM_MAX_REFINEMENTS 12
+#define SVT_HIP_GM_MAX_DIM 16384
+#define SVT_HIP_GM_MAX_MODELS (1 << 20)
+#define SVT_HIP_GM_MAX_JOBS 1024
+
+/* svt_get_shear_params (Common/Codec/EbWarpedMotion.c:921-950, with is_affine_valid :359, is_affine_shear_allowed :364 and the divisor of :343-357) of n
+ * models: d_wmmat = n x int32[6]; d_out[i] = {the six parameters, alpha .. delta after the 6-bit reduction, valid}.  alpha .. delta are 0 when wmmat[2] <= 0
+ * (the reference leaves them untouched there). */
+int svt_hip_gm_shear_params_batch_dev(SvtHipCtx *ctx, const int32_t *d_wmmat, int n, SvtHipGmModel *d_out);
+/* svt_av1_warp_error(wm, 0, 8, ref, ..., src, 0, 0, w, h, src_stride, 0, 0, INT64_MAX) (Encoder/Codec/EbEncWarpedMotion.c:171-211, :227-264) of n models over
+ * one picture in one launch: d_err[i] = the sum of error_measure_lut over the source against the reference warped in 32x32 blocks; 1 where !valid. */
+int svt_hip_gm_warp_error_batch_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int w, int h, const uint8_t *d_ref, int ref_width, int ref_height,
+                                    int ref_stride, const SvtHipGmModel *d_models, int n, int64_t *d_err);
+/* svt_av1_frame_error(0, 8, ref, stride, src, w, h, src_stride) = svt_av1_calc_frame_error_c (EbEncWarpedMotion.c:160-169, :213-225), the ref_frame_error of
+ * compute_global_motion (EbGlobalMotionEstimation.c:376), of n_refs <= 8 planes against the source; refs is a host array, width / height are not used. */
+int svt_hip_gm_frame_error_batch_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int w, int h, const SvtHipGmRef *refs, int n_refs, int64_t *d_err);
+/* svt_av1_refine_integerized_param (Encoder/Codec/global_motion.c:135-259) of njobs walks in lockstep: rounds of one warp-error launch over every job's
+ * current batch of speculated candidates and one launch that replays the reference's comparisons and writes the next batches; the host polls one counter
+ * per chunk of rounds (it synchronises the stream).  refs is a host array of n_refs <= 8 planes; d_jobs / d_results live in device memory; d_scratch holds
+ * svt_hip_gm_refine_scratch_bytes(njobs) bytes.  *polls_out (may be NULL) = how many times the host read the counter.  docs/kernels/gm.md. */
+size_t svt_hip_gm_refine_scratch_bytes(int njobs);
+int svt_hip_gm_refine_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int w, int h, const SvtHipGmRef *refs, int n_refs,
+                                  const SvtHipGmJob *d_jobs, int njobs, SvtHipGmResult *d_results, void *d_scratch, int *polls_out);
+/* The error table the three kernels use, min(16384, floor(16384 (|i - 255| / 255)^0.7 + 0.5)), i = 0..511 (host; needs no device). */
+int svt_hip_gm_error_table(uint16_t out[512]);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -176,6 +176,29 @@ class TplMbStats(C.Structure):
                 ("pad1", C.c_uint16)]
 
 
+class GmModel(C.Structure):
+    """SvtHipGmModel (include/svt_hip.h)."""
+    _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16), ("valid", C.c_int32)]
+
+
+class GmRef(C.Structure):
+    """SvtHipGmRef (include/svt_hip.h): device pointer to sample (0, 0)."""
+    _fields_ = [("d_plane", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GmJob(C.Structure):
+    """SvtHipGmJob (include/svt_hip.h)."""
+    _fields_ = [("ref", C.c_int32), ("wmtype", C.c_int32), ("wmmat", C.c_int32 * 8), ("n_refinements", C.c_int32), ("reserved", C.c_int32),
+                ("best_frame_error", C.c_int64)]
+
+
+class GmResult(C.Structure):
+    """SvtHipGmResult (include/svt_hip.h)."""
+    _fields_ = [("wmmat", C.c_int32 * 8), ("wmtype", C.c_int32), ("probes", C.c_int32), ("best_error", C.c_int64), ("rounds", C.c_int32),
+                ("invalid_probes", C.c_int32)]
+
+
+GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
 TPL_MAX_REFS = 7   # MAX_PA_ME_MV: slots 0..3 list 0, 4..6 list 1
 
 
@@ -347,6 +370,13 @@ def lib():
     L.svt_hip_tpl_dispenser_scratch_bytes.restype = C.c_size_t
     L.svt_hip_tpl_set_phases.argtypes = [vp, i32]
     L.svt_hip_tpl_dispenser_picture_dev.argtypes = [vp, C.POINTER(TplParams), u8p, i32, C.POINTER(TplRef), vp, u8p, u8p, vp, u8p, i32, vp, vp]
+    L.svt_hip_gm_error_table.argtypes = [vp]
+    L.svt_hip_gm_shear_params_batch_dev.argtypes = [vp, vp, i32, vp]
+    L.svt_hip_gm_warp_error_batch_dev.argtypes = [vp, u8p, i32, i32, i32, u8p, i32, i32, i32, vp, i32, vp]
+    L.svt_hip_gm_frame_error_batch_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, vp]
+    L.svt_hip_gm_refine_scratch_bytes.argtypes = [i32]
+    L.svt_hip_gm_refine_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_gm_refine_picture_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, vp, i32, vp, vp, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -524,6 +554,82 @@ class Context:
         top_left = C.c_void_p(d_recon.value - pad * recon_stride - pad)
         self.check(self.L.svt_hip_memcpy2d_d2h(self.h, out.ctypes.data_as(C.c_void_p), out.shape[1], top_left, recon_stride, out.shape[1], out.shape[0]), "d2h 2d")
         return out
+
+    # ---- global motion
+    def gm_shear_params_batch(self, wmmat):
+        """svt_hip_gm_shear_params_batch_dev: `wmmat` [n][6] int32 -> a ctypes array of n GmModel."""
+        import numpy as np
+        wmmat = np.ascontiguousarray(wmmat, np.int32).reshape(-1, 6)
+        n = len(wmmat)
+        d_in, d_out = self.to_device(wmmat), self.empty(n * C.sizeof(GmModel))
+        try:
+            self.check(self.L.svt_hip_gm_shear_params_batch_dev(self.h, d_in, n, d_out), "gm_shear_params_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out = (GmModel * n)()
+            if n:
+                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_out, C.sizeof(out)), "d2h")
+            return out
+        finally:
+            self.free(d_in, d_out)
+
+    def gm_warp_error_batch(self, src, ref, models):
+        """svt_hip_gm_warp_error_batch_dev: `src` / `ref` 2-D uint8 planes (offset / strided views allowed), `models` a ctypes array of GmModel -> int64 [n]."""
+        import numpy as np
+        held = []
+        try:
+            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+            d_r, p_r, s_r, _ = self._upload_plane(ref); held.append(d_r)
+            d_m = self._upload_jobs(models); held.append(d_m)
+            d_e = self.to_device(np.full(max(len(models), 1), -7, np.int64)); held.append(d_e)
+            self.check(self.L.svt_hip_gm_warp_error_batch_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], p_r, ref.shape[1], ref.shape[0], s_r, d_m, len(models), d_e),
+                       "gm_warp_error_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_e, (len(models),), np.int64)
+        finally:
+            self.free(*held)
+
+    def gm_frame_error_batch(self, src, refs):
+        """svt_hip_gm_frame_error_batch_dev: `src` and each of up to 8 `refs` a 2-D uint8 plane of one size -> int64 [len(refs)]."""
+        import numpy as np
+        held = []
+        try:
+            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+            tab = (GmRef * GM_MAX_REFS)()
+            for i, r in enumerate(refs):
+                d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
+                tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
+            d_e = self.to_device(np.full(max(len(refs), 1), -7, np.int64)); held.append(d_e)
+            self.check(self.L.svt_hip_gm_frame_error_batch_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], tab, len(refs), d_e), "gm_frame_error_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_e, (len(refs),), np.int64)
+        finally:
+            self.free(*held)
+
+    def gm_refine_picture(self, src, refs, jobs, repeat=1):
+        """svt_hip_gm_refine_picture_dev: `src` a 2-D uint8 plane, `refs` up to 8 such planes (own sizes), `jobs` a ctypes array of GmJob.  `repeat` calls are issued
+        back to back on the same scratch and results without a synchronisation of the caller's in between.  -> (ctypes array of GmResult, host polls of the last call)."""
+        held = []
+        try:
+            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+            tab = (GmRef * GM_MAX_REFS)()
+            for i, r in enumerate(refs):
+                d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
+                tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
+            n = len(jobs)
+            d_j = self._upload_jobs(jobs); held.append(d_j)
+            d_o = self.empty(n * C.sizeof(GmResult)); held.append(d_o)
+            d_x = self.empty(self.L.svt_hip_gm_refine_scratch_bytes(n)); held.append(d_x)
+            polls = C.c_int(0)
+            for _ in range(repeat):
+                self.check(self.L.svt_hip_gm_refine_picture_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], tab, len(refs), d_j, n, d_o, d_x, C.byref(polls)),
+                           "gm_refine_picture")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out = (GmResult * n)()
+            if n:
+                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_o, C.sizeof(out)), "d2h")
+            return out, polls.value
+        finally:
+            self.free(*held)
 
     def close(self):
         if self.h:

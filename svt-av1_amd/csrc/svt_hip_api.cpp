@@ -28,6 +28,7 @@ struct SvtHipCtx {
     size_t      host_scratch_bytes = 0;
     void*       me_buf = nullptr;         // device staging of svt_hip_me_fullpel_frame (host-pointer form), grown on demand
     size_t      me_buf_bytes = 0;
+    uint16_t*   gm_lut = nullptr;         // device copy of the global-motion error table, made by the first global-motion call
     std::string err;
 };
 
@@ -102,6 +103,7 @@ void svt_hip_destroy(SvtHipCtx* c) {
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->host_scratch) (void)hipHostFree(c->host_scratch);
     if (c->me_buf) (void)hipFree(c->me_buf);
+    if (c->gm_lut) (void)hipFree(c->gm_lut);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -240,7 +242,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -359,6 +361,102 @@ int svt_hip_tpl_dispenser_picture_dev(SvtHipCtx* c, const SvtHipTplParams* p, co
 int svt_hip_tpl_set_phases(SvtHipCtx* c, int mask) {
     if (!c || mask < 0 || mask > 7) return SVT_HIP_ERR_BAD_ARG;
     c->tpl_phases = mask;
+    return SVT_HIP_OK;
+}
+
+/* ---------------------------------------------------------------------------------- global motion */
+int svt_hip_gm_error_table(uint16_t out[512]) {
+    if (!out) return SVT_HIP_ERR_BAD_ARG;
+    std::memcpy(out, svt_hip_gm_error_lut_host(), 512 * sizeof(uint16_t));
+    return SVT_HIP_OK;
+}
+
+static int gm_lut(SvtHipCtx* c) {
+    if (c->gm_lut) return SVT_HIP_OK;
+    HIPCHK(c, hipMalloc((void**)&c->gm_lut, 512 * sizeof(uint16_t)));
+    hipError_t e = hipMemcpy(c->gm_lut, svt_hip_gm_error_lut_host(), 512 * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(c->gm_lut); c->gm_lut = nullptr; return fail(c, e, "global-motion error table upload"); }
+    return SVT_HIP_OK;
+}
+
+static bool gm_plane_bad(const uint8_t* p, int stride, int w, int h) {
+    return !p || w < 8 || h < 8 || w > SVT_HIP_GM_MAX_DIM || h > SVT_HIP_GM_MAX_DIM || stride < w;
+}
+
+int svt_hip_gm_shear_params_batch_dev(SvtHipCtx* c, const int32_t* d_wmmat, int n, SvtHipGmModel* d_out) {
+    SVT_HIP_ENTER(c);
+    if (!c || n < 0 || n > SVT_HIP_GM_MAX_MODELS || !d_wmmat || !d_out) {
+        if (c) c->err = "svt_hip_gm_shear_params_batch_dev: bad argument";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    hipError_t e = (hipError_t)svt_hip_launch_gm_shear_params(c->stream, d_wmmat, n, d_out);
+    if (e != hipSuccess) return fail(c, e, "global-motion shear parameter launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_gm_warp_error_batch_dev(SvtHipCtx* c, const uint8_t* d_src, int src_stride, int w, int h, const uint8_t* d_ref, int ref_width, int ref_height, int ref_stride,
+                                    const SvtHipGmModel* d_models, int n, int64_t* d_err) {
+    SVT_HIP_ENTER(c);
+    if (!c || gm_plane_bad(d_src, src_stride, w, h) || gm_plane_bad(d_ref, ref_stride, ref_width, ref_height) || n < 0 || n > SVT_HIP_GM_MAX_MODELS || !d_models || !d_err) {
+        if (c) c->err = "svt_hip_gm_warp_error_batch_dev: bad argument (planes 8 .. 16384 wide and high, stride >= width, 0 <= n <= 2^20)";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (!n) return SVT_HIP_OK;
+    if (int rc = gm_lut(c)) return rc;
+    const SvtHipGmRef r = {d_ref, ref_width, ref_height, ref_stride, 0};
+    hipError_t e = (hipError_t)svt_hip_launch_gm_warp_error(c->stream, d_src, src_stride, w, h, &r, d_models, n, c->gm_lut, d_err);
+    if (e != hipSuccess) return fail(c, e, "global-motion warp error launch");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_gm_frame_error_batch_dev(SvtHipCtx* c, const uint8_t* d_src, int src_stride, int w, int h, const SvtHipGmRef* refs, int n_refs, int64_t* d_err) {
+    SVT_HIP_ENTER(c);
+    bool bad = !c || gm_plane_bad(d_src, src_stride, w, h) || n_refs < 0 || n_refs > SVT_HIP_GM_MAX_REFS || !refs || !d_err;
+    for (int i = 0; i < n_refs && !bad; i++) bad = !refs[i].d_plane || refs[i].stride < w;
+    if (bad) {
+        if (c) c->err = "svt_hip_gm_frame_error_batch_dev: bad argument (0 <= n_refs <= 8, every plane's stride >= w)";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (!n_refs) return SVT_HIP_OK;
+    if (int rc = gm_lut(c)) return rc;
+    hipError_t e = (hipError_t)svt_hip_launch_gm_frame_error(c->stream, d_src, src_stride, w, h, refs, n_refs, c->gm_lut, d_err);
+    if (e != hipSuccess) return fail(c, e, "global-motion frame error launch");
+    return SVT_HIP_OK;
+}
+
+size_t svt_hip_gm_refine_scratch_bytes(int njobs) { return svt_hip_gm_refine_scratch_layout_bytes(njobs); }
+
+/* Rounds are enqueued in chunks and the done counter is read once per chunk.  The first chunk is what a walk needs when no directional run outlives the
+ * speculation (the initial error + one round per parameter and refinement of a 5-refinement AFFINE walk); a round after every job has finished costs two
+ * launches whose workgroups exit at once. */
+int svt_hip_gm_refine_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int src_stride, int w, int h, const SvtHipGmRef* refs, int n_refs, const SvtHipGmJob* d_jobs,
+                                  int njobs, SvtHipGmResult* d_results, void* d_scratch, int* polls_out) {
+    SVT_HIP_ENTER(c);
+    bool bad = !c || gm_plane_bad(d_src, src_stride, w, h) || n_refs < 1 || n_refs > SVT_HIP_GM_MAX_REFS || !refs || njobs < 0 || njobs > SVT_HIP_GM_MAX_JOBS ||
+               !d_jobs || !d_results || !d_scratch || ((uintptr_t)d_scratch & 7);
+    for (int i = 0; i < n_refs && !bad; i++) bad = gm_plane_bad(refs[i].d_plane, refs[i].stride, refs[i].width, refs[i].height);
+    if (bad) {
+        if (c) c->err = "svt_hip_gm_refine_picture_dev: bad argument (planes 8 .. 16384 wide and high, stride >= width, 1 <= n_refs <= 8, 0 <= njobs <= 1024)";
+        return SVT_HIP_ERR_BAD_ARG;
+    }
+    if (polls_out) *polls_out = 0;
+    if (!njobs) return SVT_HIP_OK;
+    if (int rc = gm_lut(c)) return rc;
+    const int* d_done = svt_hip_gm_done_counter(d_scratch, njobs);
+    int polls = 0;
+    for (int chunk = 0;; chunk++) {
+        const int rounds = chunk ? 8 : 32;
+        hipError_t e = (hipError_t)svt_hip_launch_gm_refine_rounds(c->stream, d_src, src_stride, w, h, refs, n_refs, d_jobs, njobs, d_results, d_scratch, c->gm_lut,
+                                                                    chunk == 0, rounds);
+        if (e != hipSuccess) return fail(c, e, "global-motion refinement launch");
+        int done = 0;
+        HIPCHK(c, hipMemcpyAsync(&done, d_done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        polls++;
+        if (done >= njobs) break;
+        if (chunk > (1 << 16)) { c->err = "svt_hip_gm_refine_picture_dev: the walk did not end"; return SVT_HIP_ERR_RUNTIME; }
+    }
+    if (polls_out) *polls_out = polls;
     return SVT_HIP_OK;
 }
 

@@ -152,6 +152,17 @@ int svt_hip_launch_filter_intra_predict(hipStream_t st, int pix_bytes, int bd, c
 int svt_hip_launch_tpl_dispenser(hipStream_t st, const SvtHipTplParams* p, const uint8_t* cur, int cur_stride, const SvtHipTplRef* refs, const uint32_t* mv,
                                  const uint8_t* ref_mask, const uint8_t* ois_mode, const int32_t* ois_cost, uint8_t* recon, int recon_stride,
                                  SvtHipTplMbStats* stats, uint8_t* decision, int phases);
+/* gm.hip; d_lut = the device copy of svt_hip_gm_error_lut_host() */
+const uint16_t* svt_hip_gm_error_lut_host(void);
+int svt_hip_launch_gm_shear_params(hipStream_t st, const int32_t* wmmat, int n, SvtHipGmModel* out);
+int svt_hip_launch_gm_warp_error(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const SvtHipGmRef* ref, const SvtHipGmModel* models, int n,
+                                 const uint16_t* d_lut, int64_t* d_err);
+int svt_hip_launch_gm_frame_error(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const SvtHipGmRef* refs, int n_refs, const uint16_t* d_lut,
+                                  int64_t* d_err);
+size_t svt_hip_gm_refine_scratch_layout_bytes(int njobs);
+int svt_hip_launch_gm_refine_rounds(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const SvtHipGmRef* refs, int n_refs, const SvtHipGmJob* jobs,
+                                    int njobs, SvtHipGmResult* results, void* scratch, const uint16_t* d_lut, int start, int n_rounds);
+const int* svt_hip_gm_done_counter(void* scratch, int njobs);
 /* per-call forms (percall.hip, cdef.hip, deblock.hip) */
 int svt_hip_launch_quantize_blocks(hipStream_t st, const int32_t* coeff, int n, int nblk, const SvtHipQuantParams* qp, const int16_t* iscan, int32_t* qcoeff,
                                    int32_t* dqcoeff, uint16_t* eob);

@@ -4,19 +4,20 @@
 // Replaces (file:line under /root/reference/Source/Lib): Common/Codec/EbWarpedMotion.c:577-694 svt_av1_warp_affine_c and :733-842
 // svt_av1_highbd_warp_affine_c (common_dsp_rtcd.h), the non-compound path svt_warp_plane / svt_highbd_warp_plane take for local-warp and
 // global-motion blocks, and their is_compound branches (:660-683, :812-835).  One workgroup per block; each of its 4 waves takes 8x8 sub-blocks in turn: 15 x 8 horizontally filtered
-// samples go through a per-wave LDS tile, then the 64 lanes produce the 8 x 8 outputs.  Both passes pick their 8-tap kernel per sample
+// samples go through a per-wave LDS tile, then the 64 lanes produce the 8 x 8 outputs.  Both passes pick their 8-tap kernel per sample (warp_dev.h: the arithmetic shared with gm.hip)
 // from Warped_Filters (LDS copy: the index diverges across lanes), with the reference's rounding at every step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
 #include "warp_filter_table.h"
+#include "warp_dev.h"
 
 namespace {
 
-__device__ const int16_t kWarpedFilter[193][8] = SVT_WARPED_FILTER_TABLE;
+using svt_warp::rp2;
+using svt_warp::clampi;
 
-__device__ __forceinline__ int rp2(int v, int n) { return (v + ((1 << n) >> 1)) >> n; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+__device__ const int16_t kWarpedFilter[193][8] = SVT_WARPED_FILTER_TABLE;
 
 // COMP: blks is a SvtHipWarpCompBlk list; round_1 = COMPOUND_ROUND1_BITS = 7 (av1 get_conv_params_no_round), DIST_PRECISION_BITS = 4
 template <typename PIX, int BD, bool COMP>
@@ -39,28 +40,17 @@ warp_predict_kernel(const PIX* __restrict__ ref, int width, int height, int stri
     const int nbx = (b.p_width + 7) >> 3, nby = (b.p_height + 7) >> 3;
     for (int sb = wave; sb < nbx * nby; sb += 4) {
         const int j = b.p_col + 8 * (sb % nbx), i = b.p_row + 8 * (sb / nbx);
-        const int src_x = (j + 4) << ss_x, src_y = (i + 4) << ss_y;
-        const int dst_x = b.mat[2] * src_x + b.mat[3] * src_y + b.mat[0], dst_y = b.mat[4] * src_x + b.mat[5] * src_y + b.mat[1];
-        const int x4 = dst_x >> ss_x, y4 = dst_y >> ss_y;
-        const int ix4 = x4 >> 16, iy4 = y4 >> 16;
-        int sx4 = x4 & 0xffff, sy4 = y4 & 0xffff;
-        sx4 += b.alpha * (-4) + b.beta * (-4); sy4 += b.gamma * (-4) + b.delta * (-4);
-        sx4 &= ~63; sy4 &= ~63;
+        const svt_warp::Cell cell = svt_warp::cell_origin(b.mat, b.alpha, b.beta, b.gamma, b.delta, j, i, ss_x, ss_y);
         // horizontal: 15 rows x 8 columns = 120 samples, two rounds of 64 lanes
 #pragma unroll
         for (int r = 0; r < 2; r++) {
             const int idx = lane + 64 * r;
             if (idx < 120) {
                 const int k = (idx >> 3) - 7, l = (idx & 7) - 4;
-                const int iy = clampi(iy4 + k, 0, height - 1);
-                const int sx = sx4 + b.beta * (k + 4) + b.alpha * (l + 4);
-                const int16_t* c = filt[rp2(sx, 10) + 64];
-                const int ix = ix4 + l - 3;
+                const int iy = clampi(cell.iy4 + k, 0, height - 1);
+                const int ix = cell.ix4 + l - 3;
                 const PIX* row = ref + (ptrdiff_t)iy * stride;
-                int sum = 1 << obh;
-#pragma unroll
-                for (int m = 0; m < 8; m++) sum += (int)row[clampi(ix + m, 0, width - 1)] * c[m];
-                tmp[wave][idx] = rp2(sum, rbh);
+                tmp[wave][idx] = svt_warp::horiz(cell, b.alpha, b.beta, k, l, filt, obh, rbh, [&](int m) { return (int)row[clampi(ix + m, 0, width - 1)]; });
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -68,11 +58,7 @@ warp_predict_kernel(const PIX* __restrict__ ref, int width, int height, int stri
         {
             const int k = (lane >> 3) - 4, l = (lane & 7) - 4;
             if (k < b.p_row + b.p_height - i - 4 && l < b.p_col + b.p_width - j - 4) {
-                const int sy = sy4 + b.delta * (k + 4) + b.gamma * (l + 4);
-                const int16_t* c = filt[rp2(sy, 10) + 64];
-                int sum = 1 << obv;
-#pragma unroll
-                for (int m = 0; m < 8; m++) sum += tmp[wave][(k + m + 4) * 8 + (l + 4)] * c[m];
+                int sum = svt_warp::vert(cell, b.gamma, b.delta, k, l, filt, obv, tmp[wave]);
                 if (COMP) {
                     sum = rp2(sum, rbv);
                     uint16_t* p = convbuf + cb.cb_off + (ptrdiff_t)(i - b.p_row + k + 4) * cb.cb_stride + (j - b.p_col + l + 4);
