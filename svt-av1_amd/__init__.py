@@ -434,9 +434,10 @@ class Context:
         finally:
             self.free(d_mode, d_cost)
 
-    def intra_predict_batch(self, edges, jobs, dst):
+    def intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_intra_predict_batch_dev: `edges` a uint8 / uint16 array of edge records, `jobs` a ctypes array of IntraJob, `dst` the 2-D destination plane
-        (same dtype) the blocks are written into; `bd` follows the dtype's use (8 for uint8, 10 for uint16).  Returns the plane after the launch."""
+        (same dtype) the blocks are written into; `bd` defaults to the dtype's usual depth (8 for uint8, 10 for uint16; uint16 planes may also hold 8-bit samples: bd=8).
+        Returns the plane after the launch."""
         import numpy as np
         pix_bytes = edges.dtype.itemsize
         assert dst.dtype == edges.dtype and dst.ndim == 2
@@ -444,7 +445,7 @@ class Context:
         try:
             if len(jobs):
                 self.check(self.L.svt_hip_memcpy_h2d(self.h, d_j, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
-            self.check(self.L.svt_hip_intra_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, d_e, d_j, len(jobs), d_d, dst.shape[1]),
+            self.check(self.L.svt_hip_intra_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), d_e, d_j, len(jobs), d_d, dst.shape[1]),
                        "intra_predict_batch")
             self.check(self.L.svt_hip_sync(self.h), "sync")
             return self.to_host(d_d, dst.shape, dst.dtype)
@@ -475,9 +476,9 @@ class Context:
             self.check(self.L.svt_hip_memcpy_h2d(self.h, d, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
         return d
 
-    def cfl_predict_batch(self, luma, edges, jobs, cb, cr, want_ac=False):
+    def cfl_predict_batch(self, luma, edges, jobs, cb, cr, want_ac=False, bd=None):
         """svt_hip_cfl_predict_batch_dev: `luma` the 2-D luma plane, `edges` a flat array of edge records, `jobs` a ctypes array of CflJob, `cb` / `cr` the 2-D chroma
-        planes (one of them may be None), all uint8 (bd 8) or all uint16 (bd 10); planes may be offset / strided views, the two chroma planes with one row stride.
+        planes (one of them may be None), all uint8 (bd 8) or all uint16 (bd 10 unless `bd` says 8); planes may be offset / strided views, the two chroma planes with one row stride.
         Returns (cb, cr) after the launch -- views like the ones given, None for a plane not given -- and with `want_ac` also the [njobs][32][32] int16 AC
         buffer; `want_ac` may be that buffer's initial content instead of True."""
         import numpy as np
@@ -500,7 +501,7 @@ class Context:
                 ac0 = np.zeros((len(jobs), 32, 32), np.int16) if want_ac is True else np.ascontiguousarray(want_ac, np.int16)
                 assert ac0.shape == (len(jobs), 32, 32)
                 d_ac = self.to_device(ac0); held.append(d_ac)
-            self.check(self.L.svt_hip_cfl_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, p_l, s_l, d_e, d_j, len(jobs), up[0][1], up[1][1],
+            self.check(self.L.svt_hip_cfl_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), p_l, s_l, d_e, d_j, len(jobs), up[0][1], up[1][1],
                                                              strides.pop(), d_ac), "cfl_predict_batch")
             self.check(self.L.svt_hip_sync(self.h), "sync")
             out = tuple(self._download_plane(u[0], u[3], p) if p is not None else None for u, p in zip(up, (cb, cr)))
@@ -510,9 +511,9 @@ class Context:
         finally:
             self.free(*held)
 
-    def filter_intra_predict_batch(self, edges, jobs, dst):
+    def filter_intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D
-        destination plane of the same dtype (may be an offset / strided view); bd 8 for uint8, 10 for uint16.  Returns the plane after the launch."""
+        destination plane of the same dtype (may be an offset / strided view); bd 8 for uint8, 10 for uint16 unless `bd` says 8.  Returns the plane after the launch."""
         pix_bytes = edges.dtype.itemsize
         assert dst.dtype == edges.dtype
         held = []
@@ -520,7 +521,7 @@ class Context:
             d_e = self.to_device(edges); held.append(d_e)
             d_j = self._upload_jobs(jobs); held.append(d_j)
             d_d, p_d, s_d, root = self._upload_plane(dst); held.append(d_d)
-            self.check(self.L.svt_hip_filter_intra_predict_batch_dev(self.h, pix_bytes, 8 if pix_bytes == 1 else 10, d_e, d_j, len(jobs), p_d, s_d),
+            self.check(self.L.svt_hip_filter_intra_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), d_e, d_j, len(jobs), p_d, s_d),
                        "filter_intra_predict_batch")
             self.check(self.L.svt_hip_sync(self.h), "sync")
             return self._download_plane(d_d, root, dst)

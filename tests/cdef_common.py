@@ -15,7 +15,8 @@ class CdefList(C.Structure):
     _fields_ = [("by", C.c_uint8), ("bx", C.c_uint8), ("skip", C.c_uint8)]
 
 
-def make_frame(w, h, bd, seed, smooth=True):
+def make_frame(w, h, bd, seed, smooth=True, dtype=None):
+    """dtype: the sample type of the planes (default: uint8 at bd 8, uint16 above); np.uint16 at bd 8 = 8-bit samples in 16-bit planes"""
     rng = np.random.default_rng(seed)
     planes_src, planes_rec = [], []
     for pli in range(3):
@@ -26,7 +27,7 @@ def make_frame(w, h, bd, seed, smooth=True):
         s = (base + edge + (0 if smooth else rng.normal(0, 20, (ph, pw)))) * (1 << (bd - 8))
         src = np.clip(s, 0, (1 << bd) - 1)
         rec = np.clip(src + rng.normal(0, 6 * (1 << (bd - 8)), (ph, pw)), 0, (1 << bd) - 1)
-        dt = np.uint8 if bd == 8 else np.uint16
+        dt = dtype or (np.uint8 if bd == 8 else np.uint16)
         planes_src.append(np.ascontiguousarray(src.astype(dt))); planes_rec.append(np.ascontiguousarray(rec.astype(dt)))
     skip8 = (rng.random((h // 8, w // 8)) < 0.3).astype(np.uint8)
     return planes_src, planes_rec, skip8
@@ -140,14 +141,14 @@ def _chart_plane(pw, ph, bd, rng, shift):
     return p
 
 
-def make_chart_frame(w, h, bd, seed):
-    """(src, rec, skip8) like make_frame (4:2:0), rec a direction chart (see chart_cell).
+def make_chart_frame(w, h, bd, seed, dtype=None):
+    """(src, rec, skip8) like make_frame (4:2:0, dtype as there), rec a direction chart (see chart_cell).
     src = rec + noise of +-9 << (bd - 8), except: its first third by first third is max - rec (anti-correlated: the largest squared errors and
     a negative covariance in the luma metric), and rows [h/3, 2h/3) x columns [2w/3, w) equal rec (zero distortion).
     skip8 is random at 25 %, except: filter block (0, 1) is skipped entirely (pictures of >= 3 filter-block columns; in a narrower picture
     every filter block holds a corner), the bottom-left filter block keeps exactly one live block (the corner), the four corner blocks are live."""
     cs, mx = bd - 8, (1 << bd) - 1
-    dt = np.uint8 if bd == 8 else np.uint16
+    dt = dtype or (np.uint8 if bd == 8 else np.uint16)
     planes_src, planes_rec = [], []
     for pli in range(3):
         rng = np.random.default_rng([seed, pli])
@@ -250,7 +251,7 @@ def ref_search_fb(ref, rec, src, bd, skip8, fbr, fbc, pri_damping, ngi=64):
         sp = C.c_void_p(s.ctypes.data + s.itemsize * (((64 * fbr) >> dec) * s.shape[1] + ((64 * fbc) >> dec)))
         for gi in range(ngi):
             pri, sec = gi // 4, gi % 4
-            if bd == 8:
+            if rec[pli].dtype == np.uint8:      # 16-bit planes take the 16-bit output and distortion functions at any depth (coeff_shift = bd - 8)
                 tmp = np.zeros(1 << 14, np.uint8)
                 ref.svt_cdef_filter_fb(ptr(tmp), None, BSTRIDE, in_ptr, dec, dec, dirs, C.byref(dirinit), var, pli, dl, count,
                                        pri, sec + (sec == 3), pri_damping, pri_damping, cs)
@@ -284,7 +285,8 @@ def ref_apply_fb(ref, rec, out, bd, skip8, fbr, fbc, y_strength, uv_strength, da
         inbuf, in_ptr = _stage_fb(rec[pli], dec, fbr, fbc, nvfb, nhfb, nb_y, nb_x)
         o = out[pli]
         dst = C.c_void_p(o.ctypes.data + o.itemsize * (((64 * fbr) >> dec) * o.shape[1] + ((64 * fbc) >> dec)))
-        ref.svt_cdef_filter_fb(dst if bd == 8 else None, None if bd == 8 else dst, o.shape[1], in_ptr, dec, dec, dirs, None, var, pli, dl, count,
+        lbd = o.dtype == np.uint8
+        ref.svt_cdef_filter_fb(dst if lbd else None, None if lbd else dst, o.shape[1], in_ptr, dec, dec, dirs, None, var, pli, dl, count,
                                lv[pli != 0], sc[pli != 0], damping, damping, cs)
 
 

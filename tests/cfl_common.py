@@ -168,14 +168,14 @@ def cfl_expected(jobs, refs, cb0, cr0, pos, order, give=(True, True)):
     return planes[0], planes[1], ac
 
 
-def cfl_check(hip, pkg, jobs, refs, dtype, order=None, view=False, give=(True, True), want_ac=True, what=""):
+def cfl_check(hip, pkg, jobs, refs, dtype, order=None, view=False, give=(True, True), want_ac=True, what="", bd=None):
     """One launch of jobs[order] on the device against the per-job reference results: both planes whole (guard bands, unselected planes, what surrounds a view) and
-    the whole AC buffer (pre-filled: nothing outside a job's W x H corner may change)."""
+    the whole AC buffer (pre-filled: nothing outside a job's W x H corner may change).  bd: default 8 for uint8, 10 for uint16."""
     order = list(range(len(jobs))) if order is None else list(order)
     luma, cb, cr, pos = cfl_layout(jobs, dtype, view)
     arr = cfl_job_array(pkg, jobs, pos, order)
     ac0 = np.full((len(order), AC_LINE, AC_LINE), AC_MARK, np.int16)
-    got = hip.cfl_predict_batch(luma, cfl_edges(jobs, dtype), arr, cb if give[0] else None, cr if give[1] else None, want_ac=ac0 if want_ac else False)
+    got = hip.cfl_predict_batch(luma, cfl_edges(jobs, dtype), arr, cb if give[0] else None, cr if give[1] else None, want_ac=ac0 if want_ac else False, bd=bd)
     ecb, ecr, eac = cfl_expected(jobs, refs, cb, cr, pos, order, give)
     for pl, (g, e) in enumerate(zip(got[:2], (ecb, ecr))):
         if not give[pl]: assert g is None; continue
@@ -310,8 +310,9 @@ def fi_layout(jobs, dtype, view=False, cols=16, cell=40, guard=4):
     return dst, [((i % cols) * cell + guard, (i // cols) * cell + guard) for i in range(n)]
 
 
-def fi_check(hip, pkg, jobs, recs, refs, order=None, view=False, what=""):
-    """One launch of jobs[order] (job i reads record i and owns cell i) against the per-job reference blocks (None = a job that must write nothing): the whole plane."""
+def fi_check(hip, pkg, jobs, recs, refs, order=None, view=False, what="", bd=None):
+    """One launch of jobs[order] (job i reads record i and owns cell i) against the per-job reference blocks (None = a job that must write nothing): the whole plane.
+    bd: default 8 for uint8 records, 10 for uint16."""
     dtype = recs.dtype
     order = list(range(len(jobs))) if order is None else list(order)
     dst, pos = fi_layout(jobs, dtype, view)
@@ -320,7 +321,7 @@ def fi_check(hip, pkg, jobs, recs, refs, order=None, view=False, what=""):
         J = arr[k]
         J.edge_off, J.dst_x, J.dst_y, J.tx_size, J.mode = i * 2 * EDGE_REC, pos[i][0], pos[i][1], jobs[i][0], jobs[i][1]
     flat = np.ascontiguousarray(recs.reshape(-1)) if len(recs) else np.zeros(4, dtype)
-    got = hip.filter_intra_predict_batch(flat, arr, dst)
+    got = hip.filter_intra_predict_batch(flat, arr, dst, bd=bd)
     r = root_of(dst).copy()
     exp = np.ndarray(dst.shape, dst.dtype, r, dst.ctypes.data - root_of(dst).ctypes.data, dst.strides)
     for i in order:

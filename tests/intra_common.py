@@ -208,7 +208,7 @@ def run_batch(hip, pkg, recs, jobs, bd):
     if n == 0:
         arr = (pkg.IntraJob * 0)()
     flat = np.ascontiguousarray(recs.reshape(-1)) if n else np.zeros(4, dt)
-    out = hip.intra_predict_batch(flat, arr, dst)
+    out = hip.intra_predict_batch(flat, arr, dst, bd=bd)
     blocks = []
     for i, j in enumerate(jobs):
         if j["tx_size"] > 18:

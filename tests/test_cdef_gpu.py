@@ -9,6 +9,7 @@ import pytest
 
 from conftest import ptr
 import cdef_common as cc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 P3, I3 = C.c_void_p * 3, C.c_int * 3
@@ -128,10 +129,21 @@ def expected_dirs(orc, luma, bd, skip8):
     return e_dir.reshape(nv * nh, 64), e_var.reshape(nv * nh, 64)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-@pytest.mark.parametrize("size", cc.CHART_SIZES)
-def test_search_table_chart(hip, orc, bd, size):
-    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED)
+# 8-bit samples in 16-bit planes run the chart of the smallest ragged size: it holds flat 0 / flat max cells, 0 / max stripes and checkerboards
+CHART_CASES = [pytest.param(bd, None, size, id=f"size{i}-{bd}") for i, size in enumerate(cc.CHART_SIZES) for bd in (8, 10)] + [pytest.param(8, np.uint16, (200, 136), id="size1-u16-8")]
+
+
+@pytest.mark.parametrize("bd,fmt,size", CHART_CASES)
+def test_search_table_chart(hip, orc, bd, fmt, size):
+    """the tables are numbers, not samples: at (u16, 8) those of the (u8, 8) run on the same chart, unchanged"""
+    fc.two_witnesses(_search_table_chart, fmt, bd, hip, orc, size)
+
+
+def _search_table_chart(hip, orc, size, bd, dt, wide):
+    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED, dt)
+    assert rec[0].dtype == dt and (bd > 8 or all(p.max() == 255 and p.min() == 0 for p in rec))
+    if wide: fc.note_inputs(*rec)
+    gots, exps = [], []
     e_dir, e_var = expected_dirs(orc, rec[0], bd, skip8)
     dead = cc.all_skip_fbs(skip8)
     assert dead or size[0] < 192
@@ -144,7 +156,9 @@ def test_search_table_chart(hip, orc, bd, size):
             assert not got[:, fb].any()                     # rows of all-skip filter blocks stay untouched
         assert np.array_equal(g_dir, e_dir), ("dir", bd, damping, np.argwhere(g_dir != e_dir)[:5])
         assert np.array_equal(g_var, e_var), ("var", bd, damping, np.argwhere(g_var != e_var)[:5])
+        gots += [got, g_dir, g_var]; exps += [exp, e_dir, e_var]
     assert got[0].any() and got[1].any() and e_dir.any() and e_var.any()
+    return gots, exps
 
 
 def test_search_table_chart_vs_reference(hip, ref):
@@ -161,10 +175,14 @@ def test_search_table_chart_vs_reference(hip, ref):
             assert np.array_equal(r[0], got[0, fb]) and np.array_equal(r[1], got[1, fb]), (bd, damping, fb)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-@pytest.mark.parametrize("size", cc.CHART_SIZES)
-def test_apply_frame_chart(hip, orc, bd, size):
-    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED)
+@pytest.mark.parametrize("bd,fmt,size", CHART_CASES)
+def test_apply_frame_chart(hip, orc, bd, fmt, size):
+    fc.two_witnesses(_apply_frame_chart, fmt, bd, hip, orc, size)
+
+
+def _apply_frame_chart(hip, orc, size, bd, dt, wide):
+    src, rec, skip8 = cc.make_chart_frame(size[0], size[1], bd, cc.CHART_SEED, dt)
+    gots, exps = [], []
     h, w = rec[0].shape
     nfb = ((h + 63) // 64) * ((w + 63) // 64)
     strides = I3(*[p.shape[1] for p in rec])
@@ -192,5 +210,7 @@ def test_apply_frame_chart(hip, orc, bd, size):
             for form, d_o in (("recomputed", d_out), ("reuse", d_out2)):
                 got = hip.to_host(d_o[pli], rec[pli].shape, rec[pli].dtype)
                 assert np.array_equal(got, exp[pli]), (form, bd, damping, pli, np.argwhere(got != exp[pli])[:5])
+                gots.append(got); exps.append(exp[pli])
         hip.free(*d_out, *d_out2, d_ys, d_uvs, d_dir, d_dir2, d_var, d_mse)
     hip.free(*d_in, *d_src, d_skip)
+    return gots, exps

@@ -13,23 +13,42 @@ import test_cfl_abi as abi
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-BDS = cc.BDS
+BDS = cc.BDS + [(np.uint16, 8)]     # (uint16, 8): 8-bit samples in 16-bit planes, against the reference's high-bit-depth functions with bd 8
 _basic = {}
 
 
 def basic(ref, dtype, bd):
-    """The 420 generator jobs of a bit depth and their reference results: computed once, shared, never modified (variants are shallow copies)."""
-    if bd not in _basic:
+    """The 420 generator jobs of a format and their reference results: computed once, shared, never modified (variants are shallow copies).
+    8-bit samples in 16-bit planes are the (uint8, 8) jobs widened (the generator draws the same values), and the reference's 8-bit and high-bit-depth functions
+    must agree on them -- AC values and both predicted planes, which stay inside 0 .. 255 and reach both ends."""
+    if (dtype, bd) not in _basic:
         jobs = cc.cfl_basic_jobs(dtype, bd)
-        _basic[bd] = (jobs, cc.ref_cfl_jobs(ref, jobs, bd))
-    return _basic[bd]
+        refs = cc.ref_cfl_jobs(ref, jobs, bd)
+        if dtype == np.uint16 and bd == 8:
+            jobs8, refs8 = basic(ref, np.uint8, 8)
+            outs = []
+            for j, j8, r, r8 in zip(jobs, jobs8, refs, refs8):
+                assert np.array_equal(j["luma"], j8["luma"]) and np.array_equal(j["pred"], j8["pred"]) and np.array_equal(j["recs"], j8["recs"])
+                assert np.array_equal(r[0], r8[0]) and all(a.dtype == np.uint16 and b.dtype == np.uint8 and np.array_equal(a, b) for a, b in zip(r[1], r8[1])), j["tx_size"]
+                outs += r[1]
+            assert max(int(o.max()) for o in outs) == 255 and min(int(o.min()) for o in outs) == 0
+        _basic[dtype, bd] = (jobs, refs)
+    return _basic[dtype, bd]
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
 def test_all_shapes_inplace_and_dc(hip, pkg, ref, dtype, bd):
     """14 shapes x (random alphas, extreme content at alpha +-16, an all-maximum block) x (in-place, dc_from_edges with dc_have 0..3) in one launch; planes and d_ac."""
     jobs, refs = basic(ref, dtype, bd)
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="basic")
+    got = cc.cfl_check(hip, pkg, jobs, refs, dtype, what="basic", bd=bd)
+    if dtype == np.uint16 and bd == 8:        # the second witness: the device on the same jobs as uint8 planes (job i sits at the same place; the guard bands hold another marker)
+        jobs8, refs8 = basic(ref, np.uint8, 8)
+        got8 = cc.cfl_check(hip, pkg, jobs8, refs8, np.uint8, what="basic, uint8", bd=8)
+        _, _, _, pos = cc.cfl_layout(jobs, dtype)
+        for j, (x, y) in zip(jobs, pos):
+            w, h = cc.cfl_dims(j)
+            assert all(np.array_equal(got[pl][y:y + h, x:x + w], got8[pl][y:y + h, x:x + w]) for pl in (0, 1)), j["tx_size"]
+        assert np.array_equal(got[2], got8[2])
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
@@ -39,16 +58,16 @@ def test_plane_masks(hip, pkg, ref, dtype, bd):
     jobs = [dict(j, plane_mask=1 + i % 3) for i, j in enumerate(jobs[::3])]
     refs = refs[::3]
     assert {(j["plane_mask"], j["dc_from_edges"]) for j in jobs} == {(m, d) for m in (1, 2, 3) for d in (0, 1)}
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="masks")
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, give=(True, False), what="cb only")
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, give=(False, True), want_ac=False, what="cr only")
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="masks", bd=bd)
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, give=(True, False), what="cb only", bd=bd)
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, give=(False, True), want_ac=False, what="cr only", bd=bd)
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
 def test_offset_odd_stride_views(hip, pkg, ref, dtype, bd):
     """Luma and chroma planes as offset views with an odd row stride: no wide access is aligned; the guard bands and what surrounds the views survive."""
     jobs, refs = basic(ref, dtype, bd)
-    cc.cfl_check(hip, pkg, jobs[::2], refs[::2], dtype, view=True, what="views")
+    cc.cfl_check(hip, pkg, jobs[::2], refs[::2], dtype, view=True, what="views", bd=bd)
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
@@ -57,10 +76,10 @@ def test_order_and_counts(hip, pkg, ref, dtype, bd):
     jobs, refs = basic(ref, dtype, bd)
     rng = np.random.default_rng(61 + bd)
     perm = rng.permutation(len(jobs))
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, order=perm, what="shuffled")
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, order=perm, what="shuffled", bd=bd)
     for n in (0, 1, 37, 75):
-        cc.cfl_check(hip, pkg, jobs[:96], refs[:96], dtype, order=perm[perm < 96][:n], what=f"njobs {n}")
-    cc.cfl_check(hip, pkg, [], [], dtype, what="no jobs at all")
+        cc.cfl_check(hip, pkg, jobs[:96], refs[:96], dtype, order=perm[perm < 96][:n], what=f"njobs {n}", bd=bd)
+    cc.cfl_check(hip, pkg, [], [], dtype, what="no jobs at all", bd=bd)
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
@@ -75,7 +94,7 @@ def test_unusable_jobs_write_nothing(hip, pkg, ref, dtype, bd):
         j = cc.cfl_job(rng, dtype, bd, chg.get("tx_size", jobs[i]["tx_size"]), chg.get("alpha", jobs[i]["alpha"]), "random", 3, i & 1, 3)
         assert not cc.cfl_valid(j)
         jobs[i], refs[i] = j, None
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="unusable jobs")
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="unusable jobs", bd=bd)
 
 
 @pytest.mark.parametrize("dtype,bd", BDS)
@@ -121,19 +140,19 @@ def test_whole_picture(hip, pkg, ref, dtype, bd, tw):
     assert len(tiles) == (176 // tw) * (144 // tw)
     ecb, ecr = cc.ref_cfl_picture(ref, luma, cb, cr, tiles, bd)
     assert (ecb != cb).mean() > 0.5 and (ecr != cr).mean() > 0.5
-    gcb, gcr = hip.cfl_predict_batch(luma, np.zeros(4, dtype), cc.cfl_picture_array(pkg, tiles), cb, cr)
+    gcb, gcr = hip.cfl_predict_batch(luma, np.zeros(4, dtype), cc.cfl_picture_array(pkg, tiles), cb, cr, bd=bd)
     assert np.array_equal(gcb, ecb) and np.array_equal(gcr, ecr)
 
 
-@pytest.mark.parametrize("dtype,bd", BDS)
+@pytest.mark.parametrize("dtype,bd", cc.BDS)
 def test_golden(hip, pkg, dtype, bd):
     """The stored case (tests/golden/make_cfl_golden.py): holds where the reference library is absent."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     import make_cfl_golden as mk
     jobs, refs = mk.load_cfl(np.load(os.path.join(ROOT, "tests", "golden", "cfl_filter_intra.npz")), dtype, bd)
     assert len(jobs) >= 5
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="golden")
-    cc.cfl_check(hip, pkg, jobs, refs, dtype, view=True, order=range(len(jobs) - 1, -1, -1), what="golden, views")
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, what="golden", bd=bd)
+    cc.cfl_check(hip, pkg, jobs, refs, dtype, view=True, order=range(len(jobs) - 1, -1, -1), what="golden, views", bd=bd)
 
 
 def test_bad_arguments_with_a_context(hip, pkg):

@@ -8,17 +8,32 @@ import pytest
 
 from conftest import ptr
 import comp_common as cmc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("bd", [8, 10, 12])
-def test_compound_blocks(hip, orc, bd):
+def plant(plane, bd, x0, y0):
+    """all max, all 0, a 0 / max checkerboard and random 0 / max samples, 192 x 192 each, from (x0, y0) on: the interpolators overshoot the range there"""
+    mx = (1 << bd) - 1
+    yy, xx = np.mgrid[0:192, 0:192]
+    plane[y0:y0 + 192, x0:x0 + 192] = mx; plane[y0:y0 + 192, x0 + 192:x0 + 384] = 0
+    plane[y0 + 192:y0 + 384, x0:x0 + 192] = ((yy + xx) & 1) * mx
+    plane[y0 + 192:y0 + 384, x0 + 192:x0 + 384] = np.random.default_rng(x0 + y0).integers(0, 2, (192, 192)) * mx
+
+
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts(8, 10, 12))
+def test_compound_blocks(hip, orc, bd, fmt):
+    fc.two_witnesses(_compound_blocks, fmt, bd, hip, orc)
+
+
+def _compound_blocks(hip, orc, bd, dt, wide):
     rng = np.random.default_rng(500 + bd)
-    dt = np.uint8 if bd == 8 else np.uint16
     W, H = 1536, 1152
     ref0 = rng.integers(0, 1 << bd, (H, W)).astype(dt); ref1 = rng.integers(0, 1 << bd, (H, W)).astype(dt)
     ref0[:200, :200] = (1 << bd) - 1; ref1[:200, :200] = 0
+    if wide:
+        plant(ref0, bd, 256, 0); plant(ref1, bd, 320, 64)      # the two references' regions overlap out of step
     n = 80
     blks, masks = cmc.make_blocks(rng, W - 256, H - 128, n, 1 << 21)
     for b in blks:
@@ -35,6 +50,7 @@ def test_compound_blocks(hip, orc, bd):
         assert np.array_equal(g, e), (bd, i, b.type, b.w, b.h, (b.subpel0_x, b.subpel0_y, b.subpel1_x, b.subpel1_y), np.argwhere(g != e)[:4])
     assert np.array_equal(got, exp) and np.array_equal(m_got, m_exp)
     assert (m_exp != masks).any() and exp.any()
+    return got, exp
 
 
 def test_compound_empty_and_bad_args(hip):
@@ -72,15 +88,20 @@ def test_obmc_costs(hip, orc):
     assert exp.any() and hip.L.svt_hip_obmc_cost_batch_dev(hip.h, None, 0, None, None, None, 0, None) == 0
 
 
-@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts(8, 10, 12))
 @pytest.mark.parametrize("ss", [0, 1])
-def test_warp_blocks(hip, orc, bd, ss):
+def test_warp_blocks(hip, orc, bd, fmt, ss):
     """svt_hip_warp_predict_batch_dev vs the oracle (pinned to svt_av1_[highbd_]warp_affine_c): block sizes 8..128, random and extreme shear,
     models that move the block outside the plane (edge clamping), luma and 4:2:0 chroma sub-sampling."""
+    fc.two_witnesses(_warp_blocks, fmt, bd, hip, orc, ss)
+
+
+def _warp_blocks(hip, orc, ss, bd, dt, wide):
     rng = np.random.default_rng(700 + bd + ss)
-    dt = np.uint8 if bd == 8 else np.uint16
     W, H = 1152, 640
     plane = rng.integers(0, 1 << bd, (H, W)).astype(dt)
+    if wide:
+        plant(plane, bd, 0, 0); plant(plane, bd, 640, 192)
     n = 40
     blks = cmc.warp_blocks(rng, W, H, n)
     exp = np.zeros((H, W), dt)
@@ -93,6 +114,7 @@ def test_warp_blocks(hip, orc, bd, ss):
         g, e = got[b.p_row:b.p_row + b.p_height, b.p_col:b.p_col + b.p_width], exp[b.p_row:b.p_row + b.p_height, b.p_col:b.p_col + b.p_width]
         assert np.array_equal(g, e), (bd, ss, i, b.p_width, b.p_height, np.argwhere(g != e)[:4])
     assert np.array_equal(got, exp) and exp.any()
+    return got, exp
 
 
 @pytest.mark.parametrize("bd", [8, 10])

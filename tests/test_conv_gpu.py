@@ -9,17 +9,25 @@ import pytest
 
 from conftest import ptr
 import dlf_common as dc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_subpel_predict(hip, pkg, orc, bd):
+def _subpel_case(hip, pkg, orc, bd, dt, wide=False):
+    """One batch of 160 blocks of every size, bank and phase -> (device result, oracle result).  wide: the case the (u16, 8) format and its (u8, 8) companion
+    share -- convolve jobs only (upsampled_pred is an 8-bit-sample function), and next to the all-max region an all-0 one, a 0 / max checkerboard and random
+    0 / max samples: the 8-tap filters overshoot the range there and the clip at (1 << bd) - 1 decides."""
     rng = np.random.default_rng(40 + bd)
-    dt = np.uint8 if bd == 8 else np.uint16
     PADV = 24
     refp = rng.integers(0, 1 << bd, (300 + 2 * PADV, 420 + 2 * PADV)).astype(dt)
     refp[PADV:PADV + 64, PADV:PADV + 64] = (1 << bd) - 1
+    if wide:
+        mx = (1 << bd) - 1
+        yy, xx = np.mgrid[0:96, 0:96]
+        refp[PADV + 64:PADV + 160, PADV:PADV + 96] = 0
+        refp[PADV:PADV + 96, PADV + 64:PADV + 160] = ((yy + xx) & 1) * mx
+        refp[PADV + 96:PADV + 192, PADV + 96:PADV + 192] = np.random.default_rng(41).integers(0, 2, (96, 96)) * mx
     n = 160
     blks = (pkg.ConvBlk * n)()
     dst_w, dst_h = 2048, 2048
@@ -29,7 +37,7 @@ def test_subpel_predict(hip, pkg, orc, bd):
         w = int(rng.choice([4, 8, 16, 32, 64, 128])); h = int(rng.choice([4, 8, 16, 32, 64, 128]))
         if cx + w > dst_w: cx = 0; cy += rowh; rowh = 0
         rowh = max(rowh, h)
-        mode = 1 if (bd == 8 and i % 3 == 0) else 0
+        mode = 1 if (bd == 8 and i % 3 == 0 and not wide) else 0
         sx, sy = int(rng.integers(0, 16)), int(rng.integers(0, 16))
         if mode: sx &= ~1; sy &= ~1
         if i % 5 == 0: sx = 0
@@ -37,6 +45,7 @@ def test_subpel_predict(hip, pkg, orc, bd):
         bx = int(rng.integers(0, 6)); by_ = int(rng.integers(0, 6))
         if mode: bx = by_ = int(rng.choice([3, 4, 0]))
         srx, sry = int(rng.integers(0, 420 - w)), int(rng.integers(0, 300 - h))
+        if wide and i % 2: srx, sry = srx % 150, sry % 150          # every other block on or next to the planted regions
         blks[i] = pkg.ConvBlk(srx, sry, cx, cy, w, h, bx, by_, sx, sy, mode, 0)
         sp = C.c_void_p(refp.ctypes.data + ((sry + PADV) * refp.shape[1] + srx + PADV) * refp.itemsize)
         if mode:
@@ -53,6 +62,23 @@ def test_subpel_predict(hip, pkg, orc, bd):
     got = hip.to_host(d_dst, exp.shape, dt)
     hip.free(d_ref, d_dst, d_b)
     assert np.array_equal(got, exp), np.argwhere(got != exp)[:5]
+    return got, exp
+
+
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_subpel_predict(hip, pkg, orc, bd, fmt):
+    """8-bit samples in 16-bit planes: the oracle at (2, 8) inside the case, and the (1, 8) result widened"""
+    fc.two_witnesses(_subpel_case, fmt, bd, hip, pkg, orc)
+
+
+def test_block_variance_rejects_8bit_samples_in_16bit_planes(hip):
+    """svt_hip_block_variance_batch_dev takes 16-bit planes at bd 10 or 16 only (the two variance functions the reference has for them): (2, 8) stays an error"""
+    d = hip.empty(64)
+    try:
+        assert hip.L.svt_hip_block_variance_batch_dev(hip.h, 2, 10, d, 8, d, 8, d, 0, d, d) == 0
+        assert hip.L.svt_hip_block_variance_batch_dev(hip.h, 2, 8, d, 8, d, 8, d, 0, d, d) == 2      # SVT_HIP_ERR_BAD_ARG
+    finally:
+        hip.free(d)
 
 
 @pytest.mark.parametrize("bd", [8, 10])

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import ptr
 import dlf_common as dc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +24,29 @@ def content(rng, h, w, bd, smooth):
     return np.clip(v, 0, (1 << bd) - 1)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+def plant(img, bd):
+    """The regions a (u16, 8) case and its (u8, 8) companion carry on top of content(): all max, all 0, a 0 / max checkerboard, and noise within 3 of either end of
+    the range (flat enough for every filter to fire, so close to the end that its clamp at (1 << bd) - 1 / 0 decides).  In place; -> img."""
+    mx = (1 << bd) - 1
+    h, w = img.shape
+    q = min(h, w) // 4
+    rng = np.random.default_rng(h * 1000 + w)
+    yy, xx = np.mgrid[0:q, 0:q]
+    img[0:q, 0:q] = mx; img[0:q, q:2 * q] = 0; img[q:2 * q, 0:q] = ((yy + xx) & 1) * mx
+    img[q:2 * q, q:2 * q] = mx - rng.integers(0, 4, (q, q)); img[2 * q:3 * q, 0:q] = rng.integers(0, 4, (q, q))
+    return img
+
+
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
 @pytest.mark.parametrize("smooth", [0, 1])
-def test_deblock_planes(hip, orc, bd, smooth):
+def test_deblock_planes(hip, orc, bd, fmt, smooth):
+    fc.two_witnesses(_deblock_planes, fmt, bd, hip, orc, smooth)
+
+
+def _deblock_planes(hip, orc, smooth, bd, dt, wide):
     w, h = 328, 200   # not multiples of 64; last SB partial
     rng = np.random.default_rng(7 + bd + smooth)
-    dt = np.uint8 if bd == 8 else np.uint16
+    gots, exps = [], []
     for seed, varied, sharp in ((15, False, 0), (16, True, 3), (17, True, 6)):
         mi, cols, rows = dc.make_mode_info(w, h, seed=seed, varied=varied)
         for plane, (pw, ph) in enumerate(((w, h), (w // 2, h // 2), (w // 2, h // 2))):
@@ -36,6 +54,7 @@ def test_deblock_planes(hip, orc, bd, smooth):
             pad = 16
             img = np.zeros((ph + 2 * pad + 4, pw + 2 * pad + 4), dt)
             img[:] = content(rng, *img.shape, bd, smooth).astype(dt)
+            if wide: plant(img[pad:pad + ph, pad:pad + pw], bd)
             exp = img.copy()
             off = (pad * img.shape[1] + pad) * img.itemsize
             orc.orc_deblock_plane(C.c_void_p(exp.ctypes.data + off), img.itemsize, img.shape[1], bd, ptr(ev), ptr(eh), ev.shape[1], ev.shape[0], sharp)
@@ -47,6 +66,8 @@ def test_deblock_planes(hip, orc, bd, smooth):
             if smooth:
                 assert (exp != img).any(), "test content never triggers a filter"
             assert np.array_equal(got, exp), (bd, smooth, plane, seed, np.argwhere(got != exp)[:4])
+            gots.append(got); exps.append(exp)
+    return gots, exps
 
 
 def test_single_direction_and_4k_property(hip, orc):
@@ -103,12 +124,19 @@ def test_plane_sse(hip, orc, bd):
             assert got == exp == closed == w * h * mx * mx, (mx, w, h, got, exp, closed)
 
 
-@pytest.mark.parametrize("bd,mode", [(8, 1), (8, 3), (10, 3)])
-def test_filter_level_search(hip, orc, pkg, bd, mode):
+SEARCH_CASES = [pytest.param(8, 1, None, id="8-1"), pytest.param(8, 3, None, id="8-3"), pytest.param(10, 3, None, id="10-3"), pytest.param(8, 3, np.uint16, id="u16-8-3")]
+
+
+@pytest.mark.parametrize("bd,mode,fmt", SEARCH_CASES)
+def test_filter_level_search(hip, orc, pkg, bd, mode, fmt):
     """svt_av1_pick_filter_level's per-plane search on the device vs the oracle's restatement of
     search_filter_level / try_filter_frame: same best level, same error, for luma (both directions) and chroma."""
+    fc.two_witnesses(_filter_level_search, fmt, bd, hip, orc, pkg, mode)
+
+
+def _filter_level_search(hip, orc, pkg, mode, bd, dt, wide):
     w, h = 328, 200
-    dt = np.uint8 if bd == 8 else np.uint16
+    results, expected = [], []
     rng = np.random.default_rng(91 + bd + mode)
     mi, cols, rows = dc.make_mode_info(w, h, seed=21, varied=False)
     for plane, (pw, ph) in enumerate(((w, h), (w // 2, h // 2), (w // 2, h // 2))):
@@ -118,6 +146,9 @@ def test_filter_level_search(hip, orc, pkg, bd, mode):
         yy, xx = np.mgrid[0:ph, 0:pw]
         blk = (((xx // 8) * 5 + (yy // 8) * 3) % 7 - 3) * (2 << (bd - 8))
         rec = np.clip(src.astype(np.int32) + blk + rng.integers(-1, 2, src.shape), 0, (1 << bd) - 1).astype(dt)
+        if wide:
+            plant(rec, bd)
+            fc.note_inputs(rec)      # the searches return levels and errors, no samples
         for dirn, start in (((0, 8), (1, 30)) if plane == 0 else ((0, 12),)):
             tmp = np.zeros_like(rec)
             best_err = C.c_int64()
@@ -135,14 +166,19 @@ def test_filter_level_search(hip, orc, pkg, bd, mode):
             assert np.array_equal(after, rec), "the unfiltered plane must stay untouched"
             assert (lvl.value, err.value) == (exp_lvl, best_err.value), (bd, mode, plane, dirn, lvl.value, exp_lvl, err.value, best_err.value)
             assert sum(1 for v in probes if v >= 0) >= 2
+            results.append((lvl.value, err.value)); expected.append((exp_lvl, best_err.value))
+    return results, expected
 
 
-@pytest.mark.parametrize("bd,mode", [(8, 1), (8, 3), (10, 3)])
-def test_filter_level_search_of_a_picture_in_lockstep(hip, orc, pkg, bd, mode):
+@pytest.mark.parametrize("bd,mode,fmt", SEARCH_CASES)
+def test_filter_level_search_of_a_picture_in_lockstep(hip, orc, pkg, bd, mode, fmt):
     """svt_hip_dlf_search_levels_picture_dev: the three planes' searches advanced together (the one or two levels each walk needs next are measured in one round trip) give what the
     oracle's restatement of search_filter_level gives plane by plane: same best level, same error; the unfiltered planes stay untouched."""
+    fc.two_witnesses(_lockstep_search, fmt, bd, hip, orc, pkg, mode)
+
+
+def _lockstep_search(hip, orc, pkg, mode, bd, dt, wide):
     w, h = 328, 200
-    dt = np.uint8 if bd == 8 else np.uint16
     rng = np.random.default_rng(191 + bd + mode)
     mi, cols, rows = dc.make_mode_info(w, h, seed=23, varied=False)
     planes = (pkg.DlfSearchPlane * 3)()
@@ -153,6 +189,9 @@ def test_filter_level_search_of_a_picture_in_lockstep(hip, orc, pkg, bd, mode):
         yy, xx = np.mgrid[0:ph, 0:pw]
         blk = (((xx // 8) * 5 + (yy // 8) * 3) % 7 - 3) * ((2 + plane) << (bd - 8))
         rec = np.clip(src.astype(np.int32) + blk + rng.integers(-1, 2, src.shape), 0, (1 << bd) - 1).astype(dt)
+        if wide:
+            plant(rec, bd)
+            fc.note_inputs(rec)      # the searches return levels and errors, no samples
         start = (8, 30, 3)[plane]
         tmp = np.zeros_like(rec)
         best_err = C.c_int64()
@@ -173,20 +212,26 @@ def test_filter_level_search_of_a_picture_in_lockstep(hip, orc, pkg, bd, mode):
         assert (best[plane], err[plane]) == exp[plane], (bd, mode, plane, best[plane], err[plane], exp[plane])
     assert hip.L.svt_hip_dlf_search_levels_picture_dev(hip.h, 4, planes, recs[0].itemsize, bd, d_s, best, err) != 0
     hip.free(d_s, *[x for d in keep for x in d])
+    return [(best[p], err[p]) for p in range(3)], exp
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_deblock_frame_all_planes(hip, orc, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_deblock_frame_all_planes(hip, orc, bd, fmt):
     """svt_hip_deblock_frame_dev (all three planes, one launch per direction) == three oracle plane calls; a NULL plane is skipped."""
+    fc.two_witnesses(_deblock_frame_all_planes, fmt, bd, hip, orc)
+
+
+def _deblock_frame_all_planes(hip, orc, bd, dt, wide):
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     w, h = 328, 200
     rng = np.random.default_rng(70 + bd)
-    dt = np.uint8 if bd == 8 else np.uint16
+    gots = []
     mi, cols, rows = dc.make_mode_info(w, h, seed=21, varied=True)
     planes, exp, edges = [], [], []
     for plane, (pw, ph) in enumerate(((w, h), (w // 2, h // 2), (w // 2, h // 2))):
         ev, eh = dc.build_edges(mi, cols, rows, plane, pw, ph)
         img = np.ascontiguousarray(content(rng, ph, pw + 8, bd, plane == 1).astype(dt))
+        if wide: plant(img[:, :pw], bd)
         e = img.copy()
         orc.orc_deblock_plane(ptr(e), img.itemsize, img.shape[1], bd, ptr(ev), ptr(eh), ev.shape[1], ev.shape[0], 2)
         planes.append(img); exp.append(e); edges.append((ev, eh))
@@ -199,25 +244,35 @@ def test_deblock_frame_all_planes(hip, orc, bd):
             got = hip.to_host(d_p[i], planes[i].shape, dt)
             assert np.array_equal(got, planes[i] if i == skip else exp[i]), (bd, skip, i)
             assert (exp[i] != planes[i]).any()
+            if skip is None: gots.append(got)
         hip.free(*d_p, *d_ev, *d_eh)
+    return gots, exp
 
 
-@pytest.mark.parametrize("bd,size", [(bd, size) for size in [(328, 200), (1928, 1088), (136, 72), (3840, 2160)] for bd in (8, 10)
-                                     if not (size == (3840, 2160) and bd == 10)])   # the 4K case runs once (8-bit)
-def test_deblock_frame_fused(hip, orc, bd, size):
+FUSED_CASES = [(bd, size) for size in [(328, 200), (1928, 1088), (136, 72), (3840, 2160)] for bd in (8, 10) if not (size == (3840, 2160) and bd == 10)]   # the 4K case runs once (8-bit)
+
+
+@pytest.mark.parametrize("bd,size,fmt", [pytest.param(bd, size, None, id=f"{bd}-size{i}") for i, (bd, size) in enumerate(FUSED_CASES)] +
+                                        [pytest.param(8, (136, 72), np.uint16, id="u16-8-136x72")])         # 8-bit samples in 16-bit planes: the smallest ragged size
+def test_deblock_frame_fused(hip, orc, bd, size, fmt):
     """svt_hip_deblock_frame_fused_dev (both directions of all planes in one out-of-place launch, tiles of 128 x 64 with a 7-sample halo) == the oracle's two passes per
     plane: sizes whose last tile is partial in both directions, varied transform sizes (4 / 8 / 14-tap luma, 4 / 6-tap chroma), three sharpness values; the source planes
     stay untouched, the destination's samples outside the plane extent too, a NULL plane is skipped."""
+    fc.two_witnesses(_deblock_frame_fused, fmt, bd, hip, orc, size)
+
+
+def _deblock_frame_fused(hip, orc, size, bd, dt, wide):
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     w, h = size
     rng = np.random.default_rng(170 + bd + w)
-    dt = np.uint8 if bd == 8 else np.uint16
+    gots, exps = [], []
     for seed, varied, sharp in ((21, True, 0), (22, True, 3), (23, False, 6)):
         mi, cols, rows = dc.make_mode_info(w, h, seed=seed, varied=varied)
         planes, exp, edges = [], [], []
         for plane, (pw, ph) in enumerate(((w, h), (w // 2, h // 2), (w // 2, h // 2))):
             ev, eh = dc.build_edges(mi, cols, rows, plane, pw, ph)
             img = np.ascontiguousarray(content(rng, ph + 3, pw + 8, bd, plane != 2).astype(dt))   # stride > width, rows below the plane
+            if wide: plant(img[:ph, :pw], bd)
             e = img.copy()
             orc.orc_deblock_plane(ptr(e), img.itemsize, img.shape[1], bd, ptr(ev), ptr(eh), ev.shape[1], ev.shape[0], sharp)
             planes.append(img); exp.append(e); edges.append((ev, eh))
@@ -241,8 +296,10 @@ def test_deblock_frame_fused(hip, orc, bd, size):
                     continue
                 assert np.array_equal(got[:ph, :pw], exp[i][:ph, :pw]), (bd, size, seed, i, np.argwhere(got[:ph, :pw] != exp[i][:ph, :pw])[:4])
                 assert (got[ph:] == 37).all() and (got[:, pw:] == 37).all(), "samples outside the plane extent were written"
-                assert i == 2 or (exp[i][:ph, :pw] != planes[i][:ph, :pw]).any()   # plane 2 is noise: nothing may be flat enough to filter
+                assert i == 2 or wide or (exp[i][:ph, :pw] != planes[i][:ph, :pw]).any()   # plane 2 is noise: nothing may be flat enough to filter
+                if skip is None: gots.append(got[:ph, :pw]); exps.append(exp[i][:ph, :pw])
             hip.free(*d_p, *d_o, *d_ev, *d_eh)
+    return gots, exps
 
 
 def host_edges_crop(L, raw, cols, rows, plane, pw, ph, fw, fh):
@@ -310,3 +367,58 @@ def test_edge_planes_built_on_the_device(hip, w, h, pad):
             assert np.array_equal(gv, ev) and np.array_equal(gh, eh), (levels, p, np.argwhere(gv != ev)[:4], np.argwhere(gh != eh)[:4])
         hip.free(*[o for pair in outs for o in pair if o])
     hip.free(d_mi)
+
+
+class LpfEdge(C.Structure):          # SvtHipLpfEdge (include/svt_hip.h)
+    _fields_ = [("off", C.c_int32), ("dir", C.c_uint8), ("len", C.c_uint8), ("blimit", C.c_uint8), ("limit", C.c_uint8), ("thresh", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+assert C.sizeof(LpfEdge) == 12
+
+
+def _lpf_edges_batch(hip, orc, bd, dt, wide):
+    """One 4-sample segment in the middle of every 16 x 16 cell of a 208 x 176 plane (the taps of the 14-sample filter stay inside the cell, so no two segments touch):
+    both directions x the four lengths x random thresholds, on cells that are smooth with a step at the edge, within 3 of either end of the range (every filter fires and
+    its clamp decides), all max, all 0, a 0 / max checkerboard, or noise.  143 segments: the last workgroup of 16 is ragged."""
+    rng = np.random.default_rng(600 + bd)
+    mx, sc = (1 << bd) - 1, 1 << (bd - 8)
+    W, H = 208, 176
+    img = np.zeros((H, W + 5), np.int64)
+    edges, k = [], 0
+    for cy in range(0, H, 16):
+        for cx in range(0, W, 16):
+            d, ln = k & 1, (4, 6, 8, 14)[(k >> 1) & 3]
+            kind = (k >> 3) % 7
+            yy, xx = np.mgrid[0:16, 0:16]
+            side = (xx if d == 0 else yy) >= 8
+            if kind == 0: cell = int(rng.integers(30, 200)) * sc + side * int(rng.integers(-6, 7)) * sc + rng.integers(-1, 2, (16, 16)) * sc
+            elif kind == 1: cell = mx - rng.integers(0, 4, (16, 16)) - side * 2
+            elif kind == 2: cell = rng.integers(0, 4, (16, 16)) + side * 2
+            elif kind == 3: cell = np.full((16, 16), mx)
+            elif kind == 4: cell = np.zeros((16, 16), np.int64)
+            elif kind == 5: cell = ((yy + xx) & 1) * mx
+            else: cell = rng.integers(0, mx + 1, (16, 16))
+            img[cy:cy + 16, cx:cx + 16] = np.clip(cell, 0, mx)
+            edges.append(LpfEdge((cy + 6) * img.shape[1] + cx + 8 if d == 0 else (cy + 8) * img.shape[1] + cx + 6, d, ln,
+                                 int(rng.integers(1, 80)), int(rng.integers(1, 20)), int(rng.integers(0, 5))))
+            k += 1
+    img = img.astype(dt)
+    n = len(edges)
+    assert n == 143
+    exp = img.copy()
+    for e in edges:
+        orc.orc_lpf_edge(C.c_void_p(exp.ctypes.data + e.off * exp.itemsize), exp.itemsize, exp.shape[1], e.dir, e.len, e.blimit, e.limit, e.thresh, bd)
+    arr = (LpfEdge * n)(*edges)
+    d_img, d_e = hip.to_device(img), hip.to_device(np.frombuffer(bytes(arr), np.uint8))
+    hip.check(hip.L.svt_hip_lpf_edges_batch_dev(hip.h, img.itemsize, bd, d_img, img.shape[1], d_e, n), "lpf edges")
+    got = hip.to_host(d_img, img.shape, dt)
+    hip.free(d_img, d_e)
+    assert (exp != img).sum() > 200, "the content triggers too few filters"
+    assert np.array_equal(got, exp), (bd, np.argwhere(got != exp)[:4])
+    return [got], [exp]
+
+
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_lpf_edges_batch(hip, orc, bd, fmt):
+    """svt_hip_lpf_edges_batch_dev (a list of 4-sample edge segments with explicit thresholds) == orc_lpf_edge, which test_oracle_vs_ref.py pins to the reference's 16 edge filters"""
+    fc.two_witnesses(_lpf_edges_batch, fmt, bd, hip, orc)

@@ -1132,3 +1132,44 @@ def test_hooks_and_wrappers_together_10bit_on_gpu(workdir):
     assert (got["ivf"], got["recon"]) == (ref["ivf"], ref["recon"])
     assert all(v[1] == 0 for v in got["hooks"].values()) and sum(v[0] for v in got["hooks"].values()) > 10, got["hooks"]
     _check_delegations(got, EXPECTED_DELEGATIONS["both"], "both")
+
+
+# ------------------------------------------------------------------------------------------------ 8-bit video through the 16-bit pipeline
+# `-16bit-pipeline 1` (static_config.is_16bit_pipeline): every stage after mode decision works on uint16_t planes whose samples are still 8-bit, so the
+# loop-filter bridge hands the library pix_bytes = 2 with bd = 8 (integration/svt_hip_lf_bridge.c: is_16bit_of) -- the third template instance of the kernels.
+PIPE16 = ("-16bit-pipeline", "1")
+# name: (w, h, frames, preset, qp, seed, SVT_HIP_HOOKS, hooks that must have run)
+PIPE16_CASES = {
+    "p16_192x128_m6": (192, 128, 5, 6, 35, 31, "all", ALL - {"tf_me", "tf_subpel"}),     # the alt-ref window of so short a clip has no ME batch
+    "p16_cif_m6": (352, 288, 8, 6, 35, 37, "all", ALL),
+    "p16_192x128_m4_optin": (192, 128, 4, 4, 40, 41, "all," + ",".join(E.OPT_IN_HOOKS), set(E.OPT_IN_HOOKS)),
+}
+
+
+def _check_pipe16(case, workdir, env, tag):
+    w, h, n, preset, q, seed, hooks, must = PIPE16_CASES[case]
+    return _check_geometry(case, w, h, n, 8, preset, q, seed, workdir, dict(env, SVT_HIP_HOOKS=hooks), tag, must=must, extra=PIPE16)
+
+
+@pytest.mark.parametrize("case", list(PIPE16_CASES))
+def test_16bit_pipeline_on_8bit_clip_on_cpu_test_double(case, workdir):
+    _check_pipe16(case, workdir, {"LD_LIBRARY_PATH": E.MOCK_DIR}, "mock")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["p16_192x128_m6", "p16_192x128_m4_optin"])
+def test_16bit_pipeline_on_8bit_clip_on_gpu(case, workdir):
+    got = _check_pipe16(case, workdir, {}, "hip")
+    assert "svt_hip MOCK" not in got["log"], "the GPU test must load svt-av1_amd/libsvtav1_hip.so, not the CPU test double"
+
+
+def test_16bit_pipeline_codes_the_same_bitstream_as_the_8bit_pipeline(workdir):
+    """The unpatched reference codes an 8-bit clip to the same bitstream with and without the flag: the 16-bit pipeline computes, on widened samples, what the
+    8-bit pipeline computes -- which is why the (u16, 8) kernel tests may also compare with the (u8, 8) result widened.  (The reconstruction FILES differ and
+    are not compared here.)"""
+    w, h, n, preset, q, seed = 192, 128, 5, 6, 35, 31
+    clip = os.path.join(workdir, "p16_flag.src.yuv")
+    E.make_clip(clip, w, h, n, seed=seed, bd=8)
+    plain = E.encode(E.APP_REF, clip, w, h, n, preset, q, 8, os.path.join(workdir, "p16_flag.ref8"))
+    wide = E.encode(E.APP_REF, clip, w, h, n, preset, q, 8, os.path.join(workdir, "p16_flag.ref16"), extra_args=PIPE16)
+    assert wide["ivf"] == plain["ivf"]

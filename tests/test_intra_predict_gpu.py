@@ -6,23 +6,43 @@ import intra_common as ic
 
 pytestmark = pytest.mark.gpu
 CHUNK = 4096
-BDS = [(np.uint8, 8), (np.uint16, 10)]
+BDS = [(np.uint8, 8), (np.uint16, 10), (np.uint16, 8)]   # (uint16, 8): 8-bit samples in 16-bit planes, what the encoder's 16-bit pipeline hands over for 8-bit video
 
 
 def _check(hip, pkg, L, recs, jobs, bd, what):
+    """Every block against the reference's predictors of the records' sample type (uint16: the high-bit-depth functions with this bd).  8-bit samples in 16-bit
+    planes have a second witness, the same records as uint8: the reference's 8-bit functions give the same blocks (asserted here, on the CPU), and so does the device."""
     ic.prepare(L)
     assert len(jobs) == len(recs)
+    wide = recs.dtype == np.uint16 and bd == 8
+    lo, hi = 1 << 16, 0
     for s in range(0, len(jobs), CHUNK):
         blocks, _ = ic.run_batch(hip, pkg, recs[s:s + CHUNK], jobs[s:s + CHUNK], bd)
+        if wide: blocks8, _ = ic.run_batch(hip, pkg, recs[s:s + CHUNK].astype(np.uint8), jobs[s:s + CHUNK], 8)
         for i, (j, got) in enumerate(zip(jobs[s:s + CHUNK], blocks)):
             exp = ic.ref_predict(L, recs[s + i], bd, j)
             assert (got == exp).all(), f"{what}: job {s + i} {j} differs at {np.argwhere(got != exp)[0].tolist()}"
+            if wide:
+                exp8 = ic.ref_predict(L, np.ascontiguousarray(recs[s + i].astype(np.uint8)), 8, j)
+                assert exp8.dtype == np.uint8 and (exp == exp8).all(), f"{what}: job {s + i} {j}: the reference's 8-bit and high-bit-depth predictors differ"
+                assert (got == blocks8[i]).all(), f"{what}: job {s + i} {j}: the device's (2, 8) and (1, 8) results differ"
+                lo, hi = min(lo, int(exp.min())), max(hi, int(exp.max()))
+    if wide: assert (lo, hi) == (0, 255), (what, lo, hi)
+
+
+def _extremes(recs, dtype, bd):
+    """8-bit samples in 16-bit planes: every ninth record all max, the next all 0, the next alternating 0 / max (the other formats keep their content)"""
+    if dtype == np.uint16 and bd == 8:
+        recs[::9] = 255; recs[1::9] = 0; recs[2::9, :, ::2] = 0; recs[2::9, :, 1::2] = 255
+    return recs
 
 
 def _records_for(rng, jobs_per_kind, dtype, bd, n_kinds):
-    """`jobs_per_kind` random records per kind plus one all-zero and one all-max record."""
+    """`jobs_per_kind` random records per kind plus one all-zero and one all-max record; 8-bit samples in 16-bit planes: the first of each kind alternates 0 / max."""
     per = jobs_per_kind + 2
     recs = ic.random_records(rng, per * n_kinds, dtype, bd)
+    if dtype == np.uint16 and bd == 8:
+        recs[::per, :, ::2] = 0; recs[::per, :, 1::2] = 255
     recs[jobs_per_kind::per] = 0
     recs[jobs_per_kind + 1::per] = (1 << bd) - 1
     return recs, per
@@ -86,7 +106,7 @@ def test_edge_filter_alone(hip, pkg, ref, dtype, bd):
                 jobs.append(ic.make_job(tx_size=4, mode=3, strength_above=s, npx_above=n, start_m1=m1))
                 jobs.append(ic.make_job(tx_size=4, mode=2, strength_left=s, npx_left=n, start_m1=m1))
                 jobs.append(ic.make_job(tx_size=4, mode=7, angle_delta=3, strength_left=s, npx_left=n, start_m1=m1))
-    recs = ic.random_records(rng, len(jobs), dtype, bd)
+    recs = _extremes(ic.random_records(rng, len(jobs), dtype, bd), dtype, bd)
     _check(hip, pkg, ref, recs, jobs, bd, "edge filter")
 
 
@@ -110,6 +130,7 @@ def test_corner_and_upsample_alone(hip, pkg, ref, dtype, bd):
     recs = ic.random_records(rng, len(jobs), dtype, bd)
     recs[::7] = (1 << bd) - 1
     recs[3::7, :, ::2] = 0   # alternating extremes: the up-sampling filter overshoots and is clipped
+    if dtype == np.uint16 and bd == 8: recs[5::7] = 0      # 8-bit samples in 16-bit planes carry all-0 records too
     _check(hip, pkg, ref, recs, jobs, bd, "corner / up-sampling")
 
 
@@ -126,7 +147,7 @@ def test_mixed_batch_guard_and_empty(hip, pkg, ref, dtype, bd):
     good = list(jobs)
     for i, chg in bad_at.items():
         jobs[i] = dict(jobs[i]); jobs[i].update(chg)
-    recs = ic.random_records(rng, len(jobs), dtype, bd)
+    recs = _extremes(ic.random_records(rng, len(jobs), dtype, bd), dtype, bd)
     blocks, plane = ic.run_batch(hip, pkg, recs, jobs, bd)
     marker = 0x5A if dtype == np.uint8 else 0x2A5
     for i, (j, got) in enumerate(zip(jobs, blocks)):

@@ -19,6 +19,11 @@ def _pair(rng, it):
     return src, refb
 
 
+# The three sample formats of the pins below: (uint16, 8) is 8-bit samples in 16-bit planes (the encoder's 16-bit pipeline on 8-bit video) -- the reference's
+# HIGH-bit-depth function with bd = 8, content drawn from 0 .. 255.
+FMT3 = ((8, np.uint8), (10, np.uint16), (8, np.uint16))
+
+
 def test_ext_all_sad_and_32x32_64x64(orc, ref):
     rng = np.random.default_rng(13596)
     for it in range(120):
@@ -357,10 +362,11 @@ def test_deblock_edge_filters(orc, ref):
     """All 16 edge filters (lbd/hbd x 4/6/8/14 x h/v) on random and smooth data
     (/root/reference/test/DeblockTest.cc:210-306)."""
     rng = np.random.default_rng(99)
-    for bd, dt in ((8, np.uint8), (10, np.uint16)):
+    for bd, dt in FMT3:
+        hbd = dt == np.uint16
         for length in (4, 6, 8, 14):
             for d, dname in ((0, "vertical"), (1, "horizontal")):
-                name = f"svt_aom_{'highbd_' if bd > 8 else ''}lpf_{dname}_{length}_c"
+                name = f"svt_aom_{'highbd_' if hbd else ''}lpf_{dname}_{length}_c"
                 for it in range(300):
                     base = rng.integers(0, 1 << bd)
                     spread = int(rng.choice([1, 2, 4, 16, 64, 1 << bd]))
@@ -370,7 +376,7 @@ def test_deblock_edge_filters(orc, ref):
                     th = np.full(16, rng.integers(0, 16), np.uint8)
                     off = 10 * 24 + 10
                     pa = C.c_void_p(a.ctypes.data + off * a.itemsize); pb = C.c_void_p(b.ctypes.data + off * b.itemsize)
-                    if bd > 8:
+                    if hbd:
                         getattr(ref, name)(pa, 24, ptr(bl), ptr(li), ptr(th), bd)
                     else:
                         getattr(ref, name)(pa, 24, ptr(bl), ptr(li), ptr(th))
@@ -453,8 +459,8 @@ def test_cdef_search_filter_block_level(orc, ref):
     """Whole filter-block strength search (64 strengths x 3 planes incl. the FP64 luma distortion) vs
     svt_cdef_filter_fb + compute_cdef_dist* driven like cdef_seg_search; multi-fb frame so that inner
     and picture-edge halos are both exercised."""
-    for bd in (8, 10):
-        src, rec, skip8 = cc.make_frame(144, 80, bd, seed=bd)   # 3 x 2 fbs, ragged right/bottom fb (16 px)
+    for bd, dt in FMT3:
+        src, rec, skip8 = cc.make_frame(144, 80, bd, seed=bd, dtype=dt)   # 3 x 2 fbs, ragged right/bottom fb (16 px)
         mse = cc.orc_search(orc, rec, src, bd, skip8, 5)
         nh = 3
         for fbr in range(2):
@@ -469,8 +475,8 @@ def test_cdef_search_filter_block_level(orc, ref):
 def test_cdef_search_chart(orc, ref):
     """The same on the direction chart (cdef_common.make_chart_frame: every direction, flat blocks, exact cost ties, saturated samples at the picture
     edge, anti-correlated source), dampings 3-6.  208 x 144: ref_search_fb cannot stage an 8-sample-wide last filter block."""
-    for bd in (8, 10):
-        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED)
+    for bd, dt in FMT3:
+        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED, dt)
         for damping in (3, 4, 5, 6):
             mse = cc.orc_search(orc, rec, src, bd, skip8, damping)
             seen = 0
@@ -489,8 +495,8 @@ def test_cdef_apply_chart(orc, ref):
     """orc_cdef_apply_frame vs svt_cdef_filter_fb driven like svt_av1_cdef_frame (cdef_common.ref_apply_fb) on the direction chart: strengths 0 / 0,
     luma off / chroma on, chroma off / luma on, 63 / 63 and secondary index 3 each meet another filter block at every damping."""
     pairs = set()
-    for bd in (8, 10):
-        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED)
+    for bd, dt in FMT3:
+        src, rec, skip8 = cc.make_chart_frame(208, 144, bd, cc.CHART_SEED, dt)
         for damping in (3, 4, 5, 6):
             ys, uvs = cc.chart_strengths(12, damping)
             pairs |= set(zip(ys.tolist(), uvs.tolist()))
@@ -526,7 +532,7 @@ def test_interp_kernels_and_convolve_sr(orc, ref):
         assert np.array_equal(mine[b], np.ctypeslib.as_array((C.c_int16 * 8 * 16).in_dll(ref, name))), name
     rng = np.random.default_rng(2)
     cp = _ConvP(); cp.round_0 = 3; cp.round_1 = 11
-    for bd, dt, pre in ((8, np.uint8, "svt_av1_"), (10, np.uint16, "svt_av1_highbd_")):
+    for bd, dt, pre in ((8, np.uint8, "svt_av1_"), (10, np.uint16, "svt_av1_highbd_"), (8, np.uint16, "svt_av1_highbd_")):
         for it in range(300):
             w = int(rng.choice([4, 8, 16, 32, 64, 128])); h = int(rng.choice([4, 8, 16, 32, 64, 128]))
             bx = int(rng.integers(0, 6)); by_ = int(rng.integers(0, 6))
@@ -535,13 +541,14 @@ def test_interp_kernels_and_convolve_sr(orc, ref):
             if it % 7 == 0: sy = 0
             src = rng.integers(0, 1 << bd, (h + 16, w + 24)).astype(dt)
             if it % 11 == 0: src[:] = (1 << bd) - 1
+            if dt == np.uint16 and bd == 8 and it % 11 == 1: src[:] = rng.integers(0, 2, src.shape) * 255      # binary 0 / 255: the filters overshoot both ends
             a = np.zeros((h, w + 3), dt); b = np.zeros((h, w + 3), dt)
             fx = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[bx])), 8, 16, 0)
             fy = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[by_])), 8, 16, 0)
             name = pre + "convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(sx != 0), int(sy != 0))] + "_sr_c"
             sp = C.c_void_p(src.ctypes.data + (8 * src.shape[1] + 8) * src.itemsize)
             args = [sp, src.shape[1], ptr(a), a.shape[1], w, h, C.byref(fx), C.byref(fy), sx, sy, C.byref(cp)]
-            if bd > 8: args.append(bd)
+            if dt == np.uint16: args.append(bd)
             getattr(ref, name)(*args)
             orc.orc_convolve_sr(sp, src.shape[1], ptr(b), b.shape[1], src.itemsize, w, h, bx, by_, sx, sy, bd)
             assert np.array_equal(a, b), (name, w, h, sx, sy)
@@ -661,8 +668,8 @@ def test_sgr_tables_filter_apply_and_projection(orc, ref):
     rng = np.random.default_rng(21)
     orc.orc_sgr_proj_error.restype = C.c_int64
     ref.svt_av1_lowbd_pixel_proj_error_c.restype = C.c_int64; ref.svt_av1_highbd_pixel_proj_error_c.restype = C.c_int64
-    for bd, dt in ((8, np.uint8), (10, np.uint16)):
-        hb = int(bd > 8)
+    for bd, dt in FMT3:
+        hb = int(dt == np.uint16)
         for it in range(24):
             ep = it % 16
             w, h = int(rng.choice([64, 40, 8, 64])), int(rng.choice([64, 56, 24, 8]))
@@ -708,8 +715,8 @@ def test_sgr_finer_search_and_unit_search(orc, ref):
     orc.orc_sgr_finer_search.restype = C.c_int64; ref.ref_shim_sgr_finer_search.restype = C.c_int64
     rng = np.random.default_rng(91)
     rstbuf = np.zeros(ref.ref_shim_sgr_rstbuf_ints(), np.int32)
-    for bd, dt in ((8, np.uint8), (10, np.uint16)):
-        hb = int(bd > 8)
+    for bd, dt in FMT3:
+        hb = int(dt == np.uint16)
         cvt = (lambda a: C.c_void_p(a >> 1)) if hb else (lambda a: C.c_void_p(a))   # CONVERT_TO_BYTEPTR
         for it, (w, h, ss) in enumerate(((64, 64, 0), (96, 72, 0), (40, 56, 1), (128, 120, 0), (32, 32, 1), (72, 40, 1))):
             yy, xx = np.mgrid[0:h + 6, 0:w + 6]
@@ -755,6 +762,10 @@ def test_plane_sse_kernels(orc, ref):
         a16 = rng.integers(0, 1024, (h, w + 5)).astype(np.uint16); b16 = rng.integers(0, 1024, (h, w + 8)).astype(np.uint16)
         assert orc.orc_plane_sse(2, ptr(a16), a16.shape[1], ptr(b16), b16.shape[1], w, h) == \
             ref.svt_full_distortion_kernel16_bits_c(ptr(a16), 0, a16.shape[1], ptr(b16), 0, b16.shape[1], w, h)
+        a16 = rng.integers(0, 256, (h, w + 5)).astype(np.uint16); b16 = rng.integers(0, 256, (h, w + 8)).astype(np.uint16)     # 8-bit samples in 16-bit planes
+        a16[:h // 2] = 255; b16[:h // 2] = 0
+        assert orc.orc_plane_sse(2, ptr(a16), a16.shape[1], ptr(b16), b16.shape[1], w, h) == \
+            ref.svt_full_distortion_kernel16_bits_c(ptr(a16), 0, a16.shape[1], ptr(b16), 0, b16.shape[1], w, h)
 
 
 def test_restoration_units_and_stripe_apply(orc, ref):
@@ -772,8 +783,7 @@ def test_restoration_units_and_stripe_apply(orc, ref):
                 assert orc.orc_rest_unit_limits(pw, ph, ss, US, ptr(lo)) == nu
                 assert ref.ref_shim_rest_unit_limits(fw, fh, plane, US, ptr(lr)) == nu
                 assert np.array_equal(lo, lr), (fw, fh, plane, US)
-                for bd in (8, 10):
-                    dt = np.uint8 if bd == 8 else np.uint16
+                for bd, dt in FMT3:
                     yy, xx = np.mgrid[0:ph, 0:pw]
                     base = (90 + 50 * np.sin(xx / 9.0) * np.cos(yy / 6.0) + 25 * (((xx // 8) + (yy // 8)) % 2)) * (1 << (bd - 8))
                     dbl = np.clip(base + rng.normal(0, 6 * (1 << (bd - 8)), (ph, pw)), 0, (1 << bd) - 1).astype(dt)
@@ -795,7 +805,7 @@ def test_restoration_units_and_stripe_apply(orc, ref):
                     orc.orc_lr_apply_plane(ptr(dbl), pw, C.c_void_p(buf_o.ctypes.data + off), st, buf_o.itemsize, pw, ph, ss, ss, US, bd,
                                            ptr(u_ep), ptr(u_xqd), ptr(u_wn), ptr(dst_o), pw)
                     dst_pad = np.zeros((ph + 8, pw + 32), dt)               # the reference's stripe filter overshoots up to 15 columns
-                    assert ref.ref_shim_lr_apply_plane_ex(plane, bd, int(bd > 8), fw, fh, ptr(dbl), pw, C.c_void_p(buf_r.ctypes.data + off), st,
+                    assert ref.ref_shim_lr_apply_plane_ex(plane, bd, int(dt == np.uint16), fw, fh, ptr(dbl), pw, C.c_void_p(buf_r.ctypes.data + off), st,
                                                           ptr(dst_pad), pw + 32, US, ptr(u_ep), ptr(u_xqd), ptr(u_wn)) == 0
                     dst_r = dst_pad[:ph, :pw]
                     assert np.array_equal(dst_o, dst_r), (fw, fh, plane, US, bd, np.argwhere(dst_o != dst_r)[:5])
@@ -832,14 +842,14 @@ def test_wiener_stats_and_convolve(orc, ref):
     """orc_wiener_compute_stats == svt_av1_compute_stats_c / _highbd_c (windows 7, 5, 3; ragged unit rectangles),
     orc_wiener_convolve_add_src == svt_av1_[highbd_]wiener_convolve_add_src_c (symmetric 7-tap kernels over the legal tap ranges)."""
     rng = np.random.default_rng(808)
-    for bd, dt in ((8, np.uint8), (10, np.uint16)):
+    for bd, dt in FMT3:
         dgd = rng.integers(0, 1 << bd, (120, 140)).astype(dt); src = np.clip(dgd.astype(np.int32) + rng.integers(-20, 21, dgd.shape), 0, (1 << bd) - 1).astype(dt)
         for win in (7, 5, 3):
             for (h0, h1, v0, v1) in ((8, 72, 8, 72), (10, 101, 5, 37), (30, 31, 40, 41)):
                 w2 = win * win
                 Mo, Ho = np.zeros(w2, np.int64), np.zeros(w2 * w2, np.int64); Mr, Hr = Mo.copy(), Ho.copy()
                 orc.orc_wiener_compute_stats(win, ptr(dgd), ptr(src), dgd.itemsize, bd, h0, h1, v0, v1, 140, 140, ptr(Mo), ptr(Ho))
-                if bd == 8:
+                if dt == np.uint8:
                     ref.svt_av1_compute_stats_c(win, ptr(dgd), ptr(src), h0, h1, v0, v1, 140, 140, ptr(Mr), ptr(Hr))
                 else:
                     ref.svt_av1_compute_stats_highbd_c(win, C.c_void_p(dgd.ctypes.data >> 1), C.c_void_p(src.ctypes.data >> 1), h0, h1, v0, v1, 140, 140, ptr(Mr), ptr(Hr), bd)
@@ -863,7 +873,7 @@ def test_wiener_stats_and_convolve(orc, ref):
             eo = np.zeros((h, w + 5), dt); er = np.zeros((h, w + 5), dt)
             p = dgd.ctypes.data + (20 * 140 + 30) * dgd.itemsize
             orc.orc_wiener_convolve_add_src(C.c_void_p(p), 140, ptr(eo), w + 5, dgd.itemsize, ptr(fx), ptr(fy), w, h, bd)
-            if bd == 8:
+            if dt == np.uint8:
                 ref.svt_av1_wiener_convolve_add_src_c(C.c_void_p(p), C.c_int64(140), ptr(er), C.c_int64(w + 5), ptr(fx), ptr(fy), w, h, C.byref(cp))
             else:
                 ref.svt_av1_highbd_wiener_convolve_add_src_c(C.c_void_p(p >> 1), C.c_int64(140), C.c_void_p(er.ctypes.data >> 1), C.c_int64(w + 5), ptr(fx), ptr(fy), w, h, C.byref(cp), bd)
@@ -901,9 +911,9 @@ def test_wiener_initial_filter(orc, ref):
 import tf_common as tfc
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd,fmt", [pytest.param(8, None, id="8"), pytest.param(10, None, id="10"), pytest.param(8, np.uint16, id="u16-8")])
 @pytest.mark.parametrize("ss", [0, 1])
-def test_wiener_tap_refinement_walk(ref, bd, ss):
+def test_wiener_tap_refinement_walk(ref, bd, fmt, ss):
     """The restatement of finer_tile_search_wiener_seg (Encoder/Codec/EbRestorationPick.c:1092-1200) that stands in for the device's wiener_walk_kernel on boxes without a
     GPU -- the state machine of oracle/hip_mock.c (svt_hip_wiener_walk_units_dev of the CPU test double, every probe on the oracle's restoration filter), which the GPU test
     tests/test_sgr_gpu.py::test_wiener_walk_units compares the device with -- against the reference's own static function, driven through oracle/ref_shim_restpick.c:
@@ -919,7 +929,7 @@ def test_wiener_tap_refinement_walk(ref, bd, ss):
     EXT = tg.EXT
     for (w, h, US, win) in ((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3)):
         if ss and win == 7: win = 5     # chroma planes search the 5-tap window at most (search_wiener_seg :1352-1358)
-        src, ext = tg.make_planes(w, h, bd, 190 + bd + ss + US)
+        src, ext = tg.make_planes(w, h, bd, 190 + bd + ss + US, fmt, fmt is not None)      # fmt: 8-bit samples in 16-bit planes, with the planted extremes of the GPU test
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         rng = np.random.default_rng(31 + ss + win)
         dbl = np.clip(ext[EXT:EXT + h, EXT:EXT + w].astype(np.int32) + rng.integers(-9, 10, (h, w)) * (1 << (bd - 8)), 0, (1 << bd) - 1).astype(ext.dtype)
@@ -954,8 +964,8 @@ def test_temporal_filter_planewise_noise_and_divu(orc, ref):
     def _cnt0(it):
         r2 = np.random.default_rng(it); [r2.integers(0, 1 << 20, 32 * 64) for _ in range(3)]
         return r2.integers(0, 3000, 32 * 64).astype(np.int64)
-    for bd in (8, 10):
-        dt = np.uint8 if bd == 8 else np.uint16
+    for bd, dt in FMT3:
+        hbd = int(dt == np.uint16)
         seen = set()
         for it in range(24):
             ss = 1 if it % 6 else 0
@@ -985,7 +995,7 @@ def test_temporal_filter_planewise_noise_and_divu(orc, ref):
                     b = blk[0]
                     ref.ref_shim_tf_planewise(ptr(np.ascontiguousarray(b["mv16_x"])), ptr(np.ascontiguousarray(b["mv16_y"])), ptr(np.ascontiguousarray(b["err16"])),
                                               ptr(np.ascontiguousarray(b["mv32_x"])), ptr(np.ascontiguousarray(b["mv32_y"])), ptr(np.ascontiguousarray(b["err32"])),
-                                              ptr(np.ascontiguousarray(b["split"])), *common, int(bd > 8), bd, *tail)
+                                              ptr(np.ascontiguousarray(b["split"])), *common, hbd, bd, *tail)
                 else:
                     orc.orc_tf_planewise(ptr(blk), *common, src[0].itemsize, bd, *tail)
                 outs.append(acc + cnt)
@@ -1001,7 +1011,7 @@ def test_temporal_filter_planewise_noise_and_divu(orc, ref):
             img = (img * (1 << (bd - 8))).astype(dt)
             if it == 3: img[:] = rng.integers(0, 1 << bd, (h, w))          # all edges: too few smooth pixels -> -1
             out = np.zeros(2, np.int64)
-            e = ref.ref_shim_estimate_noise(ptr(img), int(bd > 8), bd, w, h, w)
+            e = ref.ref_shim_estimate_noise(ptr(img), hbd, bd, w, h, w)
             g = orc.orc_tf_estimate_noise(ptr(img), img.itemsize, bd, w, h, w, ptr(out))
             assert e == g, (bd, it, e, g)
     ref.ref_shim_od_divu.restype = C.c_uint32
@@ -1024,7 +1034,8 @@ def test_compound_prediction(orc, ref):
     Block sizes, phases and filters as /root/reference/test/convolve_2d_test.cc (jnt cases) and CompBlendTest.cc."""
     rng = np.random.default_rng(77)
     W, H = 1280, 1024
-    for bd, dt in ((8, np.uint8), (10, np.uint16), (12, np.uint16)):
+    for bd, dt in ((8, np.uint8), (10, np.uint16), (12, np.uint16), (8, np.uint16)):
+        hbd = dt == np.uint16
         r0 = 5 if bd == 12 else 3           # get_conv_params_no_round: ROUND0_BITS (+ 2 at 12 bits)
         ref0 = rng.integers(0, 1 << bd, (H, W)).astype(dt); ref1 = rng.integers(0, 1 << bd, (H, W)).astype(dt)
         ref0[:130, :130] = (1 << bd) - 1; ref1[:130, :130] = 0                # extreme block
@@ -1034,7 +1045,7 @@ def test_compound_prediction(orc, ref):
             b.src0_x += 64; b.src0_y += 64; b.src1_x += 64; b.src1_y += 64
         dst = np.zeros((H, W), dt); m_orc = masks.copy()
         orc.orc_compound_predict_batch(ref0.itemsize, bd, ptr(ref0), W, ptr(ref1), W, ptr(dst), W, ptr(m_orc), blks, 0, n)
-        pre = "svt_av1_" if bd == 8 else "svt_av1_highbd_"
+        pre = "svt_av1_highbd_" if hbd else "svt_av1_"
         for i, b in enumerate(blks):
             w, h = b.w, b.h
             fx = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[b.bank_x])), 8, 16, 0)
@@ -1046,7 +1057,7 @@ def test_compound_prediction(orc, ref):
                 name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(sx_ != 0), int(sy_ != 0))] + "_c"
                 sp = C.c_void_p(plane.ctypes.data + (py * W + px) * plane.itemsize)
                 args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), sx_, sy_, C.byref(cp)]
-                if bd > 8: args.append(bd)
+                if hbd: args.append(bd)
                 getattr(ref, name)(*args)
                 mine = np.zeros((h, w), np.uint16)
                 orc.orc_jnt_convolve_d16(sp, W, plane.itemsize, w, h, b.bank_x, b.bank_y, sx_, sy_, bd, ptr(mine), w)
@@ -1058,7 +1069,7 @@ def test_compound_prediction(orc, ref):
                 name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(b.subpel1_x != 0), int(b.subpel1_y != 0))] + "_c"
                 sp = C.c_void_p(ref1.ctypes.data + (b.src1_y * W + b.src1_x) * ref1.itemsize)
                 args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), b.subpel1_x, b.subpel1_y, C.byref(cp)]
-                if bd > 8: args.append(bd)
+                if hbd: args.append(bd)
                 getattr(ref, name)(*args)
             else:
                 if b.type == 2:
@@ -1069,7 +1080,7 @@ def test_compound_prediction(orc, ref):
                     mptr, mstride, sub = ptr(seg), w, 0
                 else:
                     mptr, mstride, sub = C.c_void_p(masks.ctypes.data + b.mask_off), b.mask_stride, int(b.mask_sub)
-                if bd == 8:
+                if not hbd:
                     ref.svt_aom_lowbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp))
                 else:
                     ref.svt_aom_highbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp), bd)
@@ -1107,8 +1118,10 @@ def test_warp_affine(orc, ref):
     including models that push the block outside the plane (edge clamping) and luma / 4:2:0 chroma sub-sampling."""
     rng = np.random.default_rng(66)
     W, H = 1024, 512
-    for bd, dt in ((8, np.uint8), (10, np.uint16), (12, np.uint16)):
+    for bd, dt in ((8, np.uint8), (10, np.uint16), (12, np.uint16), (8, np.uint16)):
         plane = rng.integers(0, 1 << bd, (H, W)).astype(dt)
+        if dt == np.uint16 and bd == 8:
+            plane[:256, :256] = 255; plane[:256, 256:512] = 0; plane[256:, :512] = rng.integers(0, 2, (H - 256, 512)) * 255
         n = 28
         blks = cmc.warp_blocks(rng, W, H, n)
         for ss in (0, 1):
@@ -1117,7 +1130,7 @@ def test_warp_affine(orc, ref):
                 a = np.zeros((h, w), dt); e = np.zeros((h, w), dt)
                 mat = (C.c_int32 * 8)(*list(b.mat), 0, 0)
                 cp = _ConvP(); cp.round_0 = 5 if bd == 12 else 3; cp.round_1 = 2 * 7 - cp.round_0
-                if bd == 8:
+                if dt == np.uint8:
                     ref.svt_av1_warp_affine_c(mat, ptr(plane), W, H, W, ptr(e), b.p_col, b.p_row, w, h, w, ss, ss, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)
                 else:
                     ref.svt_av1_highbd_warp_affine_c(mat, ptr(plane), W, H, W, ptr(e), b.p_col, b.p_row, w, h, w, ss, ss, bd, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)

@@ -12,6 +12,7 @@ import os
 from conftest import ROOT, ptr
 import txfm_common as tc
 import cdef_common as cc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 
@@ -553,27 +554,58 @@ def test_compound_warp_vs_reference_c(rtcd, ref):
     """The is_compound branches of svt_av1_warp_affine / svt_av1_highbd_warp_affine (Common/Codec/EbWarpedMotion.c:660-683, :812-835): first
     reference into the 16-bit compound buffer, second reference averaged (plain and distance-weighted) into pixels — same calls to the reference's
     `_c` function and to the wrapper."""
+    _compound_warp(rtcd, ref, 321, ((8, np.uint8), (10, np.uint16), (12, np.uint16)))
+
+
+@pytest.mark.parametrize("bd,fmt", [fc.U16_8])
+def test_compound_warp_vs_reference_c_fmt(rtcd, ref, bd, fmt):
+    """The same on 8-bit samples in 16-bit planes (the high-bit-depth function with bd 8, which reaches svt_hip_warp_compound_batch_dev with pix_bytes 2, bd 8) on
+    planes with all-max, all-0, checkerboard and binary regions; there the 8-bit functions on the same samples as uint8 planes must give the same compound buffer
+    and the same pixels, the reference's first, then the wrappers'."""
+    _compound_warp(rtcd, ref, 322, ((bd, fmt),))
+
+
+def _compound_warp(rtcd, ref, seed, fmts):
     import comp_common as cmc
-    rng = np.random.default_rng(321)
+    rng = np.random.default_rng(seed)
     W, H = 320, 200
-    for bd, dt in ((8, np.uint8), (10, np.uint16), (12, np.uint16)):
+
+    def run(fn, hbd, planes, dt, bd, geom, models, jnt, fwd, bck):
+        pw, ph, pc, pr, ss = geom
+        cbuf = np.full((ph, pw + 6), 0xABCD, np.uint16); pred = np.full((ph, pw + 4), 5, dt)
+        for second, (plane, (mat, a, b_, g, d)) in enumerate(zip(planes, models)):
+            cp = ConvParams(0, second, cbuf.ctypes.data, pw + 6, 5 if bd == 12 else 3, 7, 0, 1, jnt, fwd, bck, jnt)
+            m8 = (C.c_int32 * 8)(*mat, 0, 0)
+            args = (m8, _vp(plane), W, H, plane.shape[1], _vp(pred), pc, pr, pw, ph, pw + 4, ss, ss)
+            if hbd: fn(*args, bd, C.byref(cp), a, b_, g, d)
+            else: fn(*args, C.byref(cp), a, b_, g, d)
+            if second == 0: first = cbuf.copy()
+        return first, pred
+
+    for bd, dt in fmts:
+        wide = bd == 8 and dt == np.uint16
         plane0 = rng.integers(0, 1 << bd, (H, W + 8)).astype(dt); plane1 = rng.integers(0, 1 << bd, (H, W + 8)).astype(dt)
-        for it, (pw, ph, pc, pr, ss) in enumerate(((8, 8, 0, 0, 0), (32, 16, 64, 40, 0), (64, 64, 128, 96, 1), (16, 32, 296, 160, 0), (128, 128, 64, 32, 0))):
+        if wide:
+            yy, xx = np.mgrid[0:100, 0:160]
+            plane0[:100, :160] = 255; plane0[:100, 160:320] = 0; plane0[100:, :160] = ((yy + xx) & 1) * 255
+            plane1[:100, :160] = 255; plane1[:100, 160:320] = ((yy + xx) & 1) * 255; plane1[100:, 160:320] = rng.integers(0, 2, (100, 160)) * 255
+        lo, hi = 1 << 16, 0
+        for it, geom in enumerate(((8, 8, 0, 0, 0), (32, 16, 64, 40, 0), (64, 64, 128, 96, 1), (16, 32, 296, 160, 0), (128, 128, 64, 32, 0))):
+            pw = geom[0]
             for jnt, (fwd, bck) in ((0, (0, 0)), (1, (9, 7)), (1, (13, 3))):
-                m0 = cmc.warp_model(rng, extreme=(it == 3)); m1 = cmc.warp_model(rng)
-                res = []
-                for fns in ((ref.svt_av1_warp_affine_c, ref.svt_av1_highbd_warp_affine_c), (rtcd.svt_av1_warp_affine, rtcd.svt_av1_highbd_warp_affine)):
-                    cbuf = np.full((ph, pw + 6), 0xABCD, np.uint16); pred = np.full((ph, pw + 4), 5, dt)
-                    for second, (plane, (mat, a, b_, g, d)) in enumerate(((plane0, m0), (plane1, m1))):
-                        cp = ConvParams(0, second, cbuf.ctypes.data, pw + 6, 5 if bd == 12 else 3, 7, 0, 1, jnt, fwd, bck, jnt)
-                        m8 = (C.c_int32 * 8)(*mat, 0, 0)
-                        args = (m8, _vp(plane), W, H, plane.shape[1], _vp(pred), pc, pr, pw, ph, pw + 4, ss, ss)
-                        if bd == 8 and dt == np.uint8: fns[0](*args, C.byref(cp), a, b_, g, d)
-                        else: fns[1](*args, bd, C.byref(cp), a, b_, g, d)
-                        if second == 0: first = cbuf.copy()
-                    res.append((first, pred.copy()))
+                models = (cmc.warp_model(rng, extreme=(it == 3)), cmc.warp_model(rng))
+                hbd = dt == np.uint16
+                res = [run(fn, hbd, (plane0, plane1), dt, bd, geom, models, jnt, fwd, bck)
+                       for fn in ((ref.svt_av1_highbd_warp_affine_c, rtcd.svt_av1_highbd_warp_affine) if hbd else (ref.svt_av1_warp_affine_c, rtcd.svt_av1_warp_affine))]
                 assert np.array_equal(res[0][0], res[1][0]), ("compound buffer", bd, it, jnt)
                 assert np.array_equal(res[0][1], res[1][1]) and (res[0][1][:, :pw] != 5).any(), ("averaged prediction", bd, it, jnt, fwd)
+                if wide:
+                    planes8 = (plane0.astype(np.uint8), plane1.astype(np.uint8))
+                    res8 = [run(fn, False, planes8, np.uint8, 8, geom, models, jnt, fwd, bck) for fn in (ref.svt_av1_warp_affine_c, rtcd.svt_av1_warp_affine)]
+                    for k, who in enumerate(("reference", "wrapper")):
+                        assert np.array_equal(res[k][0], res8[k][0]) and np.array_equal(res[k][1], res8[k][1]), (who, "(2, 8) vs (1, 8)", it, jnt, fwd)
+                    lo, hi = min(lo, int(res[0][1][:, :pw].min())), max(hi, int(res[0][1][:, :pw].max()))
+        if wide: assert (lo, hi) == (0, 255), (lo, hi)
 
 
 def _as(T, fn):

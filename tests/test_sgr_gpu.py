@@ -9,20 +9,33 @@ import numpy as np
 import pytest
 
 from conftest import ptr
+import dlf_common as dc
+import fmt_common as fc
 
 pytestmark = pytest.mark.gpu
 EXT = 3
 
 
-def make_planes(w, h, bd, seed):
+def plant(dgd, mx):
+    """what a case of 8-bit samples in 16-bit planes (and its uint8 companion) carries: all max, all 0, a 0 / max checkerboard, binary 0 / max noise (in place)"""
+    yy, xx = np.mgrid[0:32, 0:32]
+    dgd[:16, :16] = mx; dgd[16:32, :16] = 0
+    dgd[:32, 16:48] = mx * ((yy + xx) & 1)
+    dgd[32:64, :32] = mx * np.random.default_rng(5).integers(0, 2, (32, 32))
+    dgd[-24:, -24:] = mx; dgd[-24:, -48:-24] = 0          # in the ragged last unit too
+
+
+def make_planes(w, h, bd, seed, dt=None, wide=False):
     rng = np.random.default_rng(seed)
-    dt = np.uint8 if bd == 8 else np.uint16
+    dt = dt or (np.uint8 if bd == 8 else np.uint16)
     yy, xx = np.mgrid[0:h, 0:w]
     base = (80 + 60 * np.sin(xx / 11.0) * np.cos(yy / 5.0) + 30 * (((xx // 7) + (yy // 9)) % 2)) * (1 << (bd - 8))
     src = np.clip(base, 0, (1 << bd) - 1)
     dgd = np.clip(src + rng.normal(0, 5 * (1 << (bd - 8)), (h, w)), 0, (1 << bd) - 1)
     dgd[:16, :16] = (1 << bd) - 1; dgd[16:32, :16] = 0
+    if wide: plant(dgd, (1 << bd) - 1)
     ext = np.ascontiguousarray(np.pad(dgd.astype(dt), EXT, mode="edge"))
+    if wide: fc.note_inputs(ext)
     return np.ascontiguousarray(src.astype(dt)), ext
 
 
@@ -30,10 +43,15 @@ def units(size, unit):
     return max((size + unit // 2) // unit, 1)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_filter_search_apply(hip, orc, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_filter_search_apply(hip, orc, bd, fmt):
+    fc.two_witnesses(_filter_search_apply, fmt, bd, hip, orc)
+
+
+def _filter_search_apply(hip, orc, bd, dt, wide):
     w, h, US = 200, 152, 64          # 3 x 2 restoration units, last ones larger / ragged
-    src, ext = make_planes(w, h, bd, 50 + bd)
+    src, ext = make_planes(w, h, bd, 50 + bd, dt, wide)
+    gots, exps = [], []
     st = ext.shape[1]
     off = (EXT * st + EXT) * ext.itemsize
     d_ext, d_src = hip.to_device(ext), hip.to_device(src)
@@ -52,19 +70,28 @@ def test_filter_search_apply(hip, orc, bd):
     for ep in range(16):
         f0, f1 = orc_filter(ep)
         hip.check(hip.L.svt_hip_sgr_filter_plane_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, w, h, ep, d_f0, d_f1, w), "filter")
-        if prm[ep][0] > 0: assert np.array_equal(hip.to_host(d_f0, (h, w), np.int32), f0), ("flt0", bd, ep)
-        if prm[ep][1] > 0: assert np.array_equal(hip.to_host(d_f1, (h, w), np.int32), f1), ("flt1", bd, ep)
+        g0, g1 = hip.to_host(d_f0, (h, w), np.int32), hip.to_host(d_f1, (h, w), np.int32)
+        if prm[ep][0] > 0: assert np.array_equal(g0, f0), ("flt0", bd, ep)
+        if prm[ep][1] > 0: assert np.array_equal(g1, f1), ("flt1", bd, ep)
+        if prm[ep][0] > 0: gots.append(g0); exps.append(f0)
+        if prm[ep][1] > 0: gots.append(g1); exps.append(f1)
     hip.free(d_ext, d_src, d_f0, d_f1)
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
 @pytest.mark.parametrize("ss", [0, 1])
-def test_search_and_stripe_apply(hip, orc, bd, ss):
+def test_search_and_stripe_apply(hip, orc, bd, fmt, ss):
     """Frame level: projection sums per restoration unit and the stripe-aware apply vs the oracle functions
     that tests/test_oracle_vs_ref.py pins to av1_foreach_rest_unit_in_frame / svt_av1_loop_restoration_filter_unit:
     unit rows offset by 8 >> ss_y, stripes of 64 >> ss_y rows seeing the deblocked picture across their boundaries."""
-    for (w, h, US) in ((200, 152, 64), (328, 264, 128)):
-        src, ext = make_planes(w, h, bd, 50 + bd + ss)
+    fc.two_witnesses(_search_and_stripe_apply, fmt, bd, hip, orc, ss)
+
+
+def _search_and_stripe_apply(hip, orc, ss, bd, dt, wide):
+    gots, exps = [], []
+    for (w, h, US) in ((200, 152, 64), (328, 264, 128))[:1 if wide else 2]:
+        src, ext = make_planes(w, h, bd, 50 + bd + ss, dt, wide)
         st = ext.shape[1]
         off = (EXT * st + EXT) * ext.itemsize
         rng = np.random.default_rng(3 + ss)
@@ -80,6 +107,7 @@ def test_search_and_stripe_apply(hip, orc, bd, ss):
             got = hip.to_host(d_sums, e_sums.shape, np.int64)
             hip.free(d_sums)
             assert np.array_equal(got, e_sums), (bd, ss, w, h, US, hex(mask), np.argwhere(got != e_sums)[:5])
+            gots.append(got); exps.append(e_sums)
         # --- apply: per-unit parameter set + xqd, one unit RESTORE_NONE; with and without stripe boundaries
         u_ep = rng.integers(0, 16, ux * uy).astype(np.uint8); u_ep[2] = 255
         u_xqd = np.stack([rng.integers(-96, 32, ux * uy), rng.integers(-32, 96, ux * uy)], 1).astype(np.int32)
@@ -108,15 +136,22 @@ def test_search_and_stripe_apply(hip, orc, bd, ss):
         assert np.array_equal(got2, exp2), (bd, ss, "no stripes", np.argwhere(got2 != exp2)[:5])
         assert (exp2 != exp).any(), "stripe boundaries must matter on this content"
         hip.free(d_ext, d_src, d_dbl, d_dst, d_ep, d_xqd)
+        gots += [got, got2]; exps += [exp, exp2]
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
 @pytest.mark.parametrize("ss", [0, 1])
-def test_mixed_wiener_sgr_apply(hip, orc, bd, ss):
+def test_mixed_wiener_sgr_apply(hip, orc, bd, fmt, ss):
     """svt_hip_lr_apply_plane_dev: a plane whose units are a mix of RESTORE_NONE / RESTORE_WIENER / RESTORE_SGRPROJ, stripe boundaries
     from the deblocked plane, vs orc_lr_apply_plane (pinned to svt_av1_loop_restoration_filter_unit incl. wiener_filter_stripe)."""
-    for (w, h, US) in ((200, 152, 64), (328, 264, 128)):
-        src, ext = make_planes(w, h, bd, 90 + bd + ss)
+    fc.two_witnesses(_mixed_wiener_sgr_apply, fmt, bd, hip, orc, ss)
+
+
+def _mixed_wiener_sgr_apply(hip, orc, ss, bd, dt, wide):
+    gots, exps = [], []
+    for (w, h, US) in ((200, 152, 64), (328, 264, 128))[:1 if wide else 2]:
+        src, ext = make_planes(w, h, bd, 90 + bd + ss, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         rng = np.random.default_rng(13 + ss)
         dbl = np.clip(ext[EXT:EXT + h, EXT:EXT + w].astype(np.int32) + rng.integers(-9, 10, (h, w)) * (1 << (bd - 8)), 0, (1 << bd) - 1).astype(ext.dtype)
@@ -136,10 +171,12 @@ def test_mixed_wiener_sgr_apply(hip, orc, bd, ss):
         hip.check(hip.L.svt_hip_lr_apply_plane_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_dst, w, w, h, US, ss, d_dbl, w, d_ep, d_xqd, d_wn), "lr apply")
         got = hip.to_host(d_dst, (h, w), ext.dtype)
         assert np.array_equal(got, exp), (bd, ss, w, h, US, np.argwhere(got != exp)[:5])
+        gots.append(got); exps.append(exp)
         # svt_hip_lr_try_unit_dev = try_restoration_unit_seg: ONE unit filtered (only its tiles are launched: the rest of the destination keeps the
         # marker) and its SSE against the source, for every unit of the plane incl. the over-sized last row / column
         d_src2, d_sse = hip.to_device(src), hip.to_device(np.zeros(1, np.uint64))
         voff = 8 >> ss; ux, uy = units(w, US), units(h, US)
+        rects, e_sse = [], []
         for u in range(nu):
             d_one = hip.to_device(np.full_like(exp, 7))
             hip.check(hip.L.svt_hip_lr_try_unit_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_one, w, w, h, US, ss, d_dbl, w, d_ep, d_xqd, d_wn, d_src2, w, u, d_sse), "try unit")
@@ -153,13 +190,25 @@ def test_mixed_wiener_sgr_apply(hip, orc, bd, ss):
             mask = np.ones((h, w), bool); mask[v0:v1, x0:x1] = False
             assert (one[mask] == 7).all(), ("try unit touched samples outside its unit", bd, ss, US, u)
             assert sse == int(((ref_rect - src_rect) ** 2).sum()), ("try unit sse", bd, ss, US, u)
+            gots += [one[v0:v1, x0:x1], np.int64(sse)]; exps += [exp[v0:v1, x0:x1], np.int64(((ref_rect - src_rect) ** 2).sum())]
+            rects.append((x0, v0, x0, v0, x1 - x0, v1 - v0)); e_sse.append(int(((ref_rect - src_rect) ** 2).sum()))
             hip.free(d_one)
+        # svt_hip_lr_try_units_dev, the list form: the whole plane filtered and the SSE of every unit's rectangle in one call, plus an empty-handed rectangle list
+        d_all, d_rects, d_sses = hip.to_device(np.full_like(exp, 7)), hip.to_device(dc.blk_pairs(rects)), hip.to_device(np.zeros(nu, np.uint64))
+        hip.check(hip.L.svt_hip_lr_try_units_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_all, w, w, h, US, ss, d_dbl, w, d_ep, d_xqd, d_wn, d_src2, w, d_rects, nu, d_sses), "try units")
+        all_, sses = hip.to_host(d_all, (h, w), ext.dtype), hip.to_host(d_sses, (nu,), np.uint64)
+        assert np.array_equal(all_, exp), ("try units pixels", bd, ss, US, np.argwhere(all_ != exp)[:4])
+        assert [int(v) for v in sses] == e_sse and sum(e_sse) > 0, ("try units sse", bd, ss, US)
+        assert hip.L.svt_hip_lr_try_units_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_all, w, w, h, US, ss, d_dbl, w, d_ep, d_xqd, d_wn, d_src2, w, None, nu, d_sses) != 0
+        gots += [all_, sses]; exps += [exp, np.array(e_sse, np.uint64)]
+        hip.free(d_all, d_rects, d_sses)
         hip.free(d_ext, d_dbl, d_ep, d_xqd, d_wn, d_dst, d_src2, d_sse)
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
 @pytest.mark.parametrize("ss", [0, 1])
-def test_wiener_walk_units(hip, bd, ss):
+def test_wiener_walk_units(hip, bd, fmt, ss):
     """svt_hip_wiener_walk_units_dev (finer_tile_search_wiener_seg of every unit on the device: the coordinate descent AND all of its probes in one launch) against the
     CPU test double's restatement of the same walk on the oracle's restoration filter (oracle/hip_mock.c): the same refined taps, the same error and the same number
     of probes for every unit; inactive units untouched; windows 7 / 5 / 3; unit sizes 64 / 128 with over-sized last rows and columns; starting filters from identity to
@@ -170,9 +219,14 @@ def test_wiener_walk_units(hip, bd, ss):
     M = C.CDLL(sc.MOCK_LIB)
     sig = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     M.svt_hip_wiener_walk_units_dev.argtypes = sig
-    for (w, h, US, win) in ((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3)):
+    fc.two_witnesses(_wiener_walk_units, fmt, bd, hip, M, ss)
+
+
+def _wiener_walk_units(hip, M, ss, bd, dt, wide):
+    gots, exps = [], []
+    for (w, h, US, win) in ((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3))[:1 if wide else 4]:
         if ss and win == 7: win = 5     # chroma planes search the 5-tap window at most (search_wiener_seg :1352-1358)
-        src, ext = make_planes(w, h, bd, 190 + bd + ss + US)
+        src, ext = make_planes(w, h, bd, 190 + bd + ss + US, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         rng = np.random.default_rng(31 + ss + win)
         dbl = np.clip(ext[EXT:EXT + h, EXT:EXT + w].astype(np.int32) + rng.integers(-9, 10, (h, w)) * (1 << (bd - 8)), 0, (1 << bd) - 1).astype(ext.dtype)
@@ -200,16 +254,23 @@ def test_wiener_walk_units(hip, bd, ss):
         assert np.array_equal(g_err[on], e_err[on]) and (g_err[~on] == -1).all(), (bd, ss, US, win)
         assert np.array_equal(g_pr[on], e_pr[on]) and e_pr[on].min() >= 7, (bd, ss, US, win, g_pr, e_pr)
         assert (e_wn[on] != wn[on]).any(), "no walk moved a tap: the content does not exercise the search"
+        gots += [g_wn, g_err[on], g_pr[on]]; exps += [e_wn, e_err[on], e_pr[on]]
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_wiener_walk_units_picture(hip, pkg, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_wiener_walk_units_picture(hip, pkg, bd, fmt):
     """svt_hip_wiener_walk_units_picture_dev: the walks of three planes (luma 7-tap, two chroma planes 5-tap, different sizes and unit counts) in one launch == the three
     per-plane launches (which test_wiener_walk_units pins to the reference's walk); a plane count outside 1..3 is refused."""
+    fc.two_witnesses(_wiener_walk_units_picture, fmt, bd, hip, pkg)
+
+
+def _wiener_walk_units_picture(hip, pkg, bd, dt, wide):
     rng = np.random.default_rng(77 + bd)
     planes, keep, exp = [], [], []
+    gots, exps = [], []
     for i, (w, h, US, ss, win) in enumerate(((328, 264, 128, 0, 7), (168, 136, 64, 1, 5), (200, 96, 64, 1, 5))):
-        src, ext = make_planes(w, h, bd, 500 + bd + i)
+        src, ext = make_planes(w, h, bd, 500 + bd + i, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         dbl = np.clip(ext[EXT:EXT + h, EXT:EXT + w].astype(np.int32) + rng.integers(-9, 10, (h, w)) * (1 << (bd - 8)), 0, (1 << bd) - 1).astype(ext.dtype)
         nu = units(w, US) * units(h, US)
@@ -231,11 +292,15 @@ def test_wiener_walk_units_picture(hip, pkg, bd):
         planes.append(pkg.WienerWalkPlane(d_ext.value + off, st, w, h, US, ss, d_dbl.value, w, d_src.value, w, d_wn.value, d_act.value, win, d_err.value, d_pr.value))
         keep.append((d_ext, d_dbl, d_src, d_act, d_wn, d_err, d_pr, wn.shape, nu))
     arr = (pkg.WienerWalkPlane * 3)(*planes)
-    hip.check(hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, 1 if bd == 8 else 2, bd, 3, arr), "wiener walk (picture)")
+    pb = np.dtype(dt).itemsize
+    hip.check(hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, pb, bd, 3, arr), "wiener walk (picture)")
     for (d_ext, d_dbl, d_src, d_act, d_wn, d_err, d_pr, shape, nu), (e_wn, e_err, e_pr) in zip(keep, exp):
-        assert np.array_equal(hip.to_host(d_wn, shape, np.int16), e_wn) and np.array_equal(hip.to_host(d_err, (nu,), np.int64), e_err) and np.array_equal(hip.to_host(d_pr, (nu,), np.uint32), e_pr)
-    assert hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, 1 if bd == 8 else 2, bd, 4, arr) != 0 and hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, 1 if bd == 8 else 2, bd, 0, arr) != 0
+        g = [hip.to_host(d_wn, shape, np.int16), hip.to_host(d_err, (nu,), np.int64), hip.to_host(d_pr, (nu,), np.uint32)]
+        assert np.array_equal(g[0], e_wn) and np.array_equal(g[1], e_err) and np.array_equal(g[2], e_pr)
+        gots += g; exps += [e_wn, e_err, e_pr]
+    assert hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, pb, bd, 4, arr) != 0 and hip.L.svt_hip_wiener_walk_units_picture_dev(hip.h, pb, bd, 0, arr) != 0
     for k in keep: hip.free(*k[:7])
+    return gots, exps
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -268,11 +333,11 @@ def test_search_extreme_content(hip, orc, bd):
         assert np.array_equal(got, e_sums), (bd, comp, np.argwhere(got != e_sums)[:5])
 
 
-def _smooth_noisy(w, h, bd, seed, sigma):
+def _smooth_noisy(w, h, bd, seed, sigma, dt=None, wide=False):
     """Source with textured regions; degraded picture = coarse quantisation of it (coding-like artefacts, strength per 64x64 region) plus noise
     in some regions: different parameter sets win and the projections land inside as well as on the clamps of the tap range."""
     rng = np.random.default_rng(seed)
-    dt = np.uint8 if bd == 8 else np.uint16
+    dt = dt or (np.uint8 if bd == 8 else np.uint16)
     sc = 1 << (bd - 8)
     yy, xx = np.mgrid[0:h, 0:w]
     clean = (100 + 60 * np.sin(xx / 9.0) * np.cos(yy / 7.0) + 25 * (((xx + yy) // 11) % 2) + 0.15 * xx) * sc
@@ -280,16 +345,24 @@ def _smooth_noisy(w, h, bd, seed, sigma):
     src = np.clip(clean + rng.normal(0, 1, (h, w)) * 6 * sc * (region == 1), 0, (1 << bd) - 1)
     q = np.array([2, 6, 12, 24])[region] * sc
     dgd = np.clip((src // q) * q + q // 2 + rng.normal(0, 1, (h, w)) * sigma * sc * (region == 3), 0, (1 << bd) - 1)
+    if wide:
+        plant(dgd, (1 << bd) - 1)
+        fc.note_inputs(dgd)
     return np.ascontiguousarray(src.astype(dt)), np.ascontiguousarray(np.pad(dgd.astype(dt), EXT, mode="edge"))
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
 @pytest.mark.parametrize("ss", [0, 1])
-def test_proj_error_candidates(hip, orc, bd, ss):
+def test_proj_error_candidates(hip, orc, bd, fmt, ss):
     """svt_hip_sgr_proj_error_plane_dev vs get_pixel_proj_error of the oracle (pinned to svt_av1_{lowbd,highbd}_pixel_proj_error): random and
     extreme xqd pairs per (unit, set), ragged units, all 16 sets and a sparse mask, ncand 1 / 5 / 12."""
+    fc.two_witnesses(_proj_error_candidates, fmt, bd, hip, orc, ss)
+
+
+def _proj_error_candidates(hip, orc, ss, bd, dt, wide):
     w, h, US = 200, 152, 64
-    src, ext = _smooth_noisy(w, h, bd, 300 + bd + ss, 4)
+    src, ext = _smooth_noisy(w, h, bd, 300 + bd + ss, 4, dt, wide)
+    gots, exps = [], []
     st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
     ux, uy = units(w, US), units(h, US); nu = ux * uy
     lim = np.zeros((nu, 4), np.int32); orc.orc_rest_unit_limits(w, h, ss, US, ptr(lim))
@@ -304,6 +377,7 @@ def test_proj_error_candidates(hip, orc, bd, ss):
         hip.check(hip.L.svt_hip_sgr_proj_error_plane_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_src, w, w, h, US, ss, mask, nc, d_xqd, d_err), "proj error")
         got = hip.to_host(d_err, (nu, 16, nc), np.int64)
         hip.free(d_xqd, d_err)
+        e_all = np.zeros_like(got)
         for u in range(nu):
             x0, x1, y0, y1 = [int(v) for v in lim[u]]; uw, uh = x1 - x0, y1 - y0
             fs = ((uw + 7) & ~7) + 8
@@ -322,16 +396,24 @@ def test_proj_error_candidates(hip, orc, bd, ss):
                     e = orc.orc_sgr_proj_error(C.c_void_p(src.ctypes.data + (y0 * w + x0) * src.itemsize), w, C.c_void_p(ext.ctypes.data + off + (y0 * st + x0) * ext.itemsize), st,
                                                ext.itemsize, uw, uh, ptr(f0), fs, ptr(f1), fs, xq, ep)
                     assert got[u, ep, k] == e, (bd, ss, hex(mask), u, ep, k)
+                    e_all[u, ep, k] = e
+        gots.append(got); exps.append(e_all)
     assert hip.L.svt_hip_sgr_proj_error_plane_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_src, w, w, h, US, ss, 1, 25, d_ext, d_ext) != 0
     hip.free(d_ext, d_src)
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_search_units_plane(hip, orc, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_search_units_plane(hip, orc, bd, fmt):
     """svt_hip_sgr_search_units_plane (sums -> solve -> encode_xq -> finer search, all on the device) vs the oracle's search_selfguided_restoration
     restatement (pinned to the reference's static functions through oracle/ref_shim_restpick.c): xqd, error and best set of every unit."""
-    for (w, h, US, ss, mask, sigma) in ((264, 200, 64, 0, 0xFFFF, 5), (168, 120, 64, 1, 0xFFFF, 9), (328, 264, 128, 0, 0x0F38, 3), (1000, 584, 256, 0, 0x4221, 4)):
-        src, ext = _smooth_noisy(w, h, bd, 400 + bd + ss, sigma)
+    fc.two_witnesses(_search_units_plane, fmt, bd, hip, orc)
+
+
+def _search_units_plane(hip, orc, bd, dt, wide):
+    gots, exps = [], []
+    for (w, h, US, ss, mask, sigma) in ((264, 200, 64, 0, 0xFFFF, 5), (168, 120, 64, 1, 0xFFFF, 9), (328, 264, 128, 0, 0x0F38, 3), (1000, 584, 256, 0, 0x4221, 4))[:1 if wide else 4]:
+        src, ext = _smooth_noisy(w, h, bd, 400 + bd + ss, sigma, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         nu = units(w, US) * units(h, US)
         e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
@@ -345,6 +427,8 @@ def test_search_units_plane(hip, orc, bd):
         assert np.array_equal(g_xqd, e_xqd) and np.array_equal(g_best, e_best)
         assert rounds.value == 0   # no host rounds: the whole search runs on the device
         if mask == 0xFFFF: assert len(set(int(v) for v in e_best)) > 1, "content should make different sets win"
+        gots += [g_xqd, g_err, g_best]; exps += [e_xqd, e_err, e_best]
+    return gots, exps
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -378,36 +462,49 @@ def test_search_units_largest_unit_extreme_content(hip, orc, bd):
         assert np.array_equal(g_xqd, e_xqd) and np.array_equal(g_best, e_best), (bd, kind)
 
 
-def test_search_units_picture(hip, pkg, orc):
-    """Three planes in one call (svt_hip_sgr_search_units_picture) = the per-plane results."""
-    w, h, bd = 264, 200, 8
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_search_units_picture(hip, pkg, orc, bd, fmt):
+    """Three planes in one call (svt_hip_sgr_search_units_picture: its own scratch, results copied back to the host per set mask) = the per-plane results."""
+    fc.two_witnesses(_search_units_picture, fmt, bd, hip, pkg, orc)
+
+
+def _search_units_picture(hip, pkg, orc, bd, dt, wide):
+    w, h = 264, 200
+    pb = np.dtype(dt).itemsize
     planes, keep, exp = (pkg.SgrSearchPlane * 3)(), [], []
     for p in range(3):
         ss = int(p > 0); pw, ph = w >> ss, h >> ss
-        src, ext = _smooth_noisy(pw, ph, bd, 700 + p, 5)
-        st = ext.shape[1]; off = (EXT * st + EXT)
+        src, ext = _smooth_noisy(pw, ph, bd, 700 + p, 5, dt, wide)
+        st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         nu = units(pw, 64) * units(ph, 64)
         mask = (0xFFFF, 0x03C0, 0x8001)[p]
         e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
-        orc.orc_sgr_search_units_plane(C.c_void_p(ext.ctypes.data + off), 1, st, ptr(src), pw, pw, ph, ss, ss, 64, bd, mask, ptr(e_xqd), ptr(e_err), ptr(e_best))
+        orc.orc_sgr_search_units_plane(C.c_void_p(ext.ctypes.data + off), pb, st, ptr(src), pw, pw, ph, ss, ss, 64, bd, mask, ptr(e_xqd), ptr(e_err), ptr(e_best))
         d_ext, d_src = hip.to_device(ext), hip.to_device(src)
         g = (np.zeros_like(e_xqd), np.zeros_like(e_err), np.zeros_like(e_best))
         planes[p] = pkg.SgrSearchPlane(d_ext.value + off, st, d_src.value, pw, pw, ph, 64, ss, mask, g[0].ctypes.data, g[1].ctypes.data, g[2].ctypes.data)
         keep += [d_ext, d_src]; exp.append(((e_xqd, e_err, e_best), g))
     rounds = C.c_int(0)
-    hip.check(hip.L.svt_hip_sgr_search_units_picture(hip.h, 1, bd, 3, planes, C.byref(rounds)), "picture search")
+    hip.check(hip.L.svt_hip_sgr_search_units_picture(hip.h, pb, bd, 3, planes, C.byref(rounds)), "picture search")
+    gots, exps = [], []
     for p, (e, g) in enumerate(exp):
-        assert np.array_equal(g[1], e[1]) and np.array_equal(g[0], e[0]) and np.array_equal(g[2], e[2]), p
-    assert hip.L.svt_hip_sgr_search_units_picture(hip.h, 1, bd, 4, planes, None) != 0
+        assert np.array_equal(g[1], e[1]) and np.array_equal(g[0], e[0]) and np.array_equal(g[2], e[2]), (bd, pb, p)
+        gots += list(g); exps += list(e)
+    assert hip.L.svt_hip_sgr_search_units_picture(hip.h, pb, bd, 4, planes, None) != 0
     hip.free(*keep)
+    return gots, exps
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_search_units_plane_dev_chain(hip, orc, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_search_units_plane_dev_chain(hip, orc, bd, fmt):
     """The device-output form: results stay in HBM, d_best_ep / d_best_xqd are exactly the per-unit arrays svt_hip_sgr_apply_plane_dev takes, so the
     search -> trial filter chain needs no host round trip.  Checked: every (unit, set) result, the best set, and the plane filtered with the winners."""
+    fc.two_witnesses(_search_units_plane_dev_chain, fmt, bd, hip, orc)
+
+
+def _search_units_plane_dev_chain(hip, orc, bd, dt, wide):
     w, h, US, ss, mask = 328, 264, 128, 0, 0xFFFF
-    src, ext = _smooth_noisy(w, h, bd, 900 + bd, 6)
+    src, ext = _smooth_noisy(w, h, bd, 900 + bd, 6, dt, wide)
     st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
     nu = units(w, US) * units(h, US)
     e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
@@ -433,6 +530,7 @@ def test_search_units_plane_dev_chain(hip, orc, bd):
     # a scratch that is too small is rejected
     assert L.svt_hip_sgr_search_units_plane_dev(hip.h, ext.itemsize, bd, d_ext.value + off, st, d_src, w, w, h, US, ss, mask, d_xqd, d_err, d_best, d_bx, d_scr, nbytes - 1) != 0
     hip.free(d_ext, d_src, d_scr, d_xqd, d_err, d_best, d_bx, d_out)
+    return [g_xqd, g_err, g_best, g_bx, out], [e_xqd, e_err, e_best, e_xqd[np.arange(nu), e_best], exp]
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -517,17 +615,22 @@ def test_search_units_packed_words_and_escape_lists(hip, orc, lim, ss):
     if lim is not None: assert listed["packed"] > (w * h if lim == 3 else 1000), listed   # lim 3: most samples of most two-filter sets are listed
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_search_units_picture_dev(hip, pkg, orc, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_search_units_picture_dev(hip, pkg, orc, bd, fmt):
     """svt_hip_sgr_search_units_picture_dev: three planes of different sizes / unit sizes / set masks in one call (one walk launch for the picture:
     grid.z = plane, a plane with fewer units than the widest one leaves workgroups without work) against the oracle's per-plane search."""
+    fc.two_witnesses(_search_units_picture_dev, fmt, bd, hip, pkg, orc)
+
+
+def _search_units_picture_dev(hip, pkg, orc, bd, dt, wide):
     planes = [(328, 264, 128, 0, 0xFFFF), (168, 136, 64, 1, 0x0F3C), (200, 96, 64, 1, 0x8001)]
+    gots, exps = [], []
     L = hip.L
     L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     jobs = (pkg.SgrUnitsPlaneDev * 3)()
     keep, expect = [], []
     for i, (w, h, US, ss, mask) in enumerate(planes):
-        src, ext = _smooth_noisy(w, h, bd, 1500 + 10 * i + bd, 5 + i)
+        src, ext = _smooth_noisy(w, h, bd, 1500 + 10 * i + bd, 5 + i, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
         nu = units(w, US) * units(h, US)
         e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
@@ -538,12 +641,14 @@ def test_search_units_picture_dev(hip, pkg, orc, bd):
         keep.append(d); expect.append((nu, mask, e_xqd, e_err, e_best))
         jobs[i] = pkg.SgrUnitsPlaneDev(d["ext"].value + off, st, d["src"].value, w, w, h, US, ss, mask, d["xqd"].value, d["err"].value, d["best"].value, d["bx"].value,
                                        d["scr"].value, nbytes)
-    hip.check(L.svt_hip_sgr_search_units_picture_dev(hip.h, 1 if bd == 8 else 2, bd, 3, jobs), "units picture dev")
+    hip.check(L.svt_hip_sgr_search_units_picture_dev(hip.h, np.dtype(dt).itemsize, bd, 3, jobs), "units picture dev")
     for d, (nu, mask, e_xqd, e_err, e_best) in zip(keep, expect):
         g_xqd = hip.to_host(d["xqd"], e_xqd.shape, np.int32); g_err = hip.to_host(d["err"], e_err.shape, np.int64); g_best = hip.to_host(d["best"], e_best.shape, np.uint8)
         on = np.array([(mask >> e) & 1 for e in range(16)], bool)
         assert np.array_equal(g_err[:, on], e_err[:, on]) and np.array_equal(g_xqd[:, on], e_xqd[:, on]) and np.array_equal(g_best, e_best), (bd, nu, hex(mask))
         hip.free(*d.values())
+        gots += [g_err[:, on], g_xqd[:, on], g_best]; exps += [e_err[:, on], e_xqd[:, on], e_best]
+    return gots, exps
 
 
 @pytest.mark.parametrize("n_pics", [2, 4])

@@ -11,6 +11,7 @@ import pytest
 
 from conftest import ptr
 import txfm_common as tc
+import fmt_common as fc
 from test_oracle_golden import T, V, golden_scan, golden_cases
 
 pytestmark = pytest.mark.gpu
@@ -80,47 +81,74 @@ def oracle_block(orc, ts, tt, bd, src, pred, x, y, qp, variant, scan, shape=0):
     return co, en, q, dq, eob, cul
 
 
+def plant(src, pred, mx):
+    """what a case of 8-bit samples in 16-bit planes (and its uint8 companion) carries in the 64 x 64 cells below the two +-max ones: source = prediction = all max,
+    = all 0 (zero residual: the reconstruction is exactly max / 0), and a 0 / max checkerboard against its complement (residual +-max sample by sample: the inverse
+    overshoots both ends and the clip decides).  -> the cells' origins"""
+    yy, xx = np.mgrid[0:64, 0:64]
+    src[64:128, 0:64] = mx; pred[64:128, 0:64] = mx
+    src[64:128, 64:128] = 0; pred[64:128, 64:128] = 0
+    src[128:192, 0:64] = ((yy + xx) & 1) * mx; pred[128:192, 0:64] = (1 - ((yy + xx) & 1)) * mx
+    return [(0, 64), (64, 64), (0, 128)]
+
+
 @pytest.mark.parametrize("ts", range(19))
 def test_fwd_quant_inv_all_types(hip, pkg, orc, ts):
-    w, h = tc.TXW[ts], tc.TXH[ts]
     rng = np.random.default_rng(100 + ts)
     for bd in (8, 10):
-        dt = np.uint8 if bd == 8 else np.uint16
-        types = tc.legal_types(ts)
-        PW, PH = 4 * 64 + 8, 3 * 64  # plane with an odd-ish stride
-        src = rng.integers(0, 1 << bd, (PH, PW)).astype(dt)
-        pred = rng.integers(0, 1 << bd, (PH, PW)).astype(dt)
-        src[0:64, 0:64] = (1 << bd) - 1; pred[0:64, 0:64] = 0           # residual = +max
-        src[0:64, 64:128] = 0; pred[0:64, 64:128] = (1 << bd) - 1       # residual = -max
-        pos = [(x, y) for y in range(0, PH - h + 1, h) for x in range(0, 256 - w + 1, w)]
-        rng.shuffle(pos)
-        pos = [(0, 0), (64, 0)] + pos[:min(len(pos), 70)]
-        descs, tts = [], []
+        _fwd_quant_inv(hip, pkg, orc, ts, rng, bd, fc.dtype_of(bd), False)
+
+
+@pytest.mark.parametrize("ts", [pytest.param(ts, id=f"u16-8-{ts}") for ts in range(19)])
+def test_fwd_quant_inv_all_types_u16_8(hip, pkg, orc, ts):
+    """the same case on 8-bit samples in 16-bit planes (the forward entry takes pix_bytes 2 on 8-bit residuals, the inverse pix_bytes 2 with bd 8): the oracle, and the uint8 run widened"""
+    fc.two_witnesses(_fwd_quant_inv, np.uint16, 8, hip, pkg, orc, ts, None)
+
+
+def _fwd_quant_inv(hip, pkg, orc, ts, rng, bd, dt, wide):
+    w, h = tc.TXW[ts], tc.TXH[ts]
+    gots, exps = [], []
+    if wide: rng = np.random.default_rng(300 + ts)
+    types = tc.legal_types(ts)
+    PW, PH = 4 * 64 + 8, 3 * 64  # plane with an odd-ish stride
+    src = rng.integers(0, 1 << bd, (PH, PW)).astype(dt)
+    pred = rng.integers(0, 1 << bd, (PH, PW)).astype(dt)
+    src[0:64, 0:64] = (1 << bd) - 1; pred[0:64, 0:64] = 0           # residual = +max
+    src[0:64, 64:128] = 0; pred[0:64, 64:128] = (1 << bd) - 1       # residual = -max
+    pos = [(x, y) for y in range(0, PH - h + 1, h) for x in range(0, 256 - w + 1, w)]
+    rng.shuffle(pos)
+    pos = [(0, 0), (64, 0)] + pos[:min(len(pos), 70)]
+    if wide: pos = plant(src, pred, (1 << bd) - 1) + pos[:40]
+    descs, tts = [], []
+    for i, (x, y) in enumerate(pos):
+        tt = types[i % len(types)]
+        descs.append(pkg.tx_desc(x, y, tt)); tts.append(tt)
+    for qi, variant in ((60, 0 if bd == 8 else 1), (200, 2 if bd == 8 else 3), (20, 0 if bd == 8 else 1)):
+        qp = np.ascontiguousarray(T[f"qp/{bd}/{qi}/{qi % 3}"])
+        g = run_fwd(hip, pkg, ts, bd, src, pred, descs, qp, variant)
+        for i, ((x, y), tt) in enumerate(zip(pos, tts)):
+            scan, _ = golden_scan(ts, tt)
+            co, en, q, dq, eob, cul = oracle_block(orc, ts, tt, bd, src, pred, x, y, qp, variant, scan)
+            assert np.array_equal(g["coeff"][i], co), ("coeff", ts, tt, bd, i)
+            assert int(g["energy"][i]) == en, ("energy", ts, tt, bd)
+            assert np.array_equal(g["q"][i], q) and np.array_equal(g["dq"][i], dq), ("quant", ts, tt, bd, qi, variant)
+            assert int(g["eob"][i]) == eob and int(g["cul"][i]) == cul, ("eob/cul", ts, tt, bd, qi, variant)
+            gots += [g["coeff"][i], g["q"][i], g["dq"][i], np.int64([int(g["energy"][i]), int(g["eob"][i]), int(g["cul"][i])])]
+            exps += [co, q, dq, np.int64([en, eob, cul])]
+        # inverse on the GPU's own dequantized coefficients, non-overlapping blocks only
+        seen, keep = set(), []
         for i, (x, y) in enumerate(pos):
-            tt = types[i % len(types)]
-            descs.append(pkg.tx_desc(x, y, tt)); tts.append(tt)
-        for qi, variant in ((60, 0 if bd == 8 else 1), (200, 2 if bd == 8 else 3), (20, 0 if bd == 8 else 1)):
-            qp = np.ascontiguousarray(T[f"qp/{bd}/{qi}/{qi % 3}"])
-            g = run_fwd(hip, pkg, ts, bd, src, pred, descs, qp, variant)
-            for i, ((x, y), tt) in enumerate(zip(pos, tts)):
-                scan, _ = golden_scan(ts, tt)
-                co, en, q, dq, eob, cul = oracle_block(orc, ts, tt, bd, src, pred, x, y, qp, variant, scan)
-                assert np.array_equal(g["coeff"][i], co), ("coeff", ts, tt, bd, i)
-                assert int(g["energy"][i]) == en, ("energy", ts, tt, bd)
-                assert np.array_equal(g["q"][i], q) and np.array_equal(g["dq"][i], dq), ("quant", ts, tt, bd, qi, variant)
-                assert int(g["eob"][i]) == eob and int(g["cul"][i]) == cul, ("eob/cul", ts, tt, bd, qi, variant)
-            # inverse on the GPU's own dequantized coefficients, non-overlapping blocks only
-            seen, keep = set(), []
-            for i, (x, y) in enumerate(pos):
-                if (x, y) not in seen:
-                    seen.add((x, y)); keep.append(i)
-            rec = run_inv(hip, ts, bd, np.ascontiguousarray(g["dq"][keep]), pred, [descs[i] for i in keep])
-            p16 = pred.astype(np.uint16)
-            for i in keep:
-                x, y = pos[i]
-                exp = np.zeros((h, w), np.uint16)
-                orc.orc_inv_txfm2d_add(ptr(np.ascontiguousarray(g["dq"][i])), ptr(np.ascontiguousarray(p16[y:y + h, x:x + w])), w, ptr(exp), w, tts[i], ts, bd)
-                assert np.array_equal(rec[y:y + h, x:x + w].astype(np.uint16), exp), ("inv", ts, tts[i], bd, qi)
+            if (x, y) not in seen:
+                seen.add((x, y)); keep.append(i)
+        rec = run_inv(hip, ts, bd, np.ascontiguousarray(g["dq"][keep]), pred, [descs[i] for i in keep])
+        p16 = pred.astype(np.uint16)
+        for i in keep:
+            x, y = pos[i]
+            exp = np.zeros((h, w), np.uint16)
+            orc.orc_inv_txfm2d_add(ptr(np.ascontiguousarray(g["dq"][i])), ptr(np.ascontiguousarray(p16[y:y + h, x:x + w])), w, ptr(exp), w, tts[i], ts, bd)
+            assert np.array_equal(rec[y:y + h, x:x + w].astype(np.uint16), exp), ("inv", ts, tts[i], bd, qi)
+            gots.append(rec[y:y + h, x:x + w]); exps.append(exp if dt == np.uint16 else exp.astype(np.uint8))
+    return gots, exps
 
 
 def test_golden_vectors(hip, pkg):
@@ -155,15 +183,26 @@ def test_golden_vectors(hip, pkg):
             assert np.array_equal(rec[:, i * w:(i + 1) * w].astype(np.uint16), V[f"{ts}/{tt}/{bd}/rec"]), (ts, tt, bd)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
-def test_mixed_size_launches(hip, pkg, bd):
+@pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
+def test_mixed_size_launches(hip, pkg, bd, fmt):
     """svt_hip_fwd_txfm_quant_multi_dev / svt_hip_inv_txfm_add_multi_dev: all 19 sizes as 19 jobs of one call (two launches of <= 16
     jobs) must reproduce the single-size entry points bit for bit (those are checked against the oracle above), including ragged
     last workgroups and an empty job."""
+    fc.two_witnesses(_mixed_size_launches, fmt, bd, hip, pkg)
+
+
+def _mixed_size_launches(hip, pkg, bd, dt, wide):
+    """-> (results of the mixed-size entry points, results of the single-size entry points)"""
     rng = np.random.default_rng(70 + bd)
-    dt = np.uint8 if bd == 8 else np.uint16
     Wp, Hp = 1024, 512
     src = rng.integers(0, 1 << bd, (Hp, Wp)).astype(dt); pred = rng.integers(0, 1 << bd, (Hp, Wp)).astype(dt)
+    if wide:        # every size's row of blocks starts on these columns: all max / all 0 with a zero residual, +-max residuals, a checkerboard against its complement
+        mx = (1 << bd) - 1
+        yy, xx = np.mgrid[0:Hp, 0:64]
+        src[:, 0:64] = mx; pred[:, 0:64] = mx; src[:, 64:128] = 0; pred[:, 64:128] = 0
+        src[:, 128:192] = mx; pred[:, 128:192] = 0; src[:, 192:256] = 0; pred[:, 192:256] = mx
+        src[:, 256:320] = ((yy + xx) & 1) * mx; pred[:, 256:320] = (1 - ((yy + xx) & 1)) * mx
+    gots, exps = [], []
     qp = T[f"qp/{bd}/60/0"]
     variant = 0 if bd == 8 else 1
     d_src, d_pred = hip.to_device(src), hip.to_device(pred)
@@ -203,10 +242,13 @@ def test_mixed_size_launches(hip, pkg, bd):
         assert np.array_equal(hip.to_host(o["eob"], (n,), np.uint16), exp["eob"]), ("eob", ts)
         assert np.array_equal(hip.to_host(o["cul"], (n,), np.int32), exp["cul"]), ("cul", ts)
         assert np.array_equal(hip.to_host(o["en"], (n,), np.uint64), exp["energy"]), ("energy", ts)
+        gots += [hip.to_host(o[k], exp[e].shape, exp[e].dtype) for k, e in (("co", "coeff"), ("q", "q"), ("dq", "dq"), ("eob", "eob"), ("cul", "cul"), ("en", "energy"))]
+        exps += [exp[e] for e in ("coeff", "q", "dq", "eob", "cul", "energy")]
         w, h = tc.TXW[ts], tc.TXH[ts]
         for d in descs:
             x, y = int(d & 0x3FFF), int((d >> 14) & 0x3FFF)
             assert np.array_equal(rec[y:y + h, x:x + w], exp["rec"][y:y + h, x:x + w]), ("rec", ts)
+            gots.append(rec[y:y + h, x:x + w]); exps.append(exp["rec"][y:y + h, x:x + w])
     # svt_hip_enc_txfm_multi_dev: the same jobs with the reconstruction fused in (dequantised coefficients stay in registers) — identical
     # levels, eobs and reconstruction, with the dq output (pass 0) and without it (pass 1)
     for drop_dq in (0, 1):
@@ -234,8 +276,10 @@ def test_mixed_size_launches(hip, pkg, bd):
             for d in descs:
                 x, y = int(d & 0x3FFF), int((d >> 14) & 0x3FFF)
                 assert np.array_equal(rec_f[y:y + h, x:x + w], exp["rec"][y:y + h, x:x + w]), ("fused rec", ts, drop_dq)
+                gots.append(rec_f[y:y + h, x:x + w]); exps.append(exp["rec"][y:y + h, x:x + w])
         hip.free(d_rec_f, *[v for _, o in outs2 for v in o.values()])
     hip.free(d_src, d_pred, d_rec_multi, *keep, *[v for o in outs for v in o.values()])
+    return gots, exps
 
 
 @pytest.mark.parametrize("shape", [1, 2, 3])

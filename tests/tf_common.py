@@ -35,9 +35,18 @@ def make_blocks(rng, n, bd, big_mv=False, err_max=60):
     return b
 
 
-def make_pictures(rng, w, h, bd, ss_x, ss_y, n_refs, noise=6.0):
-    """Central picture + n_refs 'motion compensated' pictures (central + noise of varying strength, a few saturated / flat regions)."""
-    dt = np.uint8 if bd == 8 else np.uint16
+def plant(plane, mx):
+    """all max, all 0, a 0 / max checkerboard and binary 0 / max noise in the top left 64 x 64 block of a plane (in place): what the cases of 8-bit samples in 16-bit
+    planes carry"""
+    yy, xx = np.mgrid[0:32, 0:32]
+    plane[:32, :16] = mx; plane[:32, 16:32] = 0; plane[:32, 32:64] = mx * ((yy + xx) & 1)
+    plane[32:64, :32] = mx * np.random.default_rng(9).integers(0, 2, (32, 32))
+
+
+def make_pictures(rng, w, h, bd, ss_x, ss_y, n_refs, noise=6.0, dtype=None, wide=False):
+    """Central picture + n_refs 'motion compensated' pictures (central + noise of varying strength, a few saturated / flat regions).
+    dtype: sample type (default uint8 at bd 8, uint16 above); wide: plant() in the central luma plane and, out of step, in every second predictor."""
+    dt = dtype or (np.uint8 if bd == 8 else np.uint16)
     mx = (1 << bd) - 1
     yy, xx = np.mgrid[0:h, 0:w]
     base = (110 + 70 * np.sin(xx / 23.0) * np.cos(yy / 17.0) + 25 * (((xx // 16) + (yy // 16)) % 2)) * (1 << (bd - 8))
@@ -49,7 +58,9 @@ def make_pictures(rng, w, h, bd, ss_x, ss_y, n_refs, noise=6.0):
         sg = noise * (0.3 + f) * (1 << (bd - 8))
         pr = [np.ascontiguousarray(np.clip(s.astype(np.float64) + rng.normal(0, sg, s.shape), 0, mx).astype(dt)) for s in src]
         if f == 0: pr[0][:32, :32] = 0                     # maximum squared differences in one 32x32 block
+        if wide and f % 2: plant(pr[0][8:, 8:], mx)
         preds.append(pr)
+    if wide: plant(src[0], mx)
     return src, preds
 
 
@@ -64,10 +75,10 @@ def mv_word(mx, my):
     return ((np.asarray(my, np.int64) * 4 & 0xffff) << 16 | (np.asarray(mx, np.int64) * 4 & 0xffff)).astype(np.uint32)
 
 
-def make_subpel_case(rng, w, h, bd, pad, max_mv=9, noise=3.0, edge_mv=True):
+def make_subpel_case(rng, w, h, bd, pad, max_mv=9, noise=3.0, edge_mv=True, dtype=None, wide=False):
     """A central picture and a padded reference picture (the central one shifted by a smooth sub-pel field + noise), 4:2:0, and one job per 64x64 block
     whose integer vectors point near the true motion; blocks on the picture border get vectors that push the clamp of clamp_mv_to_umv_border_sb."""
-    dt = np.uint8 if bd == 8 else np.uint16
+    dt = dtype or (np.uint8 if bd == 8 else np.uint16)
     mx = (1 << bd) - 1
     sc = 1 << (bd - 8)
 
@@ -83,6 +94,8 @@ def make_subpel_case(rng, w, h, bd, pad, max_mv=9, noise=3.0, edge_mv=True):
         src.append(np.ascontiguousarray(np.clip(tex(hh, ww, 0, 0, p) + rng.normal(0, noise * sc, (hh, ww)), 0, mx).astype(dt)))
         full = np.clip(tex(hh + 2 * pd, ww + 2 * pd, -pd + 2.3 / (1 + s), -pd - 1.6 / (1 + s), p) + rng.normal(0, noise * sc, (hh + 2 * pd, ww + 2 * pd)), 0, mx).astype(dt)
         ref.append(np.ascontiguousarray(full))
+    if wide:      # interior blocks (border vectors are pushed to the clamp): the interpolation overshoots the range on the binary regions
+        plant(src[0][64:, 64:], mx); plant(ref[0][pad + 64 + 2:, pad + 64 - 3:], mx)
     bc, br = w // 64, h // 64
     jobs = np.zeros(bc * br, SUBPEL_DTYPE)
     for r in range(br):
