@@ -1103,7 +1103,8 @@ int svt_hip_tpl_set_phases(SvtHipCtx *ctx, int mask);
  * Planes: d_* points at sample (0, 0), any stride >= width, any base offset; width and height >= 8, not necessarily multiples of 8; nothing outside
  * [0, width) x [0, height) of a plane is read (the warp clamps to the reference plane's edges as the reference does).  The source is w x h; a reference
  * plane has its own width / height / stride (they bound the clamp; the error is always summed over the source's w x h).
- * Corner detection, correspondences, RANSAC, gm_get_params_cost / svt_av1_is_enough_erroradvantage and the high-bit-depth twins stay on the host. */
+ * Corner detection and the correspondence search have device forms too (the svt_hip_gm_corners / cross_correlation / correspondences entry points below); RANSAC,
+ * gm_get_params_cost / svt_av1_is_enough_erroradvantage and the high-bit-depth twins stay on the host. */
 typedef struct {
     int32_t mat[6];                     /* EbWarpedMotionParams::wmmat[0..5] as svt_warp_plane uses them */
     int16_t alpha, beta, gamma, delta;  /* its shear parameters */
@@ -1134,6 +1135,7 @@ typedef struct {
 #define SVT_HIP_GM_MAX_DIM 16384
 #define SVT_HIP_GM_MAX_MODELS (1 << 20)
 #define SVT_HIP_GM_MAX_JOBS 1024
+#define SVT_HIP_GM_MAX_CORNERS 4096
 
 /* svt_get_shear_params (Common/Codec/EbWarpedMotion.c:921-950, with is_affine_valid :359, is_affine_shear_allowed :364 and the divisor of :343-357) of n
  * models: d_wmmat = n x int32[6]; d_out[i] = {the six parameters, alpha .. delta after the 6-bit reduction, valid}.  alpha .. delta are 0 when wmmat[2] <= 0
@@ -1155,6 +1157,32 @@ int svt_hip_gm_refine_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_
                                   const SvtHipGmJob *d_jobs, int njobs, SvtHipGmResult *d_results, void *d_scratch, int *polls_out);
 /* The error table the three kernels use, min(16384, floor(16384 (|i - 255| / 255)^0.7 + 0.5)), i = 0..511 (host; needs no device). */
 int svt_hip_gm_error_table(uint16_t out[512]);
+
+/* The front half of compute_global_motion_feature_based (Encoder/Codec/global_motion.c:274-320): corners and correspondences, bit for bit; RANSAC takes the
+ * correspondence list on the host.  Lists and counts live in device memory: the kernels clamp a count to [0, max_points] and pass every coordinate, any int,
+ * through the reference's eligibility tests before it becomes an address.
+ *
+ * svt_av1_fast_corner_detect (Encoder/Codec/corner_detect.c:19-32: FAST-9 at barrier 18, third_party/fastfeat/fast_9.c, the score of :8-2937, the non-maximum
+ * suppression of nonmax.c:8-119) of n_planes <= 1 + SVT_HIP_GM_MAX_REFS planes, each of its own size, in one call.  planes is a host array.
+ * d_points[p][max_points][2] = x, y of the first max_points kept corners of plane p in raster order (the reference's truncation); d_counts[p] = min(kept,
+ * max_points); d_kept[p] (may be NULL) = kept before the truncation.  d_scratch holds svt_hip_gm_corners_scratch_bytes(planes, n_planes) bytes (0 = the planes
+ * would be refused), 8-byte aligned. */
+size_t svt_hip_gm_corners_scratch_bytes(const SvtHipGmRef *planes, int n_planes);
+int svt_hip_gm_corners_batch_dev(SvtHipCtx *ctx, const SvtHipGmRef *planes, int n_planes, int max_points, int32_t *d_points, int32_t *d_counts, int32_t *d_kept,
+                                 void *d_scratch);
+/* svt_av1_compute_cross_correlation_c (Encoder/Codec/corner_match.c:43-64) of n point pairs: d_pairs[i] = x1, y1, x2, y2; d_out[i] = cov / sqrt(var2) of the 13x13
+ * windows centred there, the reference's double (NaN where window 2 is flat).  Both planes are w x h.  A pair either of whose windows does not lie inside
+ * (6 <= x < w - 6, 6 <= y < h - 6) is not read and gets 0.0. */
+int svt_hip_gm_cross_correlation_batch_dev(SvtHipCtx *ctx, const uint8_t *d_im1, int stride1, const uint8_t *d_im2, int stride2, int w, int h, const int32_t *d_pairs,
+                                           int n, double *d_out);
+/* svt_av1_determine_correspondence (Encoder/Codec/corner_match.c:151-212, with improve_correspondence :78-149) of one source against n_refs <= 8 references.
+ * d_src_points / d_src_count: one plane's list and count as svt_hip_gm_corners_batch_dev writes them; d_ref_points[n_refs][max_points][2] / d_ref_counts[n_refs]
+ * likewise, so the two calls chain on one stream with no host round trip.  refs is a host array; every plane is read as w x h, the source's size, as the reference
+ * does (width / height of a table entry are not used; stride >= w).  d_corr[r][max_points][4] = x, y, rx, ry of the d_ncorr[r] correspondences, in the source
+ * list's order; the rest of d_corr[r] is unspecified. */
+int svt_hip_gm_correspondences_batch_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int w, int h, const int32_t *d_src_points, const int32_t *d_src_count,
+                                         const SvtHipGmRef *refs, int n_refs, const int32_t *d_ref_points, const int32_t *d_ref_counts, int max_points,
+                                         int32_t *d_corr, int32_t *d_ncorr);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -199,6 +199,7 @@ class GmResult(C.Structure):
 
 
 GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
+GM_MAX_CORNERS = 4096   # SVT_HIP_GM_MAX_CORNERS
 TPL_MAX_REFS = 7   # MAX_PA_ME_MV: slots 0..3 list 0, 4..6 list 1
 
 
@@ -377,6 +378,11 @@ def lib():
     L.svt_hip_gm_refine_scratch_bytes.argtypes = [i32]
     L.svt_hip_gm_refine_scratch_bytes.restype = C.c_size_t
     L.svt_hip_gm_refine_picture_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, vp, i32, vp, vp, C.POINTER(i32)]
+    L.svt_hip_gm_corners_scratch_bytes.argtypes = [C.POINTER(GmRef), i32]
+    L.svt_hip_gm_corners_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_gm_corners_batch_dev.argtypes = [vp, C.POINTER(GmRef), i32, i32, vp, vp, vp, vp]
+    L.svt_hip_gm_cross_correlation_batch_dev.argtypes = [vp, u8p, i32, u8p, i32, i32, i32, vp, i32, vp]
+    L.svt_hip_gm_correspondences_batch_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp, C.POINTER(GmRef), i32, vp, vp, i32, vp, vp]
     _lib = L
     return L
 
@@ -629,6 +635,97 @@ class Context:
             if n:
                 self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_o, C.sizeof(out)), "d2h")
             return out, polls.value
+        finally:
+            self.free(*held)
+
+    def _gm_plane_table(self, planes, held, n_tab):
+        tab = (GmRef * n_tab)()
+        for i, r in enumerate(planes):
+            d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
+            tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
+        return tab
+
+    def _gm_corners_dev(self, tab, n, max_points, held):
+        """-> device pointers (points [n][max_points][2], counts [n], kept [n]) of svt_hip_gm_corners_batch_dev; nothing is synchronised."""
+        import numpy as np
+        d_p = self.to_device(np.full((n, max_points, 2), -7, np.int32)); held.append(d_p)
+        d_c = self.to_device(np.full(n, -7, np.int32)); held.append(d_c)
+        d_k = self.to_device(np.full(n, -7, np.int32)); held.append(d_k)
+        d_x = self.empty(self.L.svt_hip_gm_corners_scratch_bytes(tab, n)); held.append(d_x)
+        self.check(self.L.svt_hip_gm_corners_batch_dev(self.h, tab, n, max_points, d_p, d_c, d_k, d_x), "gm_corners_batch")
+        return d_p, d_c, d_k
+
+    def gm_corners_batch(self, planes, max_points=GM_MAX_CORNERS):
+        """svt_hip_gm_corners_batch_dev: up to 9 2-D uint8 `planes` (own sizes; offset / strided views allowed) -> (list of int32 [count][2] x, y per plane,
+        counts int32 [n], kept-before-truncation int32 [n])."""
+        import numpy as np
+        held = []
+        try:
+            n = len(planes)
+            tab = self._gm_plane_table(planes, held, 1 + GM_MAX_REFS)
+            d_p, d_c, d_k = self._gm_corners_dev(tab, n, max_points, held)
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            pts, cnt, kept = self.to_host(d_p, (n, max_points, 2), np.int32), self.to_host(d_c, (n,), np.int32), self.to_host(d_k, (n,), np.int32)
+            return [pts[i, :max(0, min(int(cnt[i]), max_points))].copy() for i in range(n)], cnt, kept
+        finally:
+            self.free(*held)
+
+    def gm_cross_correlation_batch(self, im1, im2, pairs):
+        """svt_hip_gm_cross_correlation_batch_dev: `im1` / `im2` 2-D uint8 planes of one size, `pairs` [n][4] int32 x1, y1, x2, y2 -> float64 [n]."""
+        import numpy as np
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 4)
+        assert im1.shape == im2.shape
+        held = []
+        try:
+            d_a, p_a, s_a, _ = self._upload_plane(im1); held.append(d_a)
+            d_b, p_b, s_b, _ = self._upload_plane(im2); held.append(d_b)
+            d_q = self.to_device(pairs); held.append(d_q)
+            d_o = self.to_device(np.full(max(len(pairs), 1), -7.0, np.float64)); held.append(d_o)
+            self.check(self.L.svt_hip_gm_cross_correlation_batch_dev(self.h, p_a, s_a, p_b, s_b, im1.shape[1], im1.shape[0], d_q, len(pairs), d_o),
+                       "gm_cross_correlation_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_o, (len(pairs),), np.float64)
+        finally:
+            self.free(*held)
+
+    def gm_correspondences_batch(self, src, refs, src_points=None, ref_points=None, max_points=GM_MAX_CORNERS):
+        """svt_hip_gm_correspondences_batch_dev: `src` and up to 8 `refs` 2-D uint8 planes (the references are read at the source's size), `src_points` an int32
+        [n][2] list and `ref_points` one such list per reference -> list of int32 [ncorr][4] x, y, rx, ry per reference.  With both lists None the corners come
+        from svt_hip_gm_corners_batch_dev on the same stream and stay on the device in between."""
+        import numpy as np
+        held = []
+        try:
+            h, w = src.shape
+            n = len(refs)
+            if src_points is None and ref_points is None:
+                tab = self._gm_plane_table([src] + list(refs), held, 1 + GM_MAX_REFS)
+                d_p, d_c, _ = self._gm_corners_dev(tab, n + 1, max_points, held)
+                p_s, s_s = tab[0].d_plane, tab[0].stride
+                rtab = (GmRef * GM_MAX_REFS)(*[tab[i + 1] for i in range(n)])
+                d_sp, d_sc = d_p, d_c
+                d_rp, d_rc = C.c_void_p(d_p.value + max_points * 8), C.c_void_p(d_c.value + 4)
+            else:
+                d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+                rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
+                sp = np.ascontiguousarray(src_points, np.int32).reshape(-1, 2)
+                assert len(sp) <= max_points and len(ref_points) == n
+                rp = np.full((max(n, 1), max_points, 2), -7, np.int32)
+                rc = np.zeros(max(n, 1), np.int32)
+                for i, q in enumerate(ref_points):
+                    q = np.ascontiguousarray(q, np.int32).reshape(-1, 2)
+                    rp[i, :len(q)] = q; rc[i] = len(q)
+                d_sp = self.to_device(sp); held.append(d_sp)
+                d_sc = self.to_device(np.array([len(sp)], np.int32)); held.append(d_sc)
+                d_rp = self.to_device(rp); held.append(d_rp)
+                d_rc = self.to_device(rc); held.append(d_rc)
+            d_o = self.to_device(np.full((max(n, 1), max_points, 4), -7, np.int32)); held.append(d_o)
+            d_n = self.to_device(np.full(max(n, 1), -7, np.int32)); held.append(d_n)
+            self.check(self.L.svt_hip_gm_correspondences_batch_dev(self.h, p_s, s_s, w, h, d_sp, d_sc, rtab, n, d_rp, d_rc, max_points, d_o, d_n),
+                       "gm_correspondences_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out, cnt = self.to_host(d_o, (max(n, 1), max_points, 4), np.int32), self.to_host(d_n, (max(n, 1),), np.int32)
+            assert all(0 <= int(c) <= max_points for c in cnt[:n])
+            return [out[i, :int(cnt[i])].copy() for i in range(n)]
         finally:
             self.free(*held)
 

@@ -252,7 +252,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -427,6 +427,48 @@ int svt_hip_gm_refine_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int src_st
     }
     if (polls_out) *polls_out = polls;
     return SVT_HIP_OK;
+}
+
+/* the front half: corners and correspondences (gm_front.hip) */
+static bool gm_planes_bad(const SvtHipGmRef* p, int n) {
+    bool bad = !p;
+    for (int i = 0; i < n && !bad; i++) bad = gm_plane_bad(p[i].d_plane, p[i].stride, p[i].width, p[i].height);
+    return bad;
+}
+
+size_t svt_hip_gm_corners_scratch_bytes(const SvtHipGmRef* planes, int n_planes) {
+    if (n_planes < 1 || n_planes > 1 + SVT_HIP_GM_MAX_REFS || gm_planes_bad(planes, n_planes)) return 0;
+    return svt_hip_gm_corners_scratch_layout_bytes(planes, n_planes);
+}
+
+int svt_hip_gm_corners_batch_dev(SvtHipCtx* c, const SvtHipGmRef* planes, int n_planes, int max_points, int32_t* d_points, int32_t* d_counts, int32_t* d_kept,
+                                 void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    if (!c || n_planes < 1 || n_planes > 1 + SVT_HIP_GM_MAX_REFS || gm_planes_bad(planes, n_planes) || max_points < 1 || max_points > SVT_HIP_GM_MAX_CORNERS || !d_points ||
+        !d_counts || !d_scratch || ((uintptr_t)d_scratch & 7))
+        return bad_arg(c, "svt_hip_gm_corners_batch_dev: bad argument (1 <= n_planes <= 9, planes 8 .. 16384 wide and high, stride >= width, 1 <= max_points <= 4096)");
+    return launched(c, svt_hip_launch_gm_corners(c->stream, planes, n_planes, max_points, d_points, d_counts, d_kept, d_scratch), "global-motion corner launch");
+}
+
+int svt_hip_gm_cross_correlation_batch_dev(SvtHipCtx* c, const uint8_t* d_im1, int stride1, const uint8_t* d_im2, int stride2, int w, int h, const int32_t* d_pairs, int n,
+                                           double* d_out) {
+    SVT_HIP_ENTER(c);
+    if (!c || gm_plane_bad(d_im1, stride1, w, h) || gm_plane_bad(d_im2, stride2, w, h) || n < 0 || n > SVT_HIP_GM_MAX_MODELS || !d_pairs || !d_out)
+        return bad_arg(c, "svt_hip_gm_cross_correlation_batch_dev: bad argument (planes 8 .. 16384 wide and high, strides >= w, 0 <= n <= 2^20)");
+    return launched(c, svt_hip_launch_gm_cross_correlation(c->stream, d_im1, stride1, d_im2, stride2, w, h, d_pairs, n, d_out), "global-motion cross-correlation launch");
+}
+
+int svt_hip_gm_correspondences_batch_dev(SvtHipCtx* c, const uint8_t* d_src, int src_stride, int w, int h, const int32_t* d_src_points, const int32_t* d_src_count,
+                                         const SvtHipGmRef* refs, int n_refs, const int32_t* d_ref_points, const int32_t* d_ref_counts, int max_points, int32_t* d_corr,
+                                         int32_t* d_ncorr) {
+    SVT_HIP_ENTER(c);
+    bool bad = !c || gm_plane_bad(d_src, src_stride, w, h) || !d_src_points || !d_src_count || !refs || n_refs < 1 || n_refs > SVT_HIP_GM_MAX_REFS || !d_ref_points ||
+               !d_ref_counts || max_points < 1 || max_points > SVT_HIP_GM_MAX_CORNERS || !d_corr || !d_ncorr;
+    for (int i = 0; i < n_refs && !bad; i++) bad = !refs[i].d_plane || refs[i].stride < w;   // read as w x h, like the reference: width / height are not used
+    if (bad)
+        return bad_arg(c, "svt_hip_gm_correspondences_batch_dev: bad argument (source 8 .. 16384 wide and high, every stride >= w, 1 <= n_refs <= 8, 1 <= max_points <= 4096)");
+    return launched(c, svt_hip_launch_gm_correspondences(c->stream, d_src, src_stride, w, h, d_src_points, d_src_count, refs, n_refs, d_ref_points, d_ref_counts, max_points,
+                                                         d_corr, d_ncorr), "global-motion correspondence launch");
 }
 
 /* ------------------------------------------------------------------------------------------- ME */

@@ -163,6 +163,13 @@ size_t svt_hip_gm_refine_scratch_layout_bytes(int njobs);
 int svt_hip_launch_gm_refine_rounds(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const SvtHipGmRef* refs, int n_refs, const SvtHipGmJob* jobs,
                                     int njobs, SvtHipGmResult* results, void* scratch, const uint16_t* d_lut, int start, int n_rounds);
 const int* svt_hip_gm_done_counter(void* scratch, int njobs);
+/* gm_front.hip */
+size_t svt_hip_gm_corners_scratch_layout_bytes(const SvtHipGmRef* planes, int n_planes);
+int svt_hip_launch_gm_corners(hipStream_t st, const SvtHipGmRef* planes, int n_planes, int max_points, int* points, int* counts, int* kept, void* scratch);
+int svt_hip_launch_gm_cross_correlation(hipStream_t st, const uint8_t* im1, int stride1, const uint8_t* im2, int stride2, int w, int h, const int* pairs, int n,
+                                        double* out);
+int svt_hip_launch_gm_correspondences(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const int* src_points, const int* src_count,
+                                      const SvtHipGmRef* refs, int n_refs, const int* ref_points, const int* ref_counts, int max_points, int* corr, int* ncorr);
 /* per-call forms (percall.hip, cdef.hip, deblock.hip) */
 int svt_hip_launch_quantize_blocks(hipStream_t st, const int32_t* coeff, int n, int nblk, const SvtHipQuantParams* qp, const int16_t* iscan, int32_t* qcoeff,
                                    int32_t* dqcoeff, uint16_t* eob);
