@@ -1103,8 +1103,9 @@ int svt_hip_tpl_set_phases(SvtHipCtx *ctx, int mask);
  * Planes: d_* points at sample (0, 0), any stride >= width, any base offset; width and height >= 8, not necessarily multiples of 8; nothing outside
  * [0, width) x [0, height) of a plane is read (the warp clamps to the reference plane's edges as the reference does).  The source is w x h; a reference
  * plane has its own width / height / stride (they bound the clamp; the error is always summed over the source's w x h).
- * Corner detection and the correspondence search have device forms too (the svt_hip_gm_corners / cross_correlation / correspondences entry points below); RANSAC,
- * gm_get_params_cost / svt_av1_is_enough_erroradvantage and the high-bit-depth twins stay on the host. */
+ * Corner detection, the correspondence search and the RANSAC model fit have device forms too (the svt_hip_gm_corners / cross_correlation / correspondences /
+ * svt_hip_gm_fit entry points below); the decision loop with gm_get_params_cost / svt_av1_is_enough_erroradvantage is host arithmetic
+ * (svt_hip_gm_decide_host); only the high-bit-depth twins stay on the host. */
 typedef struct {
     int32_t mat[6];                     /* EbWarpedMotionParams::wmmat[0..5] as svt_warp_plane uses them */
     int16_t alpha, beta, gamma, delta;  /* its shear parameters */
@@ -1158,8 +1159,9 @@ int svt_hip_gm_refine_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_
 /* The error table the three kernels use, min(16384, floor(16384 (|i - 255| / 255)^0.7 + 0.5)), i = 0..511 (host; needs no device). */
 int svt_hip_gm_error_table(uint16_t out[512]);
 
-/* The front half of compute_global_motion_feature_based (Encoder/Codec/global_motion.c:274-320): corners and correspondences, bit for bit; RANSAC takes the
- * correspondence list on the host.  Lists and counts live in device memory: the kernels clamp a count to [0, max_points] and pass every coordinate, any int,
+/* The front half of compute_global_motion_feature_based (Encoder/Codec/global_motion.c:274-320): corners and correspondences, bit for bit; the model fit
+ * (svt_hip_gm_fit_batch_dev) takes the correspondence lists where they are.
+ * Lists and counts live in device memory: the kernels clamp a count to [0, max_points] and pass every coordinate, any int,
  * through the reference's eligibility tests before it becomes an address.
  *
  * svt_av1_fast_corner_detect (Encoder/Codec/corner_detect.c:19-32: FAST-9 at barrier 18, third_party/fastfeat/fast_9.c, the score of :8-2937, the non-maximum
@@ -1183,6 +1185,90 @@ int svt_hip_gm_cross_correlation_batch_dev(SvtHipCtx *ctx, const uint8_t *d_im1,
 int svt_hip_gm_correspondences_batch_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int w, int h, const int32_t *d_src_points, const int32_t *d_src_count,
                                          const SvtHipGmRef *refs, int n_refs, const int32_t *d_ref_points, const int32_t *d_ref_counts, int max_points,
                                          int32_t *d_corr, int32_t *d_ncorr);
+
+/* The model fit: ransac() (Encoder/Codec/ransac.c:359-542, reached through svt_av1_get_ransac_type :779-786, with least_squares / linsolve of
+ * Encoder/Codec/mathutils.h:26-111 and lcg_rand16 of random.h:20-23), svt_av1_convert_model_to_params (Encoder/Codec/global_motion.c:41-86) and the
+ * MIN_INLIER_PROB rule (global_motion.c:310-318), one workgroup per job, bit for bit: every operation is an IEEE double in the reference's order
+ * (svt-av1_amd/csrc/gm_fit.h; docs/kernels/gm.md "The fit").  A job fits one model type to one correspondence list.
+ *   d_corr[n_lists][max_points][4], d_ncorr[n_lists] : as svt_hip_gm_correspondences_batch_dev writes them (device memory); a count is clamped to [0, max_points]
+ *   jobs       : host array of njobs <= SVT_HIP_GM_FIT_MAX_JOBS; ref = the list (and the reference plane of the refinement job), 0 <= ref < n_lists;
+ *                type = 1 TRANSLATION, 2 ROTZOOM, 3 AFFINE
+ *   num_motions: must be 1 (RANSAC_NUM_MOTIONS; the reference's qsort of equal motions is unspecified beyond that)
+ *   d_fits[njobs], d_inliers[njobs][max_points] (may be NULL: the indices of the kept motion's inliers, the first num_inliers entries are specified when
+ *   num_inliers >= 3), d_refine_jobs[njobs] (may be NULL): what svt_hip_gm_refine_picture_dev reads: ref, wmtype / wmmat of the converted model, n_refinements,
+ *   best_frame_error = INT64_MAX; wmtype = -1 where compute_global_motion would not refine (no inliers after the rule, or an IDENTITY model:
+ *   EbGlobalMotionEstimation.c:331-335), which the refinement finishes at once with result wmtype -1.
+ *   d_scratch  : svt_hip_gm_fit_scratch_bytes(njobs, max_points) bytes, 8-byte aligned
+ * ret = 1 with num_inliers = 0 and identity params: fewer than 15 points, a draw degenerate more than 10 times in one trial.  A kept motion of 2 inliers
+ * reports its count and identity params (the reference recomputes from 3 inliers on).  params = the identity the reference's caller stores first
+ * (EbGlobalMotionEstimation.c:308-313) wherever the fit writes none.  A parameter whose scaled value leaves int32 has no defined conversion in the reference;
+ * here it is clamped in double first, and such models are outside the contract.  The *_double_prec variants are not built.
+ * Stream-ordered and asynchronous: no host synchronisation, no allocation. */
+typedef struct {
+    int32_t ref;                        /* index of the correspondence list = of the reference plane */
+    int32_t type;                       /* 1 TRANSLATION, 2 ROTZOOM, 3 AFFINE */
+} SvtHipGmFitJob;
+typedef struct {
+    int32_t ret;                        /* what the fit function returns */
+    int32_t npoints;                    /* the list's count after the clamp */
+    int32_t num_inliers;                /* num_inliers_by_motion[0] as the fit reports it */
+    int32_t num_inliers_kept;           /* after the MIN_INLIER_PROB rule: 0 = compute_global_motion ignores the motion */
+    double  params[8];                  /* MotionModel::params */
+    int32_t wmmat[8];                   /* svt_av1_convert_model_to_params of them */
+    int32_t wmtype;
+    int32_t reserved;
+} SvtHipGmFit;
+#define SVT_HIP_GM_FIT_MAX_JOBS 64
+size_t svt_hip_gm_fit_scratch_bytes(int njobs, int max_points);
+int svt_hip_gm_fit_batch_dev(SvtHipCtx *ctx, const int32_t *d_corr, const int32_t *d_ncorr, int n_lists, int max_points, const SvtHipGmFitJob *jobs, int njobs,
+                             int num_motions, int n_refinements, SvtHipGmFit *d_fits, int32_t *d_inliers, SvtHipGmJob *d_refine_jobs, void *d_scratch);
+
+/* The decision of compute_global_motion (Encoder/Codec/EbGlobalMotionEstimation.c:303-399) for one reference picture, replayed from per-model records: the loop
+ * over ROTZOOM, AFFINE (ROTZOOM only when rotzoom_model_only) with ONE global_motion that persists across iterations: svt_get_shear_params resets an invalid
+ * model, a TRANSLATION result is rewritten by convert_to_trans_prec, IDENTITY and ref_frame_error == 0 `continue` (without resetting the model),
+ * svt_av1_is_enough_erroradvantage((double)best / ref_frame_error, gm_get_params_cost(model, default, allow_high_precision_mv), GM_ERRORADV_TR_0) decides, a
+ * non-identity model ends the loop.  models[0] = ROTZOOM's record, models[1] = AFFINE's (not read when rotzoom_model_only).  Needs no device. */
+typedef struct {
+    int32_t num_inliers_kept;           /* SvtHipGmFit::num_inliers_kept: 0 = the motion is skipped */
+    int32_t fit_wmtype;                 /* SvtHipGmFit::wmtype: 0 = not refined */
+    int32_t wmmat[8];                   /* SvtHipGmResult::wmmat of the refinement */
+    int32_t wmtype;                     /* SvtHipGmResult::wmtype (-1 = not refined) */
+    int32_t reserved;
+    int64_t best_error;                 /* SvtHipGmResult::best_error */
+} SvtHipGmModelRecord;
+/* gm_get_params_cost(gm, &default_warp_params, allow_hp) (Encoder/Codec/EbGlobalMotionEstimationCost.c:17-75 with svt_aom_count_primitive_refsubexpfin) */
+int svt_hip_gm_params_cost_host(const int32_t wmmat[8], int wmtype, int allow_high_precision_mv);
+int svt_hip_gm_decide_host(const SvtHipGmModelRecord models[2], int64_t ref_frame_error, int rotzoom_model_only, int allow_high_precision_mv,
+                           int32_t wmmat_out[8], int32_t *wmtype_out);
+
+/* compute_global_motion (Encoder/Codec/EbGlobalMotionEstimation.c:262-405) of one source against n_refs <= 8 references in one call, on one stream: corners of
+ * the source and of every reference (one call), correspondences (one call), the ROTZOOM and, unless rotzoom_model_only, AFFINE fit of every reference (one
+ * launch), the refinement of all the jobs that launch wrote (svt_hip_gm_refine_picture_dev: its poll of the done counter is the only synchronisation before the
+ * end), the frame errors, one download, svt_hip_gm_decide_host.  The AFFINE fit and walk are speculated: the reference runs them only when ROTZOOM ends as
+ * IDENTITY; they depend on nothing the ROTZOOM iteration computes, and the decision discards them when the loop would have ended.  Corners and
+ * correspondences are found once per reference (the reference finds the same ones once per model type).
+ * A reference plane is read over the source's w x h for corners, correspondences and the frame error (so it must be at least that large) and clamps the warp
+ * to its own width x height.  results = host array of n_refs records.  d_scratch: svt_hip_gm_estimate_scratch_bytes bytes (0 = the arguments would be refused),
+ * 256-byte aligned.  8-bit only.  Not part of this call: the level / list / identity-exit logic of global_motion_estimation (:186-245). */
+typedef struct {
+    int32_t rotzoom_model_only;         /* gm_ctrls.rotzoom_model_only */
+    int32_t allow_high_precision_mv;
+    int32_t n_refinements;              /* the reference uses 5 */
+    int32_t max_points;                 /* 1 .. SVT_HIP_GM_MAX_CORNERS; the reference uses MAX_CORNERS = 4096 */
+} SvtHipGmEstimateOptions;
+typedef struct {
+    int32_t wmmat[8];                   /* *bestWarpedMotion */
+    int32_t wmtype;
+    int32_t num_correspondences;
+    int32_t n_models;                   /* 1 (ROTZOOM) or 2 (ROTZOOM, AFFINE): how many entries of fits / models are set */
+    int32_t reserved;
+    int64_t ref_frame_error;
+    SvtHipGmFit fits[2];                /* what the decision consumed, per model type */
+    SvtHipGmModelRecord models[2];
+} SvtHipGmEstimate;
+size_t svt_hip_gm_estimate_scratch_bytes(int w, int h, int n_refs, const SvtHipGmEstimateOptions *options);
+int svt_hip_gm_estimate_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int stride, int w, int h, const SvtHipGmRef *refs, int n_refs,
+                                    const SvtHipGmEstimateOptions *options, SvtHipGmEstimate *results, void *d_scratch);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -198,7 +198,36 @@ class GmResult(C.Structure):
                 ("invalid_probes", C.c_int32)]
 
 
+class GmFitJob(C.Structure):
+    """SvtHipGmFitJob (include/svt_hip.h)."""
+    _fields_ = [("ref", C.c_int32), ("type", C.c_int32)]
+
+
+class GmFit(C.Structure):
+    """SvtHipGmFit (include/svt_hip.h)."""
+    _fields_ = [("ret", C.c_int32), ("npoints", C.c_int32), ("num_inliers", C.c_int32), ("num_inliers_kept", C.c_int32), ("params", C.c_double * 8),
+                ("wmmat", C.c_int32 * 8), ("wmtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GmModelRecord(C.Structure):
+    """SvtHipGmModelRecord (include/svt_hip.h)."""
+    _fields_ = [("num_inliers_kept", C.c_int32), ("fit_wmtype", C.c_int32), ("wmmat", C.c_int32 * 8), ("wmtype", C.c_int32), ("reserved", C.c_int32),
+                ("best_error", C.c_int64)]
+
+
+class GmEstimateOptions(C.Structure):
+    """SvtHipGmEstimateOptions (include/svt_hip.h)."""
+    _fields_ = [("rotzoom_model_only", C.c_int32), ("allow_high_precision_mv", C.c_int32), ("n_refinements", C.c_int32), ("max_points", C.c_int32)]
+
+
+class GmEstimate(C.Structure):
+    """SvtHipGmEstimate (include/svt_hip.h)."""
+    _fields_ = [("wmmat", C.c_int32 * 8), ("wmtype", C.c_int32), ("num_correspondences", C.c_int32), ("n_models", C.c_int32), ("reserved", C.c_int32),
+                ("ref_frame_error", C.c_int64), ("fits", GmFit * 2), ("models", GmModelRecord * 2)]
+
+
 GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
+GM_FIT_MAX_JOBS = 64   # SVT_HIP_GM_FIT_MAX_JOBS
 GM_MAX_CORNERS = 4096   # SVT_HIP_GM_MAX_CORNERS
 TPL_MAX_REFS = 7   # MAX_PA_ME_MV: slots 0..3 list 0, 4..6 list 1
 
@@ -383,6 +412,14 @@ def lib():
     L.svt_hip_gm_corners_batch_dev.argtypes = [vp, C.POINTER(GmRef), i32, i32, vp, vp, vp, vp]
     L.svt_hip_gm_cross_correlation_batch_dev.argtypes = [vp, u8p, i32, u8p, i32, i32, i32, vp, i32, vp]
     L.svt_hip_gm_correspondences_batch_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp, C.POINTER(GmRef), i32, vp, vp, i32, vp, vp]
+    L.svt_hip_gm_fit_scratch_bytes.argtypes = [i32, i32]
+    L.svt_hip_gm_fit_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_gm_fit_batch_dev.argtypes = [vp, vp, vp, i32, i32, C.POINTER(GmFitJob), i32, i32, i32, vp, vp, vp, vp]
+    L.svt_hip_gm_params_cost_host.argtypes = [C.POINTER(C.c_int32), i32, i32]
+    L.svt_hip_gm_decide_host.argtypes = [C.POINTER(GmModelRecord), C.c_int64, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.svt_hip_gm_estimate_scratch_bytes.argtypes = [i32, i32, i32, C.POINTER(GmEstimateOptions)]
+    L.svt_hip_gm_estimate_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_gm_estimate_picture_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, C.POINTER(GmEstimateOptions), C.POINTER(GmEstimate), vp]
     _lib = L
     return L
 
@@ -726,6 +763,69 @@ class Context:
             out, cnt = self.to_host(d_o, (max(n, 1), max_points, 4), np.int32), self.to_host(d_n, (max(n, 1),), np.int32)
             assert all(0 <= int(c) <= max_points for c in cnt[:n])
             return [out[i, :int(cnt[i])].copy() for i in range(n)]
+        finally:
+            self.free(*held)
+
+    def gm_fit_batch(self, corr, counts, jobs, n_refinements=5, want_inliers=True, want_jobs=True, repeat=1, refine=None, num_motions=1):
+        """svt_hip_gm_fit_batch_dev: `corr` int32 [n_lists][max_points][4] and `counts` int32 [n_lists] as the correspondence call leaves them, `jobs` a list of
+        (list index, model type).  `repeat` calls are issued back to back on the same scratch.  refine = (src, refs): svt_hip_gm_refine_picture_dev then runs on
+        the jobs the fit wrote, without leaving the device.  -> (ctypes array of GmFit, int32 [njobs][max_points] inlier indices or None, ctypes array of GmJob or
+        None, ctypes array of GmResult or None)."""
+        import numpy as np
+        corr = np.ascontiguousarray(corr, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        n_lists, max_points = corr.shape[0], corr.shape[1]
+        n = len(jobs)
+        tab = (GmFitJob * max(n, 1))(*[GmFitJob(r, t) for r, t in jobs])
+        held = []
+        try:
+            d_c = self.to_device(corr); held.append(d_c)
+            d_n = self.to_device(counts); held.append(d_n)
+            d_f = self.to_device(np.full(max(n, 1) * C.sizeof(GmFit), 0xA5, np.uint8)); held.append(d_f)
+            d_i = d_j = None
+            if want_inliers:
+                d_i = self.to_device(np.full((max(n, 1), max_points), -7, np.int32)); held.append(d_i)
+            if want_jobs or refine:
+                d_j = self.to_device(np.full(max(n, 1) * C.sizeof(GmJob), 0xA5, np.uint8)); held.append(d_j)
+            d_x = self.empty(max(self.L.svt_hip_gm_fit_scratch_bytes(n, max_points), 8)); held.append(d_x)
+            for _ in range(repeat):
+                self.check(self.L.svt_hip_gm_fit_batch_dev(self.h, d_c, d_n, n_lists, max_points, tab, n, num_motions, n_refinements, d_f, d_i, d_j, d_x), "gm_fit_batch")
+            res = None
+            if refine and n:
+                src, refs = refine
+                d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+                rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
+                d_o = self.empty(n * C.sizeof(GmResult)); held.append(d_o)
+                d_y = self.empty(self.L.svt_hip_gm_refine_scratch_bytes(n)); held.append(d_y)
+                self.check(self.L.svt_hip_gm_refine_picture_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], rtab, len(refs), d_j, n, d_o, d_y, None), "gm_refine_picture")
+                res = (GmResult * n)()
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            fits, out_jobs = (GmFit * n)(), (GmJob * n)() if d_j else None
+            if n:
+                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(fits, C.c_void_p), d_f, C.sizeof(fits)), "d2h")
+                if d_j:
+                    self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_jobs, C.c_void_p), d_j, C.sizeof(out_jobs)), "d2h")
+                if res is not None:
+                    self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(res, C.c_void_p), d_o, C.sizeof(res)), "d2h")
+            inl = self.to_host(d_i, (max(n, 1), max_points), np.int32)[:n] if d_i else None
+            return fits, inl, out_jobs, res
+        finally:
+            self.free(*held)
+
+    def gm_estimate_picture(self, src, refs, rotzoom_model_only=0, allow_high_precision_mv=0, n_refinements=5, max_points=GM_MAX_CORNERS, repeat=1):
+        """svt_hip_gm_estimate_picture_dev: `src` a 2-D uint8 plane, `refs` up to 8 such planes at least as large (offset / strided views allowed); `repeat` calls
+        on the same scratch -> ctypes array of GmEstimate, one per reference (of the last call)."""
+        held = []
+        try:
+            h, w = src.shape
+            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+            rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
+            opt = GmEstimateOptions(rotzoom_model_only, allow_high_precision_mv, n_refinements, max_points)
+            d_x = self.empty(max(self.L.svt_hip_gm_estimate_scratch_bytes(w, h, len(refs), C.byref(opt)), 256)); held.append(d_x)
+            out = (GmEstimate * max(len(refs), 1))()
+            for _ in range(repeat):
+                self.check(self.L.svt_hip_gm_estimate_picture_dev(self.h, p_s, s_s, w, h, rtab, len(refs), C.byref(opt), out, d_x), "gm_estimate_picture")
+            return out
         finally:
             self.free(*held)
 

@@ -252,7 +252,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -469,6 +469,132 @@ int svt_hip_gm_correspondences_batch_dev(SvtHipCtx* c, const uint8_t* d_src, int
         return bad_arg(c, "svt_hip_gm_correspondences_batch_dev: bad argument (source 8 .. 16384 wide and high, every stride >= w, 1 <= n_refs <= 8, 1 <= max_points <= 4096)");
     return launched(c, svt_hip_launch_gm_correspondences(c->stream, d_src, src_stride, w, h, d_src_points, d_src_count, refs, n_refs, d_ref_points, d_ref_counts, max_points,
                                                          d_corr, d_ncorr), "global-motion correspondence launch");
+}
+
+/* the model fit (gm_fit.hip) */
+size_t svt_hip_gm_fit_scratch_bytes(int njobs, int max_points) {
+    if (njobs < 0 || njobs > SVT_HIP_GM_FIT_MAX_JOBS || max_points < 1 || max_points > SVT_HIP_GM_MAX_CORNERS) return 0;
+    return svt_hip_gm_fit_scratch_layout_bytes(njobs, max_points);
+}
+
+int svt_hip_gm_fit_batch_dev(SvtHipCtx* c, const int32_t* d_corr, const int32_t* d_ncorr, int n_lists, int max_points, const SvtHipGmFitJob* jobs, int njobs,
+                             int num_motions, int n_refinements, SvtHipGmFit* d_fits, int32_t* d_inliers, SvtHipGmJob* d_refine_jobs, void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    if (c && num_motions != 1) return bad_arg(c, "svt_hip_gm_fit_batch_dev: num_motions must be 1 (RANSAC_NUM_MOTIONS)");
+    bool bad = !c || num_motions != 1 || !d_corr || !d_ncorr || n_lists < 1 || n_lists > SVT_HIP_GM_MAX_REFS || max_points < 1 || max_points > SVT_HIP_GM_MAX_CORNERS ||
+               !jobs || njobs < 0 || njobs > SVT_HIP_GM_FIT_MAX_JOBS || n_refinements < 0 || n_refinements > SVT_HIP_GM_MAX_REFINEMENTS || !d_fits || !d_scratch ||
+               ((uintptr_t)d_scratch & 7);
+    for (int i = 0; i < njobs && !bad; i++) bad = jobs[i].ref < 0 || jobs[i].ref >= n_lists || jobs[i].type < 1 || jobs[i].type > 3;
+    if (bad)
+        return bad_arg(c, "svt_hip_gm_fit_batch_dev: bad argument (1 <= n_lists <= 8, 1 <= max_points <= 4096, 0 <= njobs <= 64, every job's 0 <= ref < n_lists and "
+                          "1 <= type <= 3, 0 <= n_refinements <= 12, scratch 8-byte aligned)");
+    if (!njobs) return SVT_HIP_OK;
+    return launched(c, svt_hip_launch_gm_fit(c->stream, d_corr, d_ncorr, max_points, jobs, njobs, n_refinements, d_fits, d_inliers, d_refine_jobs, d_scratch),
+                    "global-motion model fit launch");
+}
+
+/* the picture call: corners -> correspondences -> fits -> refinement -> frame errors on one stream, one download, the decision on the host */
+namespace {
+struct GmEstimateLayout {
+    size_t points, counts, corners, corr, ncorr, fit_scratch, jobs, refine_scratch, out, fits, results, ferr, out_bytes, total;
+    int njobs, nm;
+};
+size_t gm_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+bool gm_estimate_options_bad(const SvtHipGmEstimateOptions* o) {
+    return !o || o->max_points < 1 || o->max_points > SVT_HIP_GM_MAX_CORNERS || o->n_refinements < 0 || o->n_refinements > SVT_HIP_GM_MAX_REFINEMENTS;
+}
+GmEstimateLayout gm_estimate_layout(int w, int h, int n_refs, const SvtHipGmEstimateOptions* o) {
+    GmEstimateLayout l = {};
+    l.nm = o->rotzoom_model_only ? 1 : 2;
+    l.njobs = n_refs * l.nm;
+    SvtHipGmRef planes[1 + SVT_HIP_GM_MAX_REFS] = {};
+    for (int i = 0; i <= n_refs; i++) { planes[i].width = w; planes[i].height = h; }
+    size_t off = 0;
+    l.points = off; off += gm_up256((size_t)(1 + n_refs) * o->max_points * 2 * sizeof(int32_t));
+    l.counts = off; off += gm_up256((size_t)(1 + n_refs) * sizeof(int32_t));
+    l.corners = off; off += gm_up256(svt_hip_gm_corners_scratch_layout_bytes(planes, 1 + n_refs));
+    l.corr = off; off += gm_up256((size_t)n_refs * o->max_points * 4 * sizeof(int32_t));
+    l.ncorr = off; off += gm_up256((size_t)n_refs * sizeof(int32_t));
+    l.fit_scratch = off; off += gm_up256(svt_hip_gm_fit_scratch_layout_bytes(l.njobs, o->max_points));
+    l.jobs = off; off += gm_up256((size_t)l.njobs * sizeof(SvtHipGmJob));
+    l.refine_scratch = off; off += gm_up256(svt_hip_gm_refine_scratch_layout_bytes(l.njobs));
+    l.out = off;   // what the one download takes: fits, refinement results, frame errors, correspondence counts
+    l.fits = 0;
+    l.results = l.fits + (size_t)l.njobs * sizeof(SvtHipGmFit);
+    l.ferr = l.results + (size_t)l.njobs * sizeof(SvtHipGmResult);
+    l.out_bytes = l.ferr + (size_t)n_refs * sizeof(int64_t);
+    l.total = off + gm_up256(l.out_bytes);
+    return l;
+}
+}  // namespace
+
+size_t svt_hip_gm_estimate_scratch_bytes(int w, int h, int n_refs, const SvtHipGmEstimateOptions* options) {
+    if (w < 8 || h < 8 || w > SVT_HIP_GM_MAX_DIM || h > SVT_HIP_GM_MAX_DIM || n_refs < 1 || n_refs > SVT_HIP_GM_MAX_REFS || gm_estimate_options_bad(options)) return 0;
+    return gm_estimate_layout(w, h, n_refs, options).total;
+}
+
+int svt_hip_gm_estimate_picture_dev(SvtHipCtx* c, const uint8_t* d_src, int stride, int w, int h, const SvtHipGmRef* refs, int n_refs,
+                                    const SvtHipGmEstimateOptions* options, SvtHipGmEstimate* results, void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    bool bad = !c || gm_plane_bad(d_src, stride, w, h) || !refs || n_refs < 1 || n_refs > SVT_HIP_GM_MAX_REFS || gm_estimate_options_bad(options) || !results ||
+               !d_scratch || ((uintptr_t)d_scratch & 255);
+    // corners and correspondences read a reference over the source's w x h, as the reference does; the refinement clamps to the plane's own size
+    for (int i = 0; i < n_refs && !bad; i++)
+        bad = gm_plane_bad(refs[i].d_plane, refs[i].stride, refs[i].width, refs[i].height) || refs[i].width < w || refs[i].height < h;
+    if (bad)
+        return bad_arg(c, "svt_hip_gm_estimate_picture_dev: bad argument (planes 8 .. 16384 wide and high, stride >= width, every reference at least w x h, "
+                          "1 <= n_refs <= 8, 1 <= max_points <= 4096, 0 <= n_refinements <= 12, scratch 256-byte aligned)");
+    const GmEstimateLayout l = gm_estimate_layout(w, h, n_refs, options);
+    uint8_t* base = (uint8_t*)d_scratch;
+    int32_t* d_points = (int32_t*)(base + l.points);
+    int32_t* d_counts = (int32_t*)(base + l.counts);
+    int32_t* d_corr = (int32_t*)(base + l.corr);
+    int32_t* d_ncorr = (int32_t*)(base + l.ncorr);
+    SvtHipGmJob* d_jobs = (SvtHipGmJob*)(base + l.jobs);
+    uint8_t* d_out = base + l.out;
+    SvtHipGmFit* d_fits = (SvtHipGmFit*)(d_out + l.fits);
+    SvtHipGmResult* d_results = (SvtHipGmResult*)(d_out + l.results);
+    int64_t* d_ferr = (int64_t*)(d_out + l.ferr);
+    const int mp = options->max_points;
+
+    SvtHipGmRef planes[1 + SVT_HIP_GM_MAX_REFS];
+    planes[0] = SvtHipGmRef{d_src, w, h, stride, 0};
+    for (int i = 0; i < n_refs; i++) planes[1 + i] = SvtHipGmRef{refs[i].d_plane, w, h, refs[i].stride, 0};
+    if (int rc = svt_hip_gm_corners_batch_dev(c, planes, 1 + n_refs, mp, d_points, d_counts, nullptr, base + l.corners)) return rc;
+    if (int rc = svt_hip_gm_correspondences_batch_dev(c, d_src, stride, w, h, d_points, d_counts, refs, n_refs, d_points + (size_t)mp * 2, d_counts + 1, mp, d_corr, d_ncorr))
+        return rc;
+    SvtHipGmFitJob fit_jobs[2 * SVT_HIP_GM_MAX_REFS];
+    for (int r = 0; r < n_refs; r++)
+        for (int m = 0; m < l.nm; m++) fit_jobs[r * l.nm + m] = SvtHipGmFitJob{r, 2 + m};
+    if (int rc = svt_hip_gm_fit_batch_dev(c, d_corr, d_ncorr, n_refs, mp, fit_jobs, l.njobs, 1, options->n_refinements, d_fits, nullptr, d_jobs, base + l.fit_scratch)) return rc;
+    if (int rc = svt_hip_gm_frame_error_batch_dev(c, d_src, stride, w, h, refs, n_refs, d_ferr)) return rc;
+    if (int rc = svt_hip_gm_refine_picture_dev(c, d_src, stride, w, h, refs, n_refs, d_jobs, l.njobs, d_results, base + l.refine_scratch, nullptr)) return rc;
+
+    std::vector<uint8_t> host(l.out_bytes);
+    HIPCHK(c, hipMemcpyAsync(host.data(), d_out, l.out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const SvtHipGmFit* fits = (const SvtHipGmFit*)(host.data() + l.fits);
+    const SvtHipGmResult* res = (const SvtHipGmResult*)(host.data() + l.results);
+    const int64_t* ferr = (const int64_t*)(host.data() + l.ferr);
+    for (int r = 0; r < n_refs; r++) {
+        SvtHipGmEstimate* e = results + r;
+        std::memset(e, 0, sizeof(*e));
+        e->ref_frame_error = ferr[r];
+        e->n_models = l.nm;
+        for (int m = 0; m < l.nm; m++) {
+            const int j = r * l.nm + m;
+            e->fits[m] = fits[j];
+            SvtHipGmModelRecord* rec = e->models + m;
+            rec->num_inliers_kept = fits[j].num_inliers_kept;
+            rec->fit_wmtype = fits[j].wmtype;
+            for (int k = 0; k < 8; k++) rec->wmmat[k] = res[j].wmmat[k];
+            rec->wmtype = res[j].wmtype;
+            rec->best_error = res[j].best_error;
+        }
+        e->num_correspondences = fits[r * l.nm].npoints;
+        if (int rc = svt_hip_gm_decide_host(e->models, e->ref_frame_error, options->rotzoom_model_only, options->allow_high_precision_mv, e->wmmat, &e->wmtype)) return rc;
+    }
+    return SVT_HIP_OK;
 }
 
 /* ------------------------------------------------------------------------------------------- ME */

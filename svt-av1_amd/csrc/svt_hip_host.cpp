@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/svt_hip.h"
 #include "svt_hip_host.h"
+#include "gm_walk.h"
 
 extern "C" {
 
@@ -171,5 +172,121 @@ double svt_hip_tf_noise_sigma(int64_t sum, int64_t num) {   // EbTemporalFilteri
     return (double)sum / (6 * num) * 1.25331413732;
 }
 
+
+/* ------------------------------------------------------------------------------- global motion: the decision */
+// svt_aom_count_primitive_refsubexpfin (Encoder/Codec/EbEntropyCoding.c:3385-3401, :3430-3436, :3486-3533) with the reference's 16-bit parameter types
+static uint16_t gm_recenter_nonneg(uint16_t r, uint16_t v) {
+    if (v > (r << 1)) return v;
+    else if (v >= r) return (uint16_t)((v - r) << 1);
+    else return (uint16_t)(((r - v) << 1) - 1);
+}
+static uint16_t gm_recenter_finite_nonneg(uint16_t n, uint16_t r, uint16_t v) {
+    if ((r << 1) <= n) return gm_recenter_nonneg(r, v);
+    else return gm_recenter_nonneg((uint16_t)(n - 1 - r), (uint16_t)(n - 1 - v));
+}
+static int32_t gm_count_primitive_quniform(uint16_t n, uint16_t v) {
+    if (n <= 1) return 0;
+    const int32_t l = (31 - __builtin_clz((unsigned)(n - 1))) + 1;
+    const int32_t m = (1 << l) - n;
+    return v < m ? l - 1 : l;
+}
+static int32_t gm_count_primitive_subexpfin(uint16_t n, uint16_t k, uint16_t v) {
+    int32_t count = 0, i = 0, mk = 0;
+    while (1) {
+        const int32_t b = (i ? k + i - 1 : k);
+        const int32_t a = (1 << b);
+        if (n <= mk + 3 * a) {
+            count += gm_count_primitive_quniform((uint16_t)(n - mk), (uint16_t)(v - mk));
+            break;
+        } else {
+            const int32_t t = (v >= mk + a);
+            count++;
+            if (t) {
+                i = i + 1;
+                mk += a;
+            } else {
+                count += b;
+                break;
+            }
+        }
+    }
+    return count;
+}
+// aom_count_signed_primitive_refsubexpfin (Encoder/Codec/EbGlobalMotionEstimationCost.c:17-22): the int arguments narrow to int16_t at the call
+static int gm_count_signed_refsubexpfin(uint16_t n, uint16_t k, int16_t ref, int16_t v) {
+    ref = (int16_t)(ref + n - 1);
+    v = (int16_t)(v + n - 1);
+    const uint16_t scaled_n = (uint16_t)((n << 1) - 1);
+    return gm_count_primitive_subexpfin(scaled_n, k, gm_recenter_finite_nonneg(scaled_n, (uint16_t)ref, (uint16_t)v));
+}
+
+// gm_get_params_cost (EbGlobalMotionEstimationCost.c:25-75) against default_warp_params, the only ref_gm compute_global_motion passes
+int svt_hip_gm_params_cost_host(const int32_t wmmat[8], int wmtype, int allow_hp) {
+    if (!wmmat || wmtype < 0 || wmtype > 3) return -1;
+    const int32_t ref[8] = {0, 0, 1 << 16, 0, 0, 1 << 16, 0, 0};
+    const int kAlphaMax = 1 << 12, kK = 3, kAlphaBits = 15;
+    int params_cost = 0;
+    if (wmtype >= 2) {
+        params_cost += gm_count_signed_refsubexpfin((uint16_t)(kAlphaMax + 1), kK, (int16_t)((ref[2] >> 1) - (1 << kAlphaBits)), (int16_t)((wmmat[2] >> 1) - (1 << kAlphaBits)));
+        params_cost += gm_count_signed_refsubexpfin((uint16_t)(kAlphaMax + 1), kK, (int16_t)(ref[3] >> 1), (int16_t)(wmmat[3] >> 1));
+        if (wmtype >= 3) {
+            params_cost += gm_count_signed_refsubexpfin((uint16_t)(kAlphaMax + 1), kK, (int16_t)(ref[4] >> 1), (int16_t)(wmmat[4] >> 1));
+            params_cost += gm_count_signed_refsubexpfin((uint16_t)(kAlphaMax + 1), kK, (int16_t)((ref[5] >> 1) - (1 << kAlphaBits)), (int16_t)((wmmat[5] >> 1) - (1 << kAlphaBits)));
+        }
+    }
+    if (wmtype >= 1) {
+        const int trans_bits = (wmtype == 1) ? 9 - !allow_hp : 12;        // GM_ABS_TRANS_ONLY_BITS - !allow_hp : GM_ABS_TRANS_BITS
+        const int trans_prec_diff = (wmtype == 1) ? 13 + !allow_hp : 10;  // GM_TRANS_ONLY_PREC_DIFF + !allow_hp : GM_TRANS_PREC_DIFF
+        params_cost += gm_count_signed_refsubexpfin((uint16_t)((1 << trans_bits) + 1), kK, (int16_t)(ref[0] >> trans_prec_diff), (int16_t)(wmmat[0] >> trans_prec_diff));
+        params_cost += gm_count_signed_refsubexpfin((uint16_t)((1 << trans_bits) + 1), kK, (int16_t)(ref[1] >> trans_prec_diff), (int16_t)(wmmat[1] >> trans_prec_diff));
+    }
+    return params_cost << 9;   // AV1_PROB_COST_SHIFT
+}
+
+// The model loop of compute_global_motion (Encoder/Codec/EbGlobalMotionEstimation.c:303-399), statement by statement, on records instead of calls: an iteration
+// left by `continue` does not reset global_motion, so a ROTZOOM model on a pair whose frame error is 0 survives into (and out of) the AFFINE iteration untested.
+int svt_hip_gm_decide_host(const SvtHipGmModelRecord models[2], int64_t ref_frame_error, int rotzoom_model_only, int allow_high_precision_mv, int32_t wmmat_out[8],
+                           int32_t* wmtype_out) {
+    if (!models || !wmmat_out || !wmtype_out) return SVT_HIP_ERR_BAD_ARG;
+    const int32_t kDefault[8] = {0, 0, 1 << 16, 0, 0, 1 << 16, 0, 0};   // default_warp_params
+    int32_t gm[8], gm_type = 0;
+    for (int k = 0; k < 8; k++) gm[k] = kDefault[k];
+    for (int model = 2; model <= (rotzoom_model_only ? 2 : 3); ++model) {
+        const SvtHipGmModelRecord* rec = models + (model - 2);
+        int64_t best_warp_error = INT64_MAX;
+        if (rec->num_inliers_kept != 0 && rec->fit_wmtype != 0) {
+            const int64_t warp_error = rec->best_error;
+            if (warp_error < best_warp_error) {
+                best_warp_error = warp_error;
+                for (int k = 0; k < 8; k++) gm[k] = rec->wmmat[k];
+                gm_type = rec->wmtype;
+            }
+        }
+        if (gm_type <= 3) {
+            SvtHipGmModel shear;
+            gm_shear_params(gm, &shear);
+            if (!shear.valid) {
+                for (int k = 0; k < 8; k++) gm[k] = kDefault[k];
+                gm_type = 0;
+            }
+        }
+        if (gm_type == 1) {   // convert_to_trans_prec(allow_hp, .) * GM_TRANS_ONLY_DECODE_FACTOR
+            for (int k = 0; k < 2; k++)
+                gm[k] = (allow_high_precision_mv ? gm_round_signed(gm[k], 13) : gm_round_signed(gm[k], 14) * 2) * (1 << 13);
+        }
+        if (gm_type == 0) continue;
+        if (ref_frame_error == 0) continue;
+        const double adv = (double)best_warp_error / ref_frame_error;
+        const int cost = svt_hip_gm_params_cost_host(gm, gm_type, allow_high_precision_mv);
+        if (!(adv < 0.65 && adv * cost < 20000)) {   // svt_av1_is_enough_erroradvantage, GM_ERRORADV_TR_0
+            for (int k = 0; k < 8; k++) gm[k] = kDefault[k];
+            gm_type = 0;
+        }
+        if (gm_type != 0) break;
+    }
+    for (int k = 0; k < 8; k++) wmmat_out[k] = gm[k];
+    *wmtype_out = gm_type;
+    return SVT_HIP_OK;
+}
 
 }  // extern "C"

@@ -170,6 +170,10 @@ int svt_hip_launch_gm_cross_correlation(hipStream_t st, const uint8_t* im1, int 
                                         double* out);
 int svt_hip_launch_gm_correspondences(hipStream_t st, const uint8_t* src, int src_stride, int w, int h, const int* src_points, const int* src_count,
                                       const SvtHipGmRef* refs, int n_refs, const int* ref_points, const int* ref_counts, int max_points, int* corr, int* ncorr);
+/* gm_fit.hip */
+size_t svt_hip_gm_fit_scratch_layout_bytes(int njobs, int max_points);
+int svt_hip_launch_gm_fit(hipStream_t st, const int32_t* corr, const int32_t* ncorr, int max_points, const SvtHipGmFitJob* jobs, int njobs, int n_refinements,
+                          SvtHipGmFit* fits, int32_t* inliers, SvtHipGmJob* refine_jobs, void* scratch);
 /* per-call forms (percall.hip, cdef.hip, deblock.hip) */
 int svt_hip_launch_quantize_blocks(hipStream_t st, const int32_t* coeff, int n, int nblk, const SvtHipQuantParams* qp, const int16_t* iscan, int32_t* qcoeff,
                                    int32_t* dqcoeff, uint16_t* eob);
