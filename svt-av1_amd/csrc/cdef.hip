@@ -546,26 +546,6 @@ cdef_apply_kernel(const PIX* __restrict__ in, PIX* __restrict__ out, int stride,
     }
 }
 
-template <typename PIX>
-int search_t(hipStream_t st, const void* const rec[3], const int rs[3], const void* const src[3], const int ss[3], int w, int h,
-             const uint8_t* skip8, int pri_damping, int cs, uint64_t* mse, uint8_t* dir_buf, int32_t* var_buf) {
-    const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
-    hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rs[0], (const PIX*)src[0], ss[0], w, h,
-                       skip8, pri_damping, cs, mse, dir_buf, var_buf);
-    hipLaunchKernelGGL((cdef_search_chroma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[1], (const PIX*)rec[2], rs[1],
-                       (const PIX*)src[1], (const PIX*)src[2], ss[1], w, h, skip8, pri_damping, cs, mse + (size_t)nfb * 64, dir_buf);
-    return (int)hipGetLastError();
-}
-template <typename PIX>
-int apply_t(hipStream_t st, const void* const in[3], void* const out[3], const int stride[3], int w, int h, const uint8_t* skip8,
-            const uint8_t* ys, const uint8_t* uvs, int damping, int cs, uint8_t* dir_buf, const int32_t* var_in) {
-    const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
-    hipLaunchKernelGGL((cdef_apply_kernel<PIX, 0>), dim3(nfb), dim3(256), 0, st, (const PIX*)in[0], (PIX*)out[0], stride[0], w, h, skip8, ys, uvs, damping, cs, dir_buf, var_in);
-    for (int p = 1; p < 3; p++)
-        hipLaunchKernelGGL((cdef_apply_kernel<PIX, 1>), dim3(nfb), dim3(256), 0, st, (const PIX*)in[p], (PIX*)out[p], stride[p], w, h, skip8, ys, uvs, damping, cs, dir_buf, var_in);
-    return (int)hipGetLastError();
-}
-
 // ---- per-call forms (include/svt_hip_rtcd.h): svt_cdef_find_dir for a list of 8x8 blocks, svt_cdef_filter_block for a list of blocks, on the
 // 16-bit staging layout of the reference (CDEF_BSTRIDE rows, CDEF_VERY_LARGE outside the picture).  Same device functions as the frame kernels.
 __global__ void __launch_bounds__(64)
@@ -606,15 +586,30 @@ extern "C" int svt_hip_launch_cdef_search(hipStream_t st, int pix_bytes, const v
                                           const void* const src[3], const int src_stride[3], int w, int h, const uint8_t* skip8,
                                           int pri_damping, int bd, uint64_t* mse, uint8_t* dir_buf, int32_t* var_buf) {
     const int cs = bd - 8;
-    if (pix_bytes == 1) return search_t<uint8_t>(st, rec, rec_stride, src, src_stride, w, h, skip8, pri_damping, cs, mse, dir_buf, var_buf);
-    return search_t<uint16_t>(st, rec, rec_stride, src, src_stride, w, h, skip8, pri_damping, cs, mse, dir_buf, var_buf);
+    const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rec_stride[0], (const PIX*)src[0], src_stride[0], w, h, skip8,
+                           pri_damping, cs, mse, dir_buf, var_buf);
+        hipLaunchKernelGGL((cdef_search_chroma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[1], (const PIX*)rec[2], rec_stride[1], (const PIX*)src[1],
+                           (const PIX*)src[2], src_stride[1], w, h, skip8, pri_damping, cs, mse + (size_t)nfb * 64, dir_buf);
+    });
+    return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_cdef_apply(hipStream_t st, int pix_bytes, const void* const in[3], void* const out[3], const int stride[3],
                                          int w, int h, const uint8_t* skip8, const uint8_t* y_strength, const uint8_t* uv_strength,
                                          int damping, int bd, uint8_t* dir_buf, const int32_t* var_in) {
     const int cs = bd - 8;
-    if (pix_bytes == 1) return apply_t<uint8_t>(st, in, out, stride, w, h, skip8, y_strength, uv_strength, damping, cs, dir_buf, var_in);
-    return apply_t<uint16_t>(st, in, out, stride, w, h, skip8, y_strength, uv_strength, damping, cs, dir_buf, var_in);
+    const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((cdef_apply_kernel<PIX, 0>), dim3(nfb), dim3(256), 0, st, (const PIX*)in[0], (PIX*)out[0], stride[0], w, h, skip8, y_strength, uv_strength, damping, cs,
+                           dir_buf, var_in);
+        for (int p = 1; p < 3; p++)
+            hipLaunchKernelGGL((cdef_apply_kernel<PIX, 1>), dim3(nfb), dim3(256), 0, st, (const PIX*)in[p], (PIX*)out[p], stride[p], w, h, skip8, y_strength, uv_strength, damping,
+                               cs, dir_buf, var_in);
+    });
+    return (int)hipGetLastError();
 }
 
 SVT_HIP_TU_PROBE(cdef)

@@ -180,13 +180,11 @@ blend_a64_kernel(const PIX* __restrict__ src0, int src0_stride, const PIX* __res
 extern "C" int svt_hip_launch_compound_predict(hipStream_t st, int pix_bytes, int bd, const void* ref0, int ref0_stride, const void* ref1, int ref1_stride,
                                                void* dst, int dst_stride, uint8_t* masks, const SvtHipCompBlk* blks, int n) {
     if (n <= 0) return 0;
-#define LAUNCH(P, B) hipLaunchKernelGGL((compound_predict_kernel<P, B>), dim3(n), dim3(256), 0, st, (const P*)ref0, ref0_stride, (const P*)ref1, ref1_stride, \
-                                        (P*)dst, dst_stride, masks, blks)
-    if (pix_bytes == 1) LAUNCH(uint8_t, 8);
-    else if (bd == 8) LAUNCH(uint16_t, 8);
-    else if (bd == 10) LAUNCH(uint16_t, 10);
-    else LAUNCH(uint16_t, 12);
-#undef LAUNCH
+    svt_for_fmt12(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((compound_predict_kernel<PIX, decltype(f)::bd>), dim3(n), dim3(256), 0, st, (const PIX*)ref0, ref0_stride, (const PIX*)ref1, ref1_stride, (PIX*)dst,
+                           dst_stride, masks, blks);
+    });
     return (int)hipGetLastError();
 }
 
@@ -200,10 +198,10 @@ extern "C" int svt_hip_launch_obmc_cost(hipStream_t st, const uint8_t* pre, int 
 extern "C" int svt_hip_launch_blend_a64(hipStream_t st, int pix_bytes, const void* src0, int src0_stride, const void* src1, int src1_stride, void* dst, int dst_stride,
                                         const uint8_t* masks, const SvtHipBlendBlk* blks, int n) {
     if (n <= 0) return 0;
-    if (pix_bytes == 1) hipLaunchKernelGGL((blend_a64_kernel<uint8_t>), dim3(n), dim3(256), 0, st, (const uint8_t*)src0, src0_stride, (const uint8_t*)src1, src1_stride,
-                                           (uint8_t*)dst, dst_stride, masks, blks);
-    else hipLaunchKernelGGL((blend_a64_kernel<uint16_t>), dim3(n), dim3(256), 0, st, (const uint16_t*)src0, src0_stride, (const uint16_t*)src1, src1_stride, (uint16_t*)dst,
-                            dst_stride, masks, blks);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((blend_a64_kernel<PIX>), dim3(n), dim3(256), 0, st, (const PIX*)src0, src0_stride, (const PIX*)src1, src1_stride, (PIX*)dst, dst_stride, masks, blks);
+    });
     return (int)hipGetLastError();
 }
 

@@ -153,9 +153,10 @@ block_variance_kernel(const PIX* __restrict__ a, int a_stride, const PIX* __rest
 extern "C" int svt_hip_launch_subpel_predict(hipStream_t st, int pix_bytes, int bd, const void* ref, int ref_stride, void* dst,
                                              int dst_stride, const SvtHipConvBlk* blks, int n) {
     if (n <= 0) return 0;
-    if (pix_bytes == 1) hipLaunchKernelGGL((subpel_predict_kernel<uint8_t, 8>), dim3(n), dim3(256), 0, st, (const uint8_t*)ref, ref_stride, (uint8_t*)dst, dst_stride, blks);
-    else if (bd == 8) hipLaunchKernelGGL((subpel_predict_kernel<uint16_t, 8>), dim3(n), dim3(256), 0, st, (const uint16_t*)ref, ref_stride, (uint16_t*)dst, dst_stride, blks);
-    else hipLaunchKernelGGL((subpel_predict_kernel<uint16_t, 10>), dim3(n), dim3(256), 0, st, (const uint16_t*)ref, ref_stride, (uint16_t*)dst, dst_stride, blks);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((subpel_predict_kernel<PIX, decltype(f)::bd>), dim3(n), dim3(256), 0, st, (const PIX*)ref, ref_stride, (PIX*)dst, dst_stride, blks);
+    });
     return (int)hipGetLastError();
 }
 // The SvtHipConvBlk list of every whole 16x16 luma block from the open-loop ME table: block (bx, by) of the picture reads its integer vector from
@@ -184,13 +185,16 @@ extern "C" int svt_hip_launch_subpel_jobs_from_me(hipStream_t st, const uint32_t
 extern "C" int svt_hip_launch_block_sad(hipStream_t st, int pix_bytes, const void* a, int a_stride, const void* b, int b_stride,
                                         const SvtHipBlkPair* d, int n, uint32_t* out) {
     if (n <= 0) return 0;
-    if (pix_bytes == 1) hipLaunchKernelGGL((block_sad_kernel<uint8_t>), dim3(n), dim3(64), 0, st, (const uint8_t*)a, a_stride, (const uint8_t*)b, b_stride, d, out);
-    else hipLaunchKernelGGL((block_sad_kernel<uint16_t>), dim3(n), dim3(64), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, d, out);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((block_sad_kernel<PIX>), dim3(n), dim3(64), 0, st, (const PIX*)a, a_stride, (const PIX*)b, b_stride, d, out);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_block_variance(hipStream_t st, int pix_bytes, int bd, const void* a, int a_stride, const void* b, int b_stride,
                                              const SvtHipBlkPair* d, int n, uint32_t* var_out, uint32_t* sse_out) {
     if (n <= 0) return 0;
+    // a set of its own, (u8, 8) | (u16, 16) | (u16, 10): bd 16 is the reference's variance_highbd_c, no sample format of the other launchers
     if (pix_bytes == 1) hipLaunchKernelGGL((block_variance_kernel<uint8_t, 8>), dim3(n), dim3(64), 0, st, (const uint8_t*)a, a_stride, (const uint8_t*)b, b_stride, d, var_out, sse_out);
     else if (bd == 16) hipLaunchKernelGGL((block_variance_kernel<uint16_t, 16>), dim3(n), dim3(64), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, d, var_out, sse_out);
     else hipLaunchKernelGGL((block_variance_kernel<uint16_t, 10>), dim3(n), dim3(64), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, d, var_out, sse_out);

@@ -202,15 +202,6 @@ deblock_frame_pass_kernel(const DeblockFrame f, int sharpness) {
             s[(ptrdiff_t)(k - 1) * tap] = (PIX)px[6 + k];
         }
 }
-template <typename PIX, int BD>
-int launch_frame(hipStream_t st, const DeblockFrame& f, int sharp) {
-    int uw = 0, uh = 0;
-    for (int p = 0; p < 3; p++) { if (f.plane[p]) { uw = f.units_w[p] > uw ? f.units_w[p] : uw; uh = f.units_h[p] > uh ? f.units_h[p] : uh; } }
-    if (uw <= 0 || uh <= 0) return 0;
-    hipLaunchKernelGGL((deblock_frame_pass_kernel<PIX, BD, 0>), dim3((uw + 255) / 256, 4 * uh, 3), dim3(256), 0, st, f, sharp);
-    hipLaunchKernelGGL((deblock_frame_pass_kernel<PIX, BD, 1>), dim3((4 * uw + 255) / 256, uh, 3), dim3(256), 0, st, f, sharp);
-    return (int)hipGetLastError();
-}
 
 // ---- both directions of all three planes in ONE launch, out of place (EbDeblockingFilter.c:614 loop_filter_sb does both per superblock).
 // A workgroup owns a 128 x 64 tile of a plane.  Which samples decide a tile's result: a horizontal edge at row e reads the vertically filtered rows
@@ -324,25 +315,6 @@ deblock_fused_kernel(const DeblockFused f, int sharpness) {
         }
     }
 }
-template <typename PIX, int BD>
-int launch_fused(hipStream_t st, DeblockFused& f, int sharp) {
-    int n = 0;
-    for (int p = 0; p < 3; p++) {
-        f.tiles_x[p] = (f.pw[p] + kFW - 1) / kFW; f.tiles_y[p] = (f.ph[p] + kFH - 1) / kFH;
-        if (f.src[p]) n = f.tiles_x[p] * f.tiles_y[p] > n ? f.tiles_x[p] * f.tiles_y[p] : n;
-    }
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL((deblock_fused_kernel<PIX, BD>), dim3(n, 1, 3), dim3(256), 0, st, f, sharp);
-    return (int)hipGetLastError();
-}
-
-template <typename PIX, int BD>
-int launch_both(hipStream_t st, PIX* plane, int stride, const uint16_t* ev, const uint16_t* eh, int uw, int uh, int sharp, int lv_v, int lv_h) {
-    if (ev) hipLaunchKernelGGL((deblock_pass_kernel<PIX, BD, 0>), dim3((uw + 255) / 256, 4 * uh), dim3(256), 0, st, plane, stride, ev, uw, uh, sharp, lv_v);
-    if (eh) hipLaunchKernelGGL((deblock_pass_kernel<PIX, BD, 1>), dim3((4 * uw + 255) / 256, uh), dim3(256), 0, st, plane, stride, eh, uw, uh, sharp, lv_h);
-    return (int)hipGetLastError();
-}
-
 // svt_spatial_full_distortion_kernel_c / svt_full_distortion_kernel16_bits_c (Common/Codec/EbPictureOperators.c; called by
 // picture_sse_calculations, EbDeblockingFilter.c:830-961): sum of squared differences of two planes.  A workgroup owns 8 rows
 // of 1024 columns; lanes read 4 consecutive samples, u32 partials (<= 8 * 4 * 1023^2 < 2^32), one u64 atomic per wave.
@@ -412,9 +384,10 @@ __global__ void __launch_bounds__(256) dlf_build_edges_kernel(const EdgeBuild a)
 extern "C" int svt_hip_launch_lpf_edge_list(hipStream_t st, void* plane, int pix_bytes, int stride, int bd, const void* jobs, int n) {
     if (n <= 0) return 0;
     dim3 grid((n + 15) / 16);
-    if (pix_bytes == 1) hipLaunchKernelGGL((lpf_edge_list_kernel<uint8_t, 8>), grid, dim3(64), 0, st, (uint8_t*)plane, stride, (const SvtHipLpfEdge*)jobs, n);
-    else if (bd == 8) hipLaunchKernelGGL((lpf_edge_list_kernel<uint16_t, 8>), grid, dim3(64), 0, st, (uint16_t*)plane, stride, (const SvtHipLpfEdge*)jobs, n);
-    else hipLaunchKernelGGL((lpf_edge_list_kernel<uint16_t, 10>), grid, dim3(64), 0, st, (uint16_t*)plane, stride, (const SvtHipLpfEdge*)jobs, n);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((lpf_edge_list_kernel<PIX, decltype(f)::bd>), grid, dim3(64), 0, st, (PIX*)plane, stride, (const SvtHipLpfEdge*)jobs, n);
+    });
     return (int)hipGetLastError();
 }
 
@@ -422,18 +395,30 @@ extern "C" int svt_hip_launch_lpf_edge_list(hipStream_t st, void* plane, int pix
 extern "C" int svt_hip_launch_deblock_plane(hipStream_t st, void* plane, int pix_bytes, int stride, int bd, const uint16_t* edges_v,
                                             const uint16_t* edges_h, int units_w, int units_h, int sharpness, int level_v, int level_h) {
     if (units_w <= 0 || units_h <= 0) return 0;
-    if (pix_bytes == 1) return launch_both<uint8_t, 8>(st, (uint8_t*)plane, stride, edges_v, edges_h, units_w, units_h, sharpness, level_v, level_h);
-    if (bd == 8) return launch_both<uint16_t, 8>(st, (uint16_t*)plane, stride, edges_v, edges_h, units_w, units_h, sharpness, level_v, level_h);
-    return launch_both<uint16_t, 10>(st, (uint16_t*)plane, stride, edges_v, edges_h, units_w, units_h, sharpness, level_v, level_h);
+    const dim3 grid_v((units_w + 255) / 256, 4 * units_h), grid_h((4 * units_w + 255) / 256, units_h);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        constexpr int BD = decltype(f)::bd;
+        if (edges_v) hipLaunchKernelGGL((deblock_pass_kernel<PIX, BD, 0>), grid_v, dim3(256), 0, st, (PIX*)plane, stride, edges_v, units_w, units_h, sharpness, level_v);
+        if (edges_h) hipLaunchKernelGGL((deblock_pass_kernel<PIX, BD, 1>), grid_h, dim3(256), 0, st, (PIX*)plane, stride, edges_h, units_w, units_h, sharpness, level_h);
+    });
+    return (int)hipGetLastError();
 }
 
 extern "C" int svt_hip_launch_deblock_frame(hipStream_t st, void* const plane[3], int pix_bytes, const int stride[3], int bd, const uint16_t* const ev[3],
                                             const uint16_t* const eh[3], const int units_w[3], const int units_h[3], int sharpness) {
     DeblockFrame f;
     for (int p = 0; p < 3; p++) { f.plane[p] = plane[p]; f.stride[p] = stride[p]; f.ev[p] = ev[p]; f.eh[p] = eh[p]; f.units_w[p] = units_w[p]; f.units_h[p] = units_h[p]; }
-    if (pix_bytes == 1) return launch_frame<uint8_t, 8>(st, f, sharpness);
-    if (bd == 8) return launch_frame<uint16_t, 8>(st, f, sharpness);
-    return launch_frame<uint16_t, 10>(st, f, sharpness);
+    int uw = 0, uh = 0;
+    for (int p = 0; p < 3; p++) { if (f.plane[p]) { uw = f.units_w[p] > uw ? f.units_w[p] : uw; uh = f.units_h[p] > uh ? f.units_h[p] : uh; } }
+    if (uw <= 0 || uh <= 0) return 0;
+    svt_for_fmt(pix_bytes, bd, [&](auto t) {
+        using PIX = typename decltype(t)::pix;
+        constexpr int BD = decltype(t)::bd;
+        hipLaunchKernelGGL((deblock_frame_pass_kernel<PIX, BD, 0>), dim3((uw + 255) / 256, 4 * uh, 3), dim3(256), 0, st, f, sharpness);
+        hipLaunchKernelGGL((deblock_frame_pass_kernel<PIX, BD, 1>), dim3((4 * uw + 255) / 256, uh, 3), dim3(256), 0, st, f, sharpness);
+    });
+    return (int)hipGetLastError();
 }
 
 // *out must be zero before the launch (the caller enqueues the memset)
@@ -441,21 +426,26 @@ extern "C" int svt_hip_launch_plane_sse(hipStream_t st, int pix_bytes, const voi
                                         uint64_t* out) {
     if (w <= 0 || h <= 0) return 0;
     dim3 grid((w + 1023) / 1024, (h + 7) / 8);
-    if (pix_bytes == 1) hipLaunchKernelGGL((plane_sse_kernel<uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)a, a_stride, (const uint8_t*)b, b_stride, w, h, (unsigned long long*)out);
-    else hipLaunchKernelGGL((plane_sse_kernel<uint16_t>), grid, dim3(256), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, w, h, (unsigned long long*)out);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((plane_sse_kernel<PIX>), grid, dim3(256), 0, st, (const PIX*)a, a_stride, (const PIX*)b, b_stride, w, h, (unsigned long long*)out);
+    });
     return (int)hipGetLastError();
 }
 
 extern "C" int svt_hip_launch_deblock_fused(hipStream_t st, const void* const src[3], void* const dst[3], int pix_bytes, const int stride[3], int bd, const int pw[3],
                                             const int ph[3], const uint16_t* const ev[3], const uint16_t* const eh[3], const int units_w[3], const int units_h[3], int sharpness) {
     DeblockFused f;
+    int n = 0;
     for (int p = 0; p < 3; p++) {
         f.src[p] = src[p]; f.dst[p] = dst[p]; f.stride[p] = stride[p]; f.ev[p] = ev[p]; f.eh[p] = eh[p]; f.units_w[p] = units_w[p]; f.units_h[p] = units_h[p];
         f.pw[p] = pw[p]; f.ph[p] = ph[p];
+        f.tiles_x[p] = (f.pw[p] + kFW - 1) / kFW; f.tiles_y[p] = (f.ph[p] + kFH - 1) / kFH;
+        if (f.src[p]) n = f.tiles_x[p] * f.tiles_y[p] > n ? f.tiles_x[p] * f.tiles_y[p] : n;
     }
-    if (pix_bytes == 1) return launch_fused<uint8_t, 8>(st, f, sharpness);
-    if (bd == 8) return launch_fused<uint16_t, 8>(st, f, sharpness);
-    return launch_fused<uint16_t, 10>(st, f, sharpness);
+    if (n <= 0) return 0;
+    svt_for_fmt(pix_bytes, bd, [&](auto t) { hipLaunchKernelGGL((deblock_fused_kernel<typename decltype(t)::pix, decltype(t)::bd>), dim3(n, 1, 3), dim3(256), 0, st, f, sharpness); });
+    return (int)hipGetLastError();
 }
 
 SVT_HIP_TU_PROBE(deblock)

@@ -15,12 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-
 // out[blk][0] = sum (c - r)^2 (= sum c^2 when recon == nullptr), [1] = sum c^2, [2] = sum |c|
 __global__ void __launch_bounds__(256)
 coeff_distortion_kernel(const int32_t* __restrict__ coeff, const int32_t* __restrict__ recon, int n, int nblk, unsigned long long* __restrict__ out) {
@@ -85,12 +79,16 @@ extern "C" int svt_hip_launch_block_sse(hipStream_t st, int pix_bytes, const voi
     if (n <= 0) return 0;
     if (n <= 2048) {   // few pairs: probably large rectangles (restoration units) — row-sliced form; long lists are small blocks, one wave each
         if (hipMemsetAsync(out, 0, sizeof(uint64_t) * n, st) != hipSuccess) return (int)hipGetLastError();
-        if (pix_bytes == 1) hipLaunchKernelGGL((block_sse_rows_kernel<uint8_t>), dim3(n, 8), dim3(256), 0, st, (const uint8_t*)a, a_stride, (const uint8_t*)b, b_stride, pairs, (unsigned long long*)out);
-        else hipLaunchKernelGGL((block_sse_rows_kernel<uint16_t>), dim3(n, 8), dim3(256), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, pairs, (unsigned long long*)out);
+        svt_for_pix(pix_bytes, [&](auto f) {
+            using PIX = typename decltype(f)::pix;
+            hipLaunchKernelGGL((block_sse_rows_kernel<PIX>), dim3(n, 8), dim3(256), 0, st, (const PIX*)a, a_stride, (const PIX*)b, b_stride, pairs, (unsigned long long*)out);
+        });
         return (int)hipGetLastError();
     }
-    if (pix_bytes == 1) hipLaunchKernelGGL((block_sse_kernel<uint8_t>), dim3((n + 3) / 4), dim3(256), 0, st, (const uint8_t*)a, a_stride, (const uint8_t*)b, b_stride, pairs, n, (unsigned long long*)out);
-    else hipLaunchKernelGGL((block_sse_kernel<uint16_t>), dim3((n + 3) / 4), dim3(256), 0, st, (const uint16_t*)a, a_stride, (const uint16_t*)b, b_stride, pairs, n, (unsigned long long*)out);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((block_sse_kernel<PIX>), dim3((n + 3) / 4), dim3(256), 0, st, (const PIX*)a, a_stride, (const PIX*)b, b_stride, pairs, n, (unsigned long long*)out);
+    });
     return (int)hipGetLastError();
 }
 

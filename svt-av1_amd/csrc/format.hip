@@ -81,8 +81,10 @@ extern "C" int svt_hip_launch_picture_format(hipStream_t st, int mode, const voi
 extern "C" int svt_hip_launch_generate_padding(hipStream_t st, void* plane, int pix_bytes, int stride, int w, int h, int pad_w, int pad_h) {
     if (w <= 0 || h <= 0 || (pad_w <= 0 && pad_h <= 0)) return 0;
     const dim3 grid(min((w + 2 * pad_w + 255) / 256, 16), h + 2 * pad_h), block(256);
-    if (pix_bytes == 1) hipLaunchKernelGGL(generate_padding_kernel<uint8_t>, grid, block, 0, st, (uint8_t*)plane, stride, w, h, pad_w, pad_h);
-    else hipLaunchKernelGGL(generate_padding_kernel<uint16_t>, grid, block, 0, st, (uint16_t*)plane, stride, w, h, pad_w, pad_h);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(generate_padding_kernel<PIX>, grid, block, 0, st, (PIX*)plane, stride, w, h, pad_w, pad_h);
+    });
     return (int)hipGetLastError();
 }
 

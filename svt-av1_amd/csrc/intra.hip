@@ -234,8 +234,10 @@ extern "C" int svt_hip_launch_intra_ois(hipStream_t st, const uint8_t* src, int 
 extern "C" int svt_hip_launch_intra_predict(hipStream_t st, int pix_bytes, int bd, const void* edges, const SvtHipIntraJob* jobs, int njobs, void* dst,
                                             int dst_stride) {
     if (njobs <= 0) return 0;
-    if (pix_bytes == 1) hipLaunchKernelGGL(intra_predict_batch_kernel<uint8_t>, dim3(njobs), dim3(256), 0, st, (const uint8_t*)edges, jobs, bd, (uint8_t*)dst, dst_stride);
-    else hipLaunchKernelGGL(intra_predict_batch_kernel<uint16_t>, dim3(njobs), dim3(256), 0, st, (const uint16_t*)edges, jobs, bd, (uint16_t*)dst, dst_stride);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(intra_predict_batch_kernel<PIX>, dim3(njobs), dim3(256), 0, st, (const PIX*)edges, jobs, bd, (PIX*)dst, dst_stride);
+    });
     return (int)hipGetLastError();
 }
 

@@ -289,12 +289,11 @@ extern "C" int svt_hip_launch_cfl_predict(hipStream_t st, int pix_bytes, int bd,
                                           int njobs, void* cb, void* cr, int chroma_stride, int16_t* ac) {
     if (njobs <= 0) return 0;
     const dim3 grid((njobs + WG_JOBS - 1) / WG_JOBS), block(64 * WG_WAVES);
-    if (pix_bytes == 1)
-        hipLaunchKernelGGL(cfl_predict_batch_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)luma, luma_stride, (const uint8_t*)edges, jobs, njobs, bd, (uint8_t*)cb,
-                           (uint8_t*)cr, chroma_stride, ac);
-    else
-        hipLaunchKernelGGL(cfl_predict_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)luma, luma_stride, (const uint16_t*)edges, jobs, njobs, bd,
-                           (uint16_t*)cb, (uint16_t*)cr, chroma_stride, ac);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(cfl_predict_batch_kernel<PIX>, grid, block, 0, st, (const PIX*)luma, luma_stride, (const PIX*)edges, jobs, njobs, bd, (PIX*)cb, (PIX*)cr,
+                           chroma_stride, ac);
+    });
     return (int)hipGetLastError();
 }
 
@@ -302,10 +301,10 @@ extern "C" int svt_hip_launch_filter_intra_predict(hipStream_t st, int pix_bytes
                                                    int dst_stride) {
     if (njobs <= 0) return 0;
     const dim3 grid((njobs + WG_JOBS - 1) / WG_JOBS), block(64 * WG_WAVES);
-    if (pix_bytes == 1)
-        hipLaunchKernelGGL(filter_intra_batch_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)edges, jobs, njobs, bd, (uint8_t*)dst, dst_stride);
-    else
-        hipLaunchKernelGGL(filter_intra_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)edges, jobs, njobs, bd, (uint16_t*)dst, dst_stride);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(filter_intra_batch_kernel<PIX>, grid, block, 0, st, (const PIX*)edges, jobs, njobs, bd, (PIX*)dst, dst_stride);
+    });
     return (int)hipGetLastError();
 }
 

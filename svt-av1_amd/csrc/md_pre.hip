@@ -289,6 +289,15 @@ md_subpel_grid_kernel(const uint8_t* __restrict__ src, int src_stride, int pic_w
     }
 }
 
+// the by-value kernel arguments of a launch: every slot filled, the ones past the count with entry 0
+void fill_lists(const SvtHipMdRefPlane* refs, int n_refs, const SvtHipMdPu* pus, int n_pus, RefPlanes& rp, PuList& pl) {
+    for (int i = 0; i < SVT_HIP_MD_MAX_REFS; i++) rp.r[i] = refs[i < n_refs ? i : 0];
+    for (int i = 0; i < SVT_HIP_MD_MAX_PUS; i++) {
+        const SvtHipMdPu p = pus[i < n_pus ? i : 0];
+        pl.x[i] = p.x; pl.y[i] = p.y; pl.w[i] = p.w; pl.h[i] = p.h;
+    }
+}
+
 }   // namespace
 
 extern "C" int svt_hip_launch_md_fullpel_sad(hipStream_t st, int pix_bytes, const void* src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus,
@@ -296,13 +305,11 @@ extern "C" int svt_hip_launch_md_fullpel_sad(hipStream_t st, int pix_bytes, cons
     if (n_sb <= 0 || n_refs <= 0 || n_pus <= 0) return 0;
     RefPlanes rp;
     PuList    pl;
-    for (int i = 0; i < SVT_HIP_MD_MAX_REFS; i++) rp.r[i] = refs[i < n_refs ? i : 0];
-    for (int i = 0; i < SVT_HIP_MD_MAX_PUS; i++) {
-        const SvtHipMdPu p = pus[i < n_pus ? i : 0];
-        pl.x[i] = p.x; pl.y[i] = p.y; pl.w[i] = p.w; pl.h[i] = p.h;
-    }
-    if (pix_bytes == 2) hipLaunchKernelGGL(md_fullpel_sad_kernel<uint16_t>, dim3(n_sb, n_refs), dim3(256), 0, st, (const uint16_t*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, mv, sad);
-    else hipLaunchKernelGGL(md_fullpel_sad_kernel<uint8_t>, dim3(n_sb, n_refs), dim3(256), 0, st, (const uint8_t*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, mv, sad);
+    fill_lists(refs, n_refs, pus, n_pus, rp, pl);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(md_fullpel_sad_kernel<PIX>, dim3(n_sb, n_refs), dim3(256), 0, st, (const PIX*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, mv, sad);
+    });
     return (int)hipGetLastError();
 }
 
@@ -312,14 +319,12 @@ extern "C" int svt_hip_launch_md_fullpel_avg_sad(hipStream_t st, int pix_bytes, 
     RefPlanes rp;
     PuList    pl;
     PairList  pp;
-    for (int i = 0; i < SVT_HIP_MD_MAX_REFS; i++) rp.r[i] = refs[i < n_refs ? i : 0];
-    for (int i = 0; i < SVT_HIP_MD_MAX_PUS; i++) {
-        const SvtHipMdPu p = pus[i < n_pus ? i : 0];
-        pl.x[i] = p.x; pl.y[i] = p.y; pl.w[i] = p.w; pl.h[i] = p.h;
-    }
+    fill_lists(refs, n_refs, pus, n_pus, rp, pl);
     for (int i = 0; i < SVT_HIP_MD_MAX_PAIRS; i++) { pp.c0[i] = pairs[i < n_pairs ? i : 0][0]; pp.c1[i] = pairs[i < n_pairs ? i : 0][1]; }
-    if (pix_bytes == 2) hipLaunchKernelGGL(md_fullpel_avg_sad_kernel<uint16_t>, dim3(n_sb, n_pairs), dim3(256), 0, st, (const uint16_t*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, n_pairs, pp, mv, sad);
-    else hipLaunchKernelGGL(md_fullpel_avg_sad_kernel<uint8_t>, dim3(n_sb, n_pairs), dim3(256), 0, st, (const uint8_t*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, n_pairs, pp, mv, sad);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(md_fullpel_avg_sad_kernel<PIX>, dim3(n_sb, n_pairs), dim3(256), 0, st, (const PIX*)src, src_stride, pic_w, pic_h, sb_cols, n_pus, n_refs, rp, pl, n_pairs, pp, mv, sad);
+    });
     return (int)hipGetLastError();
 }
 
@@ -328,11 +333,7 @@ extern "C" int svt_hip_launch_md_subpel_grid(hipStream_t st, const uint8_t* src,
     if (n_sb <= 0 || n_refs <= 0 || n_pus <= 0) return 0;
     RefPlanes rp;
     PuList    pl;
-    for (int i = 0; i < SVT_HIP_MD_MAX_REFS; i++) rp.r[i] = refs[i < n_refs ? i : 0];
-    for (int i = 0; i < SVT_HIP_MD_MAX_PUS; i++) {
-        const SvtHipMdPu p = pus[i < n_pus ? i : 0];
-        pl.x[i] = p.x; pl.y[i] = p.y; pl.w[i] = p.w; pl.h[i] = p.h;
-    }
+    fill_lists(refs, n_refs, pus, n_pus, rp, pl);
     PuSel small, large;   // PUs up to 16 wide: one wave each; the rest (and the ones the kernel declines: it writes their "not computed" pairs): four waves
     int   n_small = 0, n_large = 0;
     for (int i = 0; i < n_pus; i++) {

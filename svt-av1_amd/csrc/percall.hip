@@ -274,8 +274,10 @@ int svt_hip_launch_quantize_blocks(hipStream_t st, const int32_t* coeff, int n, 
 int svt_hip_launch_residual(hipStream_t st, int pix_bytes, const void* src, int ss, const void* pred, int ps, int16_t* res, int rs, int w, int h) {
     if (w <= 0 || h <= 0) return 0;
     dim3 grid((w + 63) / 64, (h + 3) / 4);
-    if (pix_bytes == 1) hipLaunchKernelGGL((residual_kernel<uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)src, ss, (const uint8_t*)pred, ps, res, rs, w, h);
-    else hipLaunchKernelGGL((residual_kernel<uint16_t>), grid, dim3(256), 0, st, (const uint16_t*)src, ss, (const uint16_t*)pred, ps, res, rs, w, h);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((residual_kernel<PIX>), grid, dim3(256), 0, st, (const PIX*)src, ss, (const PIX*)pred, ps, res, rs, w, h);
+    });
     return (int)hipGetLastError();
 }
 int svt_hip_launch_ext_all_sad(hipStream_t st, const uint8_t* src, int ss, const uint8_t* ref, int rs, const void* jobs, int n, uint32_t* state) {
@@ -312,8 +314,10 @@ int svt_hip_launch_upsampled_pred(hipStream_t st, const uint8_t* ref, int rs, ui
 }
 int svt_hip_launch_iwht4x4_add(hipStream_t st, int pix_bytes, int bd, const int32_t* dq, const uint16_t* eob, const void* pred, int ps, void* recon, int rs, const uint32_t* descs, int n) {
     if (n <= 0) return 0;
-    if (pix_bytes == 1) hipLaunchKernelGGL((iwht4x4_add_kernel<uint8_t>), dim3((n + 63) / 64), dim3(64), 0, st, dq, eob, (const uint8_t*)pred, ps, (uint8_t*)recon, rs, descs, n, bd);
-    else hipLaunchKernelGGL((iwht4x4_add_kernel<uint16_t>), dim3((n + 63) / 64), dim3(64), 0, st, dq, eob, (const uint16_t*)pred, ps, (uint16_t*)recon, rs, descs, n, bd);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((iwht4x4_add_kernel<PIX>), dim3((n + 63) / 64), dim3(64), 0, st, dq, eob, (const PIX*)pred, ps, (PIX*)recon, rs, descs, n, bd);
+    });
     return (int)hipGetLastError();
 }
 }

@@ -24,12 +24,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1)
-        v += ((unsigned long long)(unsigned)__shfl_xor((int)(v >> 32), m, 64) << 32) | (unsigned)__shfl_xor((int)v, m, 64);
-    return v;
-}
 __device__ __forceinline__ long long wave_sum_i64(long long v) { return (long long)wave_sum_u64((unsigned long long)v); }
 __device__ __forceinline__ int clip_px(int v, int bd) { const int mx = (1 << bd) - 1; return v < 0 ? 0 : (v > mx ? mx : v); }
 
@@ -934,24 +928,30 @@ blend_d16_kernel(PIX* __restrict__ dst, int ds, const uint16_t* __restrict__ s0,
 extern "C" int svt_hip_launch_diffwtd_mask(hipStream_t st, int elem_bytes, uint8_t* mask, const void* a, int as, const void* b, int bs, int w, int h, int inverse, int round,
                                            int shift) {
     const dim3 grid((w * h + 255) / 256);
-    if (elem_bytes == 1) hipLaunchKernelGGL(diffwtd_mask_kernel<uint8_t>, grid, dim3(256), 0, st, mask, (const uint8_t*)a, as, (const uint8_t*)b, bs, w, h, inverse, round, shift);
-    else hipLaunchKernelGGL(diffwtd_mask_kernel<uint16_t>, grid, dim3(256), 0, st, mask, (const uint16_t*)a, as, (const uint16_t*)b, bs, w, h, inverse, round, shift);
+    svt_for_pix(elem_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(diffwtd_mask_kernel<PIX>, grid, dim3(256), 0, st, mask, (const PIX*)a, as, (const PIX*)b, bs, w, h, inverse, round, shift);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_blend_d16(hipStream_t st, int pix_bytes, int bd, void* dst, int ds, const uint16_t* s0, int s0s, const uint16_t* s1, int s1s, const uint8_t* mask,
                                         int ms, int w, int h, int subw, int subh, int round0, int round1) {
     const dim3 grid((w + 63) / 64, (h + 3) / 4);
     const int  b = pix_bytes == 1 ? 8 : bd, offset_bits = b + 14 - round0, round_offset = (1 << (offset_bits - round1)) + (1 << (offset_bits - round1 - 1));
-    if (pix_bytes == 1) hipLaunchKernelGGL(blend_d16_kernel<uint8_t>, grid, dim3(256), 0, st, (uint8_t*)dst, ds, s0, s0s, s1, s1s, mask, ms, w, h, subw, subh, round_offset, 14 - round0 - round1, b);
-    else hipLaunchKernelGGL(blend_d16_kernel<uint16_t>, grid, dim3(256), 0, st, (uint16_t*)dst, ds, s0, s0s, s1, s1s, mask, ms, w, h, subw, subh, round_offset, 14 - round0 - round1, b);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(blend_d16_kernel<PIX>, grid, dim3(256), 0, st, (PIX*)dst, ds, s0, s0s, s1, s1s, mask, ms, w, h, subw, subh, round_offset, 14 - round0 - round1, b);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_jnt_convolve(hipStream_t st, int pix_bytes, int bd, int variant, const void* src, int ss, void* dst, int ds, uint16_t* cb, int cbs,
                                            const int16_t* taps, int w, int h, int round0, int round1, int do_average, int use_jnt, int fwd, int bck) {
     const dim3    grid((w + 63) / 64, (h + 3) / 4);
     const JntArgs a = {variant, w, h, round0, round1, do_average, use_jnt, fwd, bck, pix_bytes == 1 ? 8 : bd};
-    if (pix_bytes == 1) hipLaunchKernelGGL(jnt_convolve_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)src, ss, (uint8_t*)dst, ds, cb, cbs, taps, a);
-    else hipLaunchKernelGGL(jnt_convolve_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)src, ss, (uint16_t*)dst, ds, cb, cbs, taps, a);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(jnt_convolve_kernel<PIX>, grid, dim3(256), 0, st, (const PIX*)src, ss, (PIX*)dst, ds, cb, cbs, taps, a);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_repack64(hipStream_t st, int32_t* coeff, int rows, int per_block, int nblk) {
@@ -976,8 +976,10 @@ extern "C" int svt_hip_launch_ext_sad_32_64(hipStream_t st, uint32_t* state, con
 }
 extern "C" int svt_hip_launch_cdef_dist(hipStream_t st, int pix_bytes, const void* dst, int dstride, const void* src, const uint8_t* list, int n, int bw_log2, int bh_log2,
                                         int cs, int pli, uint64_t* out) {
-    if (pix_bytes == 1) hipLaunchKernelGGL(cdef_dist_kernel<uint8_t>, dim3(1), dim3(256), 0, st, (const uint8_t*)dst, dstride, (const uint8_t*)src, list, n, bw_log2, bh_log2, cs, pli, out);
-    else hipLaunchKernelGGL(cdef_dist_kernel<uint16_t>, dim3(1), dim3(256), 0, st, (const uint16_t*)dst, dstride, (const uint16_t*)src, list, n, bw_log2, bh_log2, cs, pli, out);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(cdef_dist_kernel<PIX>, dim3(1), dim3(256), 0, st, (const PIX*)dst, dstride, (const PIX*)src, list, n, bw_log2, bh_log2, cs, pli, out);
+    });
     return (int)hipGetLastError();
 }
 static int one_dual_step(hipStream_t st, const uint64_t* mse0, const uint64_t* mse1, int sb_count, int* lev0, int* lev1, int nb, int start_gi, int end_gi, uint64_t* best,
@@ -1062,10 +1064,10 @@ extern "C" int svt_hip_launch_strength_select_multi(hipStream_t st, int n_pics, 
 extern "C" int svt_hip_launch_sgr_flt_proj(hipStream_t st, int pix_bytes, const void* src, int ss, const void* dat, int ds, const int32_t* f0, int f0s, const int32_t* f1, int f1s,
                                            int w, int h, int r0, int r1, int mode, int xq0, int xq1, long long* acc, int32_t* xq_out) {
     const int blocks = h < 256 ? h : 256;
-    if (pix_bytes == 1)
-        hipLaunchKernelGGL(sgr_flt_proj_kernel<uint8_t>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)src, ss, (const uint8_t*)dat, ds, f0, f0s, f1, f1s, w, h, r0, r1, mode, xq0, xq1, acc);
-    else
-        hipLaunchKernelGGL(sgr_flt_proj_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, (const uint16_t*)src, ss, (const uint16_t*)dat, ds, f0, f0s, f1, f1s, w, h, r0, r1, mode, xq0, xq1, acc);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(sgr_flt_proj_kernel<PIX>, dim3(blocks), dim3(256), 0, st, (const PIX*)src, ss, (const PIX*)dat, ds, f0, f0s, f1, f1s, w, h, r0, r1, mode, xq0, xq1, acc);
+    });
     if (mode == 0) hipLaunchKernelGGL(sgr_flt_solve_kernel, dim3(1), dim3(1), 0, st, acc, w * h, r0, r1, xq_out);
     return (int)hipGetLastError();
 }
@@ -1078,8 +1080,11 @@ extern "C" int svt_hip_launch_convolve8(hipStream_t st, int vert, const uint8_t*
 extern "C" int svt_hip_launch_wiener_convolve(hipStream_t st, int pix_bytes, int bd, const void* src, int ss, void* dst, int ds, const int16_t* taps, int w, int h, int round0,
                                               int round1) {
     const dim3 grid((w + 63) / 64, (h + 3) / 4);
-    if (pix_bytes == 1) hipLaunchKernelGGL(wiener_convolve_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)src, ss, (uint8_t*)dst, ds, taps, w, h, round0, round1, 8);
-    else hipLaunchKernelGGL(wiener_convolve_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)src, ss, (uint16_t*)dst, ds, taps, w, h, round0, round1, bd);
+    const int b = pix_bytes == 1 ? 8 : bd;
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(wiener_convolve_kernel<PIX>, grid, dim3(256), 0, st, (const PIX*)src, ss, (PIX*)dst, ds, taps, w, h, round0, round1, b);
+    });
     return (int)hipGetLastError();
 }
 

@@ -1247,18 +1247,17 @@ extern "C" int svt_hip_launch_wiener_walk_multi(hipStream_t st, int pix_bytes, i
             }
     }
     if (fits) hipLaunchKernelGGL(wiener_walk8w_kernel, grid, dim3(1024), 0, st, a);
-    else if (pix_bytes == 1) hipLaunchKernelGGL((wiener_walk_kernel<uint8_t, 8>), grid, dim3(1024), 0, st, a);
-    else if (bd == 8) hipLaunchKernelGGL((wiener_walk_kernel<uint16_t, 8>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((wiener_walk_kernel<uint16_t, 10>), grid, dim3(1024), 0, st, a);
+    else svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((wiener_walk_kernel<typename decltype(f)::pix, decltype(f)::bd>), grid, dim3(1024), 0, st, a); });
     return (int)hipGetLastError();
 }
 
 extern "C" int svt_hip_launch_sgr_filter(hipStream_t st, int pix_bytes, int bd, const void* plane, int stride, int pw, int ph, int ep,
                                          int32_t* flt0, int32_t* flt1, int flt_stride) {
     dim3 grid((pw + 63) / 64, (ph + 15) / 16);
-    if (pix_bytes == 1) hipLaunchKernelGGL((sgr_filter_kernel<uint8_t, 8>), grid, dim3(256), 0, st, (const uint8_t*)plane, stride, pw, ph, ep, flt0, flt1, flt_stride);
-    else if (bd == 8) hipLaunchKernelGGL((sgr_filter_kernel<uint16_t, 8>), grid, dim3(256), 0, st, (const uint16_t*)plane, stride, pw, ph, ep, flt0, flt1, flt_stride);
-    else hipLaunchKernelGGL((sgr_filter_kernel<uint16_t, 10>), grid, dim3(256), 0, st, (const uint16_t*)plane, stride, pw, ph, ep, flt0, flt1, flt_stride);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((sgr_filter_kernel<PIX, decltype(f)::bd>), grid, dim3(256), 0, st, (const PIX*)plane, stride, pw, ph, ep, flt0, flt1, flt_stride);
+    });
     return (int)hipGetLastError();
 }
 namespace {
@@ -1273,12 +1272,10 @@ SgrSearchPlaneArgs sgr_search_plane_args(const void* dgd, int stride, const void
 template <int STORE>
 int sgr_search_launch(hipStream_t st, int pix_bytes, int bd, const SgrSearchPic& a) {
     const dim3 grid((unsigned)a.first_tile[kSgrMaxPlanes]);
-    if (STORE == 2) {
-        if (pix_bytes == 1) hipLaunchKernelGGL((sgr_search8_kernel<uint8_t, 8, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((sgr_search8_kernel<uint16_t, 8, 2>), grid, dim3(256), 0, st, a);
-    } else if (pix_bytes == 1) hipLaunchKernelGGL((sgr_search8_kernel<uint8_t, 8, STORE == 2 ? 1 : STORE>), grid, dim3(256), 0, st, a);
-    else if (bd == 8) hipLaunchKernelGGL((sgr_search8_kernel<uint16_t, 8, STORE == 2 ? 1 : STORE>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((sgr_search8_kernel<uint16_t, 10, STORE == 2 ? 1 : STORE>), grid, dim3(256), 0, st, a);
+    if constexpr (STORE == 2)   // the packed words exist at bit depth 8 only (the launcher below refuses the rest)
+        svt_for_pix(pix_bytes, [&](auto f) { hipLaunchKernelGGL((sgr_search8_kernel<typename decltype(f)::pix, 8, 2>), grid, dim3(256), 0, st, a); });
+    else
+        svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((sgr_search8_kernel<typename decltype(f)::pix, decltype(f)::bd, STORE>), grid, dim3(256), 0, st, a); });
     return (int)hipGetLastError();
 }
 int sgr_esc_lim() {
@@ -1324,9 +1321,11 @@ extern "C" int svt_hip_launch_sgr_proj_error(hipStream_t st, int pix_bytes, int 
     dim3 grid8((pw + S_TW - 1) / S_TW, (ph + voff + S_TH - 1) / S_TH);
     unsigned long long* e = (unsigned long long*)err;
     if (ncand < 1 || ncand > kSgrMaxCand) return (int)hipErrorInvalidValue;
-    if (pix_bytes == 1) hipLaunchKernelGGL((sgr_proj_error_kernel<uint8_t, 8>), grid8, dim3(256), 0, st, (const uint8_t*)dgd, stride, (const uint8_t*)src, src_stride, pw, ph, unit_size, units_x, units_y, voff, ep_mask, ncand, xqd, e);
-    else if (bd == 8) hipLaunchKernelGGL((sgr_proj_error_kernel<uint16_t, 8>), grid8, dim3(256), 0, st, (const uint16_t*)dgd, stride, (const uint16_t*)src, src_stride, pw, ph, unit_size, units_x, units_y, voff, ep_mask, ncand, xqd, e);
-    else hipLaunchKernelGGL((sgr_proj_error_kernel<uint16_t, 10>), grid8, dim3(256), 0, st, (const uint16_t*)dgd, stride, (const uint16_t*)src, src_stride, pw, ph, unit_size, units_x, units_y, voff, ep_mask, ncand, xqd, e);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((sgr_proj_error_kernel<PIX, decltype(f)::bd>), grid8, dim3(256), 0, st, (const PIX*)dgd, stride, (const PIX*)src, src_stride, pw, ph, unit_size, units_x,
+                           units_y, voff, ep_mask, ncand, xqd, e);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_sgr_apply_tiles(hipStream_t st, int pix_bytes, int bd, const void* dgd, int stride, void* dst, int dst_stride, int pw,
@@ -1335,9 +1334,11 @@ extern "C" int svt_hip_launch_sgr_apply_tiles(hipStream_t st, int pix_bytes, int
     const int voff = 8 >> ss_y, sh = 64 >> ss_y;
     if (ntx <= 0 || nty <= 0) return 0;
     dim3 grid8(ntx, nty);
-    if (pix_bytes == 1) hipLaunchKernelGGL((lr_apply8_kernel<uint8_t>), grid8, dim3(256), 0, st, (const uint8_t*)dgd, stride, (uint8_t*)dst, dst_stride, pw, ph, unit_size, units_x, units_y, voff, sh, (const uint8_t*)dbl, dbl_stride, unit_ep, unit_xqd, unit_wiener, tx0, ty0);
-    else if (bd == 8) hipLaunchKernelGGL((lr_apply8_kernel<uint16_t>), grid8, dim3(256), 0, st, (const uint16_t*)dgd, stride, (uint16_t*)dst, dst_stride, pw, ph, unit_size, units_x, units_y, voff, sh, (const uint16_t*)dbl, dbl_stride, unit_ep, unit_xqd, unit_wiener, tx0, ty0);
-    else hipLaunchKernelGGL((lr_apply8_kernel<uint16_t, 10>), grid8, dim3(256), 0, st, (const uint16_t*)dgd, stride, (uint16_t*)dst, dst_stride, pw, ph, unit_size, units_x, units_y, voff, sh, (const uint16_t*)dbl, dbl_stride, unit_ep, unit_xqd, unit_wiener, tx0, ty0);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((lr_apply8_kernel<PIX, decltype(f)::bd>), grid8, dim3(256), 0, st, (const PIX*)dgd, stride, (PIX*)dst, dst_stride, pw, ph, unit_size, units_x, units_y, voff,
+                           sh, (const PIX*)dbl, dbl_stride, unit_ep, unit_xqd, unit_wiener, tx0, ty0);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_sgr_apply(hipStream_t st, int pix_bytes, int bd, const void* dgd, int stride, void* dst, int dst_stride, int pw,

@@ -50,6 +50,12 @@ int bad_arg(SvtHipCtx* c, const char* msg = nullptr) {
 int launched(SvtHipCtx* c, int rc, const char* what) { return rc == hipSuccess ? SVT_HIP_OK : fail(c, (hipError_t)rc, what); }
 // 8-bit samples in bytes, 8- or 10-bit samples in 16-bit words
 bool fmt_ok(int pix_bytes, int bd) { return (pix_bytes == 1 || pix_bytes == 2) && (bd == 8 || bd == 10) && !(pix_bytes == 1 && bd != 8); }
+// the sample size alone (entry points whose kernels take no bit depth, or take it as a value)
+bool pix_ok(int pix_bytes) { return pix_bytes == 1 || pix_bytes == 2; }
+// ... 8-, 10- or 12-bit samples in 16-bit words: the kernels with a 12-bit instance
+bool fmt12_ok(int pix_bytes, int bd) { return (pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && (bd == 8 || bd == 10 || bd == 12)); }
+// ... any depth from 8 to 12 in 16-bit words (9 and 11 too): the kernels that take the bit depth as a value
+bool fmt_8to12_ok(int pix_bytes, int bd) { return (pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && bd >= 8 && bd <= 12); }
 }  // namespace
 #define HIPCHK(c, call)                                   \
     do {                                                  \
@@ -688,7 +694,7 @@ int svt_hip_fwd_txfm_quant_batch_dev(SvtHipCtx* c, int tx_size, int pix_bytes, c
                                      int32_t* d_qcoeff, int32_t* d_dqcoeff, uint16_t* d_eob, int32_t* d_cul_level,
                                      uint64_t* d_energy) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_src || !d_pred || !d_descs || nblk < 0 || tx_size < 0 || tx_size > 18 || (pix_bytes != 1 && pix_bytes != 2) ||
+    if (!c || !d_src || !d_pred || !d_descs || nblk < 0 || tx_size < 0 || tx_size > 18 || !pix_ok(pix_bytes) ||
         ((d_qcoeff != nullptr) != (d_dqcoeff != nullptr)) || (d_qcoeff && (!qp || !scans || !scans->iscan[0])) || (qp && !quant_ok(*qp)))
         return bad_arg(c, "svt_hip_fwd_txfm_quant_batch_dev: bad argument");
     return launched(c, svt_hip_launch_fwd_txfm_quant(c->stream, tx_size, pix_bytes, d_src, src_stride, d_pred, pred_stride, d_descs, nblk, qp, scans, d_coeff, d_qcoeff,
@@ -763,7 +769,7 @@ int svt_hip_dlf_build_edges_picture_dev(SvtHipCtx* c, const SvtHipDlfModeInfo* d
 int svt_hip_plane_sse_dev(SvtHipCtx* c, int pix_bytes, const void* d_a, int a_stride, const void* d_b, int b_stride, int w, int h,
                           uint64_t* d_sse) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_a || !d_b || !d_sse || (pix_bytes != 1 && pix_bytes != 2) || w <= 0 || h <= 0) return bad_arg(c, "svt_hip_plane_sse_dev: bad argument");
+    if (!c || !d_a || !d_b || !d_sse || !pix_ok(pix_bytes) || w <= 0 || h <= 0) return bad_arg(c, "svt_hip_plane_sse_dev: bad argument");
     HIPCHK(c, hipMemsetAsync(d_sse, 0, sizeof(uint64_t), c->stream));
     return launched(c, svt_hip_launch_plane_sse(c->stream, pix_bytes, d_a, a_stride, d_b, b_stride, w, h, d_sse), "plane sse launch");
 }
@@ -841,7 +847,7 @@ int svt_hip_dlf_search_levels_picture_dev(SvtHipCtx* c, int n_planes, const SvtH
 
 int svt_hip_fwd_txfm_quant_multi_dev(SvtHipCtx* c, int pix_bytes, const SvtHipFwdTxJob* jobs, int njobs) {
     SVT_HIP_ENTER(c);
-    if (!c || (!jobs && njobs) || njobs < 0 || (pix_bytes != 1 && pix_bytes != 2)) return bad_arg(c);
+    if (!c || (!jobs && njobs) || njobs < 0 || !pix_ok(pix_bytes)) return bad_arg(c);
     for (int j = 0; j < njobs; j++) {
         const SvtHipFwdTxJob& J = jobs[j];
         if (J.nblk < 0 || J.tx_size < 0 || J.tx_size > 18 || (J.nblk && (!J.d_src || !J.d_pred || !J.d_descs)) || ((J.d_qcoeff != nullptr) != (J.d_dqcoeff != nullptr)) ||
@@ -907,7 +913,7 @@ int svt_hip_subpel_jobs_from_me_dev(SvtHipCtx* c, const uint32_t* d_best_mv, int
 int svt_hip_block_sad_batch_dev(SvtHipCtx* c, int pix_bytes, const void* d_a, int a_stride, const void* d_b, int b_stride,
                                 const SvtHipBlkPair* d_pairs, int n, uint32_t* d_sad) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_a || !d_b || !d_pairs || !d_sad || n < 0 || (pix_bytes != 1 && pix_bytes != 2)) return bad_arg(c);
+    if (!c || !d_a || !d_b || !d_pairs || !d_sad || n < 0 || !pix_ok(pix_bytes)) return bad_arg(c);
     return launched(c, svt_hip_launch_block_sad(c->stream, pix_bytes, d_a, a_stride, d_b, b_stride, d_pairs, n, d_sad), "block sad launch");
 }
 // What the md_*_picture forms share: the picture's geometry, the prediction-unit list and the reference-plane list.  The SAD forms also bound every unit's own
@@ -984,7 +990,7 @@ int svt_hip_coeff_distortion_batch_dev(SvtHipCtx* c, const int32_t* d_coeff, con
 int svt_hip_block_sse_batch_dev(SvtHipCtx* c, int pix_bytes, const void* d_a, int a_stride, const void* d_b, int b_stride, const SvtHipBlkPair* d_pairs,
                                 int n, uint64_t* d_sse) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_a || !d_b || !d_pairs || !d_sse || n < 0 || (pix_bytes != 1 && pix_bytes != 2)) return bad_arg(c);
+    if (!c || !d_a || !d_b || !d_pairs || !d_sse || n < 0 || !pix_ok(pix_bytes)) return bad_arg(c);
     return launched(c, svt_hip_launch_block_sse(c->stream, pix_bytes, d_a, a_stride, d_b, b_stride, d_pairs, n, d_sse), "block sse launch");
 }
 int svt_hip_block_variance_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_a, int a_stride, const void* d_b, int b_stride,
@@ -1304,8 +1310,7 @@ int svt_hip_wiener_stats_plane_dev(SvtHipCtx* c, int pix_bytes, int bd, int win,
     if (!c || !d_dgd || !d_src || !d_M || !d_H || (win != 7 && win != 5 && win != 3) || unit_size < 64 || (unit_size & 63) || unit_size > 256 ||
         (ss_y != 0 && ss_y != 1) || pw <= 0 || ph <= 0)
         return bad_arg(c);
-    if ((pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && bd != 8 && bd != 10 && bd != 12) || (pix_bytes != 1 && pix_bytes != 2))
-        return bad_arg(c, "svt_hip_wiener_stats_plane_dev: bad sample format");
+    if (!fmt12_ok(pix_bytes, bd)) return bad_arg(c, "svt_hip_wiener_stats_plane_dev: bad sample format");
     if (pix_bytes == 2) {
         const int n_units = sgr_units(pw, unit_size) * sgr_units(ph, unit_size);
         const size_t need = svt_hip_wiener_stats16_scratch(win, pw, ph, n_units);
@@ -1321,9 +1326,8 @@ int svt_hip_tf_filter_frame_dev(SvtHipCtx* c, int pix_bytes, int bd, const void*
                                 const int dst_stride[3], int w, int h, int ss_x, int ss_y, int tf_chroma, const SvtHipTfRef* refs, int n_refs,
                                 const double noise_levels[3], int decay_control, int min_frame_size, uint64_t* d_sse) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_src || !src_stride || !d_dst || !dst_stride || !refs || !noise_levels || !d_sse || (pix_bytes != 1 && pix_bytes != 2) ||
-        (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && (bd < 8 || bd > 12)) || w <= 0 || h <= 0 || (w & 63) || (h & 63) || n_refs < 1 ||
-        n_refs > SVT_HIP_TF_MAX_REFS || (ss_x != 0 && ss_x != 1) || (ss_y != 0 && ss_y != 1) || (ss_y == 1 && ss_x == 0) || decay_control <= 0)
+    if (!c || !d_src || !src_stride || !d_dst || !dst_stride || !refs || !noise_levels || !d_sse || !fmt_8to12_ok(pix_bytes, bd) || w <= 0 || h <= 0 ||
+        (w & 63) || (h & 63) || n_refs < 1 || n_refs > SVT_HIP_TF_MAX_REFS || (ss_x != 0 && ss_x != 1) || (ss_y != 0 && ss_y != 1) || (ss_y == 1 && ss_x == 0) || decay_control <= 0)
         return bad_arg(c, "svt_hip_tf_filter_frame_dev: bad argument");
     for (int p = 0; p < (tf_chroma ? 3 : 1); p++) {
         if (!d_src[p] || !d_dst[p]) return bad_arg(c);
@@ -1345,9 +1349,7 @@ int svt_hip_tf_filter_frame_dev(SvtHipCtx* c, int pix_bytes, int bd, const void*
 
 int svt_hip_tf_estimate_noise_dev(SvtHipCtx* c, const void* d_src, int pix_bytes, int bd, int width, int height, int stride, int64_t* d_out) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_src || !d_out || (pix_bytes != 1 && pix_bytes != 2) || (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && (bd < 8 || bd > 12)) ||
-        width <= 0 || height <= 0 || stride < width)
-        return bad_arg(c);
+    if (!c || !d_src || !d_out || !fmt_8to12_ok(pix_bytes, bd) || width <= 0 || height <= 0 || stride < width) return bad_arg(c);
     if (int rc = launched(c, hipMemsetAsync(d_out, 0, 2 * sizeof(int64_t), c->stream), "tf noise memset")) return rc;
     return launched(c, svt_hip_launch_tf_noise(c->stream, d_src, pix_bytes, bd, width, height, stride, (uint64_t*)d_out), "tf noise launch");
 }
@@ -1357,7 +1359,7 @@ int svt_hip_tf_subpel_frame_dev(SvtHipCtx* c, int pix_bytes, int bd, const void*
                                 int tf_chroma, const SvtHipTfSubpelBlk* d_jobs, int n_jobs, SvtHipTfBlk64* d_blocks) {
     SVT_HIP_ENTER(c);
     if (!c || !d_src || !src_stride || !d_ref || !ref_stride || !d_pred || !pred_stride || !d_jobs || !d_blocks || n_jobs < 0 || mi_cols <= 0 || mi_rows <= 0 ||
-        (pix_bytes != 1 && pix_bytes != 2) || (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && bd != 8 && bd != 10))
+        !fmt_ok(pix_bytes, bd))
         return bad_arg(c, "svt_hip_tf_subpel_frame_dev: bad argument");
     for (int p = 0; p < (tf_chroma ? 3 : 1); p++)
         if (!d_src[p] || !d_ref[p] || !d_pred[p]) return bad_arg(c);
@@ -1368,7 +1370,7 @@ int svt_hip_tf_subpel_frame_dev(SvtHipCtx* c, int pix_bytes, int bd, const void*
 int svt_hip_compound_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_ref0, int ref0_stride, const void* d_ref1, int ref1_stride,
                                        void* d_dst, int dst_stride, uint8_t* d_masks, const SvtHipCompBlk* d_blks, int nblk) {
     SVT_HIP_ENTER(c);
-    if (!c || nblk < 0 || (pix_bytes != 1 && pix_bytes != 2) || (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && bd != 8 && bd != 10 && bd != 12))
+    if (!c || nblk < 0 || !fmt12_ok(pix_bytes, bd))
         return bad_arg(c, "svt_hip_compound_predict_batch_dev: bad argument");
     if (nblk == 0) return SVT_HIP_OK;
     if (!d_ref0 || !d_ref1 || !d_dst || !d_blks) return bad_arg(c);
@@ -1388,7 +1390,7 @@ int svt_hip_obmc_cost_batch_dev(SvtHipCtx* c, const uint8_t* d_pre, int pre_stri
 int svt_hip_warp_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_ref, int width, int height, int stride, void* d_dst, int dst_stride,
                                    int ss_x, int ss_y, const SvtHipWarpBlk* d_blks, int nblk) {
     SVT_HIP_ENTER(c);
-    if (!c || nblk < 0 || (pix_bytes != 1 && pix_bytes != 2) || (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && bd != 8 && bd != 10 && bd != 12) ||
+    if (!c || nblk < 0 || !fmt12_ok(pix_bytes, bd) ||
         (ss_x != 0 && ss_x != 1) || (ss_y != 0 && ss_y != 1))
         return bad_arg(c, "svt_hip_warp_predict_batch_dev: bad argument");
     if (nblk == 0) return SVT_HIP_OK;
@@ -1398,7 +1400,7 @@ int svt_hip_warp_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const vo
 int svt_hip_warp_compound_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_ref, int width, int height, int stride, void* d_dst, int dst_stride,
                                     int ss_x, int ss_y, uint16_t* d_convbuf, const SvtHipWarpCompBlk* d_blks, int nblk) {
     SVT_HIP_ENTER(c);
-    if (!c || nblk < 0 || (pix_bytes != 1 && pix_bytes != 2) || (pix_bytes == 1 && bd != 8) || (pix_bytes == 2 && bd != 8 && bd != 10 && bd != 12) ||
+    if (!c || nblk < 0 || !fmt12_ok(pix_bytes, bd) ||
         (ss_x != 0 && ss_x != 1) || (ss_y != 0 && ss_y != 1))
         return bad_arg(c, "svt_hip_warp_compound_batch_dev: bad argument");
     if (nblk == 0) return SVT_HIP_OK;
@@ -1410,7 +1412,7 @@ int svt_hip_warp_compound_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const v
 int svt_hip_blend_a64_batch_dev(SvtHipCtx* c, int pix_bytes, const void* d_src0, int src0_stride, const void* d_src1, int src1_stride, void* d_dst, int dst_stride,
                                 const uint8_t* d_masks, const SvtHipBlendBlk* d_blks, int nblk) {
     SVT_HIP_ENTER(c);
-    if (!c || nblk < 0 || (pix_bytes != 1 && pix_bytes != 2)) return bad_arg(c);
+    if (!c || nblk < 0 || !pix_ok(pix_bytes)) return bad_arg(c);
     if (nblk == 0) return SVT_HIP_OK;
     if (!d_src0 || !d_src1 || !d_dst || !d_masks || !d_blks) return bad_arg(c);
     return launched(c, svt_hip_launch_blend_a64(c->stream, pix_bytes, d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_masks, d_blks, nblk), "blend_a64 launch");
@@ -1429,7 +1431,7 @@ int svt_hip_picture_format_dev(SvtHipCtx* c, int mode, const void* d_in0, int in
 
 int svt_hip_generate_padding_dev(SvtHipCtx* c, void* d_plane, int pix_bytes, int stride, int w, int h, int pad_w, int pad_h) {
     SVT_HIP_ENTER(c);
-    if (!c || (pix_bytes != 1 && pix_bytes != 2) || w < 0 || h < 0 || pad_w < 0 || pad_h < 0) return bad_arg(c);
+    if (!c || !pix_ok(pix_bytes) || w < 0 || h < 0 || pad_w < 0 || pad_h < 0) return bad_arg(c);
     if (w == 0 || h == 0 || (pad_w == 0 && pad_h == 0)) return SVT_HIP_OK;
     if (!d_plane || stride < w + pad_w) return bad_arg(c);
     return launched(c, svt_hip_launch_generate_padding(c->stream, d_plane, pix_bytes, stride, w, h, pad_w, pad_h), "generate padding launch");
@@ -1448,7 +1450,7 @@ int svt_hip_quantize_batch_dev(SvtHipCtx* c, const int32_t* d_coeff, int n_coeff
 int svt_hip_residual_dev(SvtHipCtx* c, int pix_bytes, const void* d_src, int src_stride, const void* d_pred, int pred_stride, int16_t* d_residual,
                          int residual_stride, int w, int h) {
     SVT_HIP_ENTER(c);
-    if (!c || (pix_bytes != 1 && pix_bytes != 2) || w < 0 || h < 0) return bad_arg(c);
+    if (!c || !pix_ok(pix_bytes) || w < 0 || h < 0) return bad_arg(c);
     if (w == 0 || h == 0) return SVT_HIP_OK;
     if (!d_src || !d_pred || !d_residual) return bad_arg(c);
     return launched(c, svt_hip_launch_residual(c->stream, pix_bytes, d_src, src_stride, d_pred, pred_stride, d_residual, residual_stride, w, h), "residual launch");
@@ -1489,13 +1491,13 @@ int svt_hip_handle_transform64_n2n4_batch_dev(SvtHipCtx* c, int tx_size, int32_t
 int svt_hip_diffwtd_mask_dev(SvtHipCtx* c, int elem_bytes, uint8_t* d_mask, const void* d_src0, int src0_stride, const void* d_src1, int src1_stride, int w, int h, int inverse,
                              int round, int shift) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_mask || !d_src0 || !d_src1 || w < 1 || h < 1 || (elem_bytes != 1 && elem_bytes != 2) || round < 0 || round > 15 || shift < 0 || shift > 8) return bad_arg(c);
+    if (!c || !d_mask || !d_src0 || !d_src1 || w < 1 || h < 1 || !pix_ok(elem_bytes) || round < 0 || round > 15 || shift < 0 || shift > 8) return bad_arg(c);
     return launched(c, svt_hip_launch_diffwtd_mask(c->stream, elem_bytes, d_mask, d_src0, src0_stride, d_src1, src1_stride, w, h, inverse, round, shift), "diffwtd mask launch");
 }
 int svt_hip_blend_a64_d16_dev(SvtHipCtx* c, int pix_bytes, int bd, void* d_dst, int dst_stride, const uint16_t* d_src0, int src0_stride, const uint16_t* d_src1, int src1_stride,
                               const uint8_t* d_mask, int mask_stride, int w, int h, int subw, int subh, int round_0, int round_1) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_dst || !d_src0 || !d_src1 || !d_mask || w < 1 || h < 1 || !((pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && bd >= 8 && bd <= 12)) || round_0 < 3 || round_0 > 5 ||
+    if (!c || !d_dst || !d_src0 || !d_src1 || !d_mask || w < 1 || h < 1 || !fmt_8to12_ok(pix_bytes, bd) || round_0 < 3 || round_0 > 5 ||
         round_1 < 1 || 14 - round_0 - round_1 < 0)
         return bad_arg(c);
     return launched(c, svt_hip_launch_blend_d16(c->stream, pix_bytes, bd, d_dst, dst_stride, d_src0, src0_stride, d_src1, src1_stride, d_mask, mask_stride, w, h,
@@ -1506,7 +1508,7 @@ int svt_hip_jnt_convolve_dev(SvtHipCtx* c, int pix_bytes, int bd, int variant, c
                              int bck_offset) {
     SVT_HIP_ENTER(c);
     if (!c || !d_src || !d_convbuf || !d_taps || (do_average && !d_dst) || w < 1 || h < 1 || variant < 0 || variant > 3 ||
-        !((pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && bd >= 8 && bd <= 12)) || round_0 < 3 || round_0 > 5 || round_1 < 1 || 14 - round_0 - round_1 < 0)
+        !fmt_8to12_ok(pix_bytes, bd) || round_0 < 3 || round_0 > 5 || round_1 < 1 || 14 - round_0 - round_1 < 0)
         return bad_arg(c);
     return launched(c, svt_hip_launch_jnt_convolve(c->stream, pix_bytes, bd, variant, d_src, src_stride, d_dst, dst_stride, d_convbuf, convbuf_stride, d_taps, w, h,
                                                    round_0, round_1, do_average, use_jnt_comp_avg, fwd_offset, bck_offset), "jnt convolve launch");
@@ -1530,7 +1532,7 @@ int svt_hip_ext_sad_32x32_64x64_batch_dev(SvtHipCtx* c, uint32_t* d_state, const
 int svt_hip_cdef_dist_dev(SvtHipCtx* c, int pix_bytes, const void* d_dst, int dstride, const void* d_src, const uint8_t* d_list, int n, int bw_log2, int bh_log2,
                           int coeff_shift, int pli, uint64_t* d_out) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_dst || !d_src || !d_list || !d_out || n < 0 || (pix_bytes != 1 && pix_bytes != 2) || (bw_log2 != 2 && bw_log2 != 3) || (bh_log2 != 2 && bh_log2 != 3) ||
+    if (!c || !d_dst || !d_src || !d_list || !d_out || n < 0 || !pix_ok(pix_bytes) || (bw_log2 != 2 && bw_log2 != 3) || (bh_log2 != 2 && bh_log2 != 3) ||
         coeff_shift < 0 || coeff_shift > 4)
         return bad_arg(c);
     return launched(c, svt_hip_launch_cdef_dist(c->stream, pix_bytes, d_dst, dstride, d_src, d_list, n, bw_log2, bh_log2, coeff_shift, pli, d_out), "cdef dist launch");
@@ -1608,7 +1610,7 @@ int svt_hip_cdef_finish_dev(SvtHipCtx* c, const uint64_t* d_mse0, const uint64_t
 int svt_hip_sgr_flt_proj_dev(SvtHipCtx* c, int pix_bytes, const void* d_src, int src_stride, const void* d_dat, int dat_stride, const int32_t* d_flt0, int flt0_stride,
                              const int32_t* d_flt1, int flt1_stride, int w, int h, int r0, int r1, int mode, const int32_t* xq, int64_t* d_acc, int32_t* d_xq) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_src || !d_dat || !d_acc || w < 1 || h < 1 || (pix_bytes != 1 && pix_bytes != 2) || (mode != 0 && mode != 1) || (r0 > 0 && !d_flt0) || (r1 > 0 && !d_flt1) ||
+    if (!c || !d_src || !d_dat || !d_acc || w < 1 || h < 1 || !pix_ok(pix_bytes) || (mode != 0 && mode != 1) || (r0 > 0 && !d_flt0) || (r1 > 0 && !d_flt1) ||
         (mode == 0 && !d_xq) || (mode == 1 && !xq))
         return bad_arg(c);
     if (int rc = launched(c, hipMemsetAsync(d_acc, 0, 5 * sizeof(int64_t), c->stream), "sgr flt proj clear")) return rc;
@@ -1624,7 +1626,7 @@ int svt_hip_convolve8_dev(SvtHipCtx* c, int vert, const uint8_t* d_src, int src_
 int svt_hip_wiener_convolve_add_src_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_src, int src_stride, void* d_dst, int dst_stride, const int16_t* d_taps, int w, int h,
                                         int round_0, int round_1) {
     SVT_HIP_ENTER(c);
-    if (!c || !d_src || !d_dst || !d_taps || w < 1 || h < 1 || !((pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && bd >= 8 && bd <= 12)) || round_0 < 1 || round_0 > 7 ||
+    if (!c || !d_src || !d_dst || !d_taps || w < 1 || h < 1 || !fmt_8to12_ok(pix_bytes, bd) || round_0 < 1 || round_0 > 7 ||
         round_1 < 1 || round_1 > 14)
         return bad_arg(c);
     return launched(c, svt_hip_launch_wiener_convolve(c->stream, pix_bytes, bd, d_src, src_stride, d_dst, dst_stride, d_taps, w, h, round_0, round_1), "wiener convolve launch");

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/svt_hip.h"
+#include "fmt_dispatch.h"
 
 
 // One empty kernel per translation unit: svt_hip_warmup() asks for its attributes, which makes the runtime load that unit's code object for the current device
@@ -21,6 +22,12 @@ __device__ __forceinline__ int svt_xcd_order(int b, int n) {
     const int q = n >> 3, r = n & 7, x = b & 7, s = b >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + s;
 #endif
+}
+// The sum of a 64-bit value over the 64 lanes of a wave, in every lane (__shfl_xor moves 32 bits: the halves travel apart).
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
 }
 #endif
 #define SVT_HIP_TU_PROBE(name)                                                                                                    \

@@ -266,9 +266,7 @@ extern "C" int svt_hip_launch_tf_subpel(hipStream_t st, int pix_bytes, int bd, c
     }
     a.mi_cols = mi_cols; a.mi_rows = mi_rows; a.tf_hp = tf_hp; a.tf_chroma = tf_chroma; a.th16 = th16; a.jobs = jobs; a.blocks = blocks;
     const dim3 grid(4 * n_jobs), block(64 * kWaves);
-    if (pix_bytes == 1) hipLaunchKernelGGL((tf_subpel_kernel<uint8_t, 8>), grid, block, 0, st, a);
-    else if (bd == 8) hipLaunchKernelGGL((tf_subpel_kernel<uint16_t, 8>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((tf_subpel_kernel<uint16_t, 10>), grid, block, 0, st, a);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((tf_subpel_kernel<typename decltype(f)::pix, decltype(f)::bd>), grid, block, 0, st, a); });
     return (int)hipGetLastError();
 }
 

@@ -115,12 +115,6 @@ __device__ __forceinline__ void block_terms(const SvtHipTfBlk64* __restrict__ b,
     d_factor = dd > 1.0 ? dd : 1.0;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One workgroup = one 32x32 luma block and its chroma, all frames.  Luma: thread t owns row t >> 3, columns 4 (t & 7) .. + 3.
@@ -350,14 +344,17 @@ extern "C" int svt_hip_launch_tf_filter(hipStream_t st, int pix_bytes, int bd, c
     }
     a.n_refs = n_refs; a.bc64 = w / 64; a.tf_chroma = tf_chroma; a.hbd = pix_bytes == 2; a.sq_shift = pix_bytes == 2 ? (bd - 8) * 2 : 0;
     a.dist_thr = dist_thr; a.rdist_thr = 1.0 / dist_thr; a.sse = (unsigned long long*)sse;
-    return pix_bytes == 1 ? launch_filter<uint8_t>(st, a, w, h, ss_x, ss_y) : launch_filter<uint16_t>(st, a, w, h, ss_x, ss_y);
+    return svt_for_pix(pix_bytes, [&](auto f) { return launch_filter<typename decltype(f)::pix>(st, a, w, h, ss_x, ss_y); });
 }
 
 extern "C" int svt_hip_launch_tf_noise(hipStream_t st, const void* src, int pix_bytes, int bd, int width, int height, int stride, uint64_t* out) {
     const int rows = height - 2 > 0 ? height - 2 : 1;
     const int grid = rows < 2048 ? rows : 2048;
-    if (pix_bytes == 1) hipLaunchKernelGGL(tf_noise_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)src, width, height, stride, 0, (unsigned long long*)out);
-    else hipLaunchKernelGGL(tf_noise_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)src, width, height, stride, bd - 8, (unsigned long long*)out);
+    const int sh = pix_bytes == 1 ? 0 : bd - 8;
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL(tf_noise_kernel<PIX>, dim3(grid), dim3(256), 0, st, (const PIX*)src, width, height, stride, sh, (unsigned long long*)out);
+    });
     return (int)hipGetLastError();
 }
 

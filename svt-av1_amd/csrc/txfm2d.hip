@@ -424,12 +424,10 @@ int launch_fwd(hipStream_t st, int pix_bytes, const void* src, int ss, const voi
                int32_t* cul, uint64_t* energy) {
     constexpr int L = W > H ? W : H, TEAMS = threads_of(W, H) / L;
     dim3 grid((n + TEAMS - 1) / TEAMS), block(threads_of(W, H));
-    if (pix_bytes == 1)
-        hipLaunchKernelGGL((fwd_txfm_quant_kernel<W, H, uint8_t>), grid, block, 0, st, (const uint8_t*)src, ss, (const uint8_t*)pred, ps,
-                           descs, n, qp, sc, coeff, q, dq, eob, cul, energy);
-    else
-        hipLaunchKernelGGL((fwd_txfm_quant_kernel<W, H, uint16_t>), grid, block, 0, st, (const uint16_t*)src, ss, (const uint16_t*)pred, ps,
-                           descs, n, qp, sc, coeff, q, dq, eob, cul, energy);
+    svt_for_pix(pix_bytes, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((fwd_txfm_quant_kernel<W, H, PIX>), grid, block, 0, st, (const PIX*)src, ss, (const PIX*)pred, ps, descs, n, qp, sc, coeff, q, dq, eob, cul, energy);
+    });
     return (int)hipGetLastError();
 }
 template <int W, int H>
@@ -437,12 +435,10 @@ int launch_inv(hipStream_t st, int pix_bytes, int bd, const int32_t* dq, const v
                const uint32_t* descs, int n) {
     constexpr int L = W > H ? W : H, TEAMS = threads_of(W, H) / L;
     dim3 grid((n + TEAMS - 1) / TEAMS), block(threads_of(W, H));
-    if (pix_bytes == 1)
-        hipLaunchKernelGGL((inv_txfm_add_kernel<W, H, 8, uint8_t>), grid, block, 0, st, dq, (const uint8_t*)pred, ps, (uint8_t*)recon, rs, descs, n);
-    else if (bd == 8)
-        hipLaunchKernelGGL((inv_txfm_add_kernel<W, H, 8, uint16_t>), grid, block, 0, st, dq, (const uint16_t*)pred, ps, (uint16_t*)recon, rs, descs, n);
-    else
-        hipLaunchKernelGGL((inv_txfm_add_kernel<W, H, 10, uint16_t>), grid, block, 0, st, dq, (const uint16_t*)pred, ps, (uint16_t*)recon, rs, descs, n);
+    svt_for_fmt(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((inv_txfm_add_kernel<W, H, decltype(f)::bd, PIX>), grid, block, 0, st, dq, (const PIX*)pred, ps, (PIX*)recon, rs, descs, n);
+    });
     return (int)hipGetLastError();
 }
 
@@ -495,8 +491,7 @@ extern "C" int svt_hip_launch_fwd_txfm_quant_multi(hipStream_t st, int pix_bytes
         }
         a.first_wg[a.njobs] = wg;
         if (!wg) continue;
-        if (pix_bytes == 1) hipLaunchKernelGGL((fwd_txfm_quant_multi_kernel<uint8_t>), dim3(wg), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((fwd_txfm_quant_multi_kernel<uint16_t>), dim3(wg), dim3(256), 0, st, a);
+        svt_for_pix(pix_bytes, [&](auto f) { hipLaunchKernelGGL((fwd_txfm_quant_multi_kernel<typename decltype(f)::pix>), dim3(wg), dim3(256), 0, st, a); });
     }
     return (int)hipGetLastError();
 }
@@ -514,9 +509,7 @@ extern "C" int svt_hip_launch_enc_txfm_multi(hipStream_t st, int pix_bytes, int 
         }
         e.f.first_wg[e.f.njobs] = wg;
         if (!wg) continue;
-        if (pix_bytes == 1) hipLaunchKernelGGL((enc_txfm_multi_kernel<uint8_t, 8>), dim3(wg), dim3(256), 0, st, e);
-        else if (bd == 8) hipLaunchKernelGGL((enc_txfm_multi_kernel<uint16_t, 8>), dim3(wg), dim3(256), 0, st, e);
-        else hipLaunchKernelGGL((enc_txfm_multi_kernel<uint16_t, 10>), dim3(wg), dim3(256), 0, st, e);
+        svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((enc_txfm_multi_kernel<typename decltype(f)::pix, decltype(f)::bd>), dim3(wg), dim3(256), 0, st, e); });
     }
     return (int)hipGetLastError();
 }
@@ -533,9 +526,7 @@ extern "C" int svt_hip_launch_inv_txfm_add_multi(hipStream_t st, int pix_bytes, 
         }
         a.first_wg[a.njobs] = wg;
         if (!wg) continue;
-        if (pix_bytes == 1) hipLaunchKernelGGL((inv_txfm_add_multi_kernel<uint8_t, 8>), dim3(wg), dim3(256), 0, st, a);
-        else if (bd == 8) hipLaunchKernelGGL((inv_txfm_add_multi_kernel<uint16_t, 8>), dim3(wg), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((inv_txfm_add_multi_kernel<uint16_t, 10>), dim3(wg), dim3(256), 0, st, a);
+        svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((inv_txfm_add_multi_kernel<typename decltype(f)::pix, decltype(f)::bd>), dim3(wg), dim3(256), 0, st, a); });
     }
     return (int)hipGetLastError();
 }

@@ -85,23 +85,21 @@ warp_predict_kernel(const PIX* __restrict__ ref, int width, int height, int stri
 extern "C" int svt_hip_launch_warp_predict(hipStream_t st, int pix_bytes, int bd, const void* ref, int width, int height, int stride, void* dst, int dst_stride,
                                            int ss_x, int ss_y, const SvtHipWarpBlk* blks, int n) {
     if (n <= 0) return 0;
-#define LAUNCH(P, B) hipLaunchKernelGGL((warp_predict_kernel<P, B, false>), dim3(n), dim3(256), 0, st, (const P*)ref, width, height, stride, (P*)dst, dst_stride, ss_x, ss_y, (const void*)blks, (uint16_t*)nullptr)
-    if (pix_bytes == 1) LAUNCH(uint8_t, 8);
-    else if (bd == 8) LAUNCH(uint16_t, 8);
-    else if (bd == 10) LAUNCH(uint16_t, 10);
-    else LAUNCH(uint16_t, 12);
-#undef LAUNCH
+    svt_for_fmt12(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((warp_predict_kernel<PIX, decltype(f)::bd, false>), dim3(n), dim3(256), 0, st, (const PIX*)ref, width, height, stride, (PIX*)dst, dst_stride, ss_x,
+                           ss_y, (const void*)blks, (uint16_t*)nullptr);
+    });
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_warp_compound(hipStream_t st, int pix_bytes, int bd, const void* ref, int width, int height, int stride, void* dst, int dst_stride,
                                             int ss_x, int ss_y, uint16_t* convbuf, const SvtHipWarpCompBlk* blks, int n) {
     if (n <= 0) return 0;
-#define LAUNCH(P, B) hipLaunchKernelGGL((warp_predict_kernel<P, B, true>), dim3(n), dim3(256), 0, st, (const P*)ref, width, height, stride, (P*)dst, dst_stride, ss_x, ss_y, (const void*)blks, convbuf)
-    if (pix_bytes == 1) LAUNCH(uint8_t, 8);
-    else if (bd == 8) LAUNCH(uint16_t, 8);
-    else if (bd == 10) LAUNCH(uint16_t, 10);
-    else LAUNCH(uint16_t, 12);
-#undef LAUNCH
+    svt_for_fmt12(pix_bytes, bd, [&](auto f) {
+        using PIX = typename decltype(f)::pix;
+        hipLaunchKernelGGL((warp_predict_kernel<PIX, decltype(f)::bd, true>), dim3(n), dim3(256), 0, st, (const PIX*)ref, width, height, stride, (PIX*)dst, dst_stride, ss_x,
+                           ss_y, (const void*)blks, convbuf);
+    });
     return (int)hipGetLastError();
 }
 

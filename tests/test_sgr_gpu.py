@@ -222,9 +222,9 @@ def test_wiener_walk_units(hip, bd, fmt, ss):
     fc.two_witnesses(_wiener_walk_units, fmt, bd, hip, M, ss)
 
 
-def _wiener_walk_units(hip, M, ss, bd, dt, wide):
+def _wiener_walk_units(hip, M, ss, bd, dt, wide, cases=((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3))):
     gots, exps = [], []
-    for (w, h, US, win) in ((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3))[:1 if wide else 4]:
+    for (w, h, US, win) in cases[:1 if wide else 4]:
         if ss and win == 7: win = 5     # chroma planes search the 5-tap window at most (search_wiener_seg :1352-1358)
         src, ext = make_planes(w, h, bd, 190 + bd + ss + US, dt, wide)
         st = ext.shape[1]; off = (EXT * st + EXT) * ext.itemsize
@@ -256,6 +256,18 @@ def _wiener_walk_units(hip, M, ss, bd, dt, wide):
         assert (e_wn[on] != wn[on]).any(), "no walk moved a tap: the content does not exercise the search"
         gots += [g_wn, g_err[on], g_pr[on]]; exps += [e_wn, e_err[on], e_pr[on]]
     return gots, exps
+
+
+def test_wiener_walk_unit_beyond_the_resident_window(hip):
+    """The 8-bit walk of a unit that does not fit the resident form's LDS window (wiener_walk_kernel<uint8_t, 8>, which the smaller units of test_wiener_walk_units never
+    reach): one unit of unit size 256 that is 1.5 x in both directions -- 13 tile rows x 38 rows x (6 x 64 + 8) bytes = 193 648 > 124 KB."""
+    import shard_common as sc
+    if not os.path.exists(sc.MOCK_LIB):
+        pytest.skip("oracle/_ref/mock/libsvtav1_hip.so not built")
+    M = C.CDLL(sc.MOCK_LIB)
+    M.svt_hip_wiener_walk_units_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _wiener_walk_units(hip, M, 0, 8, np.uint8, False, cases=((380, 380, 256, 7),))
 
 
 @pytest.mark.parametrize("bd,fmt", fc.bd_fmts())
@@ -577,10 +589,18 @@ def test_search_units_packed_words_and_escape_lists(hip, orc, lim, ss):
     whose |flt - u| does not fit is a zero word in the plane and an exact entry of the (unit, set)'s escape list.  The right half of the picture is binary 0 / 255 (which
     escapes at the real limit of 1024 as well); SVT_HIP_SGR_ESC_LIM (read per launch) narrows the range so that ordinary samples are listed too: 48 lists a few per cent,
     3 nearly everything -- the walk then is the sample-by-sample sum of the lists.  All 16 sets against the oracle, for this form and for the default 6-byte form."""
-    bd = 8
-    w, h, US, mask = 424, 328, 128, 0xFFFF   # 3 x 3 units, last column 168 wide (not a multiple of 64), last row 72 + 128
+    _packed_words_case(hip, orc, lim, ss, np.uint8, 424, 328, 128)   # 3 x 3 units, last column 168 wide (not a multiple of 64), last row 72 + 128
+
+
+def test_search_units_packed_words_u16_8(hip, orc):
+    """The same for 8-bit samples in 16-bit words (sgr_search8_kernel<uint16_t, 8, 2>): two units of the smallest size, the second one ragged, at the narrowed limit."""
+    _packed_words_case(hip, orc, 48, 0, np.uint16, 136, 72, 64)
+
+
+def _packed_words_case(hip, orc, lim, ss, dt, w, h, US):
+    bd, mask = 8, 0xFFFF
     mx = 255
-    src, ext = _smooth_noisy(w, h, bd, 1500 + ss, 5)
+    src, ext = _smooth_noisy(w, h, bd, 1500 + ss, 5, dt)
     rng = np.random.default_rng(1600 + ss)
     ext[EXT:EXT + h, EXT + w // 2:EXT + w] = (mx * rng.integers(0, 2, (h, w - w // 2))).astype(ext.dtype)
     ext[:, EXT + w:] = ext[:, EXT + w - 1:EXT + w]; ext[:EXT, :] = ext[EXT:EXT + 1, :]; ext[EXT + h:, :] = ext[EXT + h - 1:EXT + h, :]
