@@ -902,7 +902,9 @@ int svt_hip_lpf_edges_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, void *d_p
  * svt_nxm_sad_kernel_sub_sampled (:953; aom_dsp_rtcd.c:372 — the plain SAD of all rows), and in the first partitioning pass (PD_PASS_0) at presets above M4
  * the open-loop ME vectors enter stage 0 unrefined (EbEncDecProcess.c:3050-3093).  One launch per picture computes that distortion for every
  * (superblock, PU of `pus`, reference picture):
- *   d_src  : sample (0, 0) of the source luma plane, pic_w x pic_h samples exist from there (PUs that leave them are skipped)
+ *   d_src  : sample (0, 0) of the source luma plane, pic_w x pic_h samples exist from there (PUs that leave them are skipped).  Any address and stride: the kernels read
+ *            a row's samples as whole aligned dwords, so up to 4 bytes past the last sample of a PU row are read (8- and 16-bit planes alike) and the caller's plane
+ *            must be readable there — after the last row of the picture too.  The bridge's padded pictures are.
  *   pus    : the PUs of a 64x64 superblock, positions relative to it (host array; the 85 square PUs of the open-loop ME in its order, or any other list)
  *   refs   : the reference pictures' luma planes (host array of n_refs <= SVT_HIP_MD_MAX_REFS descriptors; d_plane = device address of sample (0, 0),
  *            [x_min, x_max) x [y_min, y_max) = the sample coordinates its allocation holds, padding included)
@@ -912,7 +914,7 @@ int svt_hip_lpf_edges_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, void *d_p
 #define SVT_HIP_MD_MAX_REFS 7     /* MAX_PA_ME_MV, Encoder/Codec/EbMotionEstimationLcuResults.h:23 */
 #define SVT_HIP_MD_MAX_PUS 128
 #define SVT_HIP_MD_NO_MV (-32768)
-typedef struct { uint8_t x, y, w, h; } SvtHipMdPu;   /* w a multiple of 4, at most 64 */
+typedef struct { uint8_t x, y, w, h; } SvtHipMdPu;   /* w a multiple of 4, at most 64 (every such width, not only the powers of two); h 1 .. 64 */
 typedef struct { const uint8_t *d_plane; int32_t stride, x_min, y_min, x_max, y_max; } SvtHipMdRefPlane;
 int svt_hip_md_fullpel_sad_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus,
                                        const SvtHipMdPu *pus, int n_refs, const SvtHipMdRefPlane *refs, const uint32_t *d_mv, uint32_t *d_sad);
@@ -940,7 +942,8 @@ int svt_hip_md_fullpel_avg_sad_picture_hbd_dev(SvtHipCtx *ctx, const uint16_t *d
  * (superblock, square PU of `pus`, reference picture), all 49 grid positions:
  *   d_out : [n_sb][n_pus][n_refs][49][2] = (variance, sse) of grid position 7 * row + col, offsets (2 col - 6, 2 row - 6) eighth-samples from the full-pel vector in d_mv;
  *           0xffffffff pairs = not computed (no vector, PU outside the picture or not 8 / 16 / 32 / 64 square, window outside the reference's allocation)
- *   bank  : the interpolation kernels of subpel_search_type as in SvtHipUpsampledBlk (0 = USE_8_TAPS, 4 = USE_4_TAPS, 3 = USE_2_TAPS)
+ *   bank  : the interpolation kernels, 0 .. 5 as in SvtHipUpsampledBlk, all accepted (1 = EIGHTTAP_SMOOTH, 2 = MULTITAP_SHARP, 5 = 4-tap smooth); the encoder's
+ *           subpel_search_type uses three of them: 0 = USE_8_TAPS, 4 = USE_4_TAPS, 3 = USE_2_TAPS
  * The other arguments are svt_hip_md_fullpel_sad_picture_dev's. */
 #define SVT_HIP_MD_GRID 49
 int svt_hip_md_subpel_grid_picture_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus, const SvtHipMdPu *pus,

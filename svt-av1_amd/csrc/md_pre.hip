@@ -80,6 +80,7 @@ md_fullpel_sad_kernel(const PIX* __restrict__ src, int src_stride, int pic_w, in
             if (lane == 0) sad[slot] = 0xffffffffu;
             continue;
         }
+        // lanes per row, whole rows per step; where w / 4 does not divide 64 the last 64 - rows * n4 lanes have row == rows: they load (clamped, inside the PU) and add nothing
         const int n4 = w >> 2, rows = 64 / n4, row = lane / n4, c4 = (lane - row * n4) << 2;
         const PIX* ps = src + (ptrdiff_t)y * src_stride + x + c4;
         const PIX* pr = (const PIX*)ref.d_plane + (ptrdiff_t)ry * ref.stride + rx + c4;
@@ -92,7 +93,7 @@ md_fullpel_sad_kernel(const PIX* __restrict__ src, int src_stride, int pic_w, in
                 a[u] = ld4(ps + (ptrdiff_t)yy * src_stride); b[u] = ld4(pr + (ptrdiff_t)yy * ref.stride);
             }
 #pragma unroll
-            for (int u = 0; u < 4; u++) { const uint32_t t = sad4(a[u], b[u], s); s = r0 + u * rows + row < h ? t : s; }
+            for (int u = 0; u < 4; u++) { const uint32_t t = sad4(a[u], b[u], s); s = row < rows && r0 + u * rows + row < h ? t : s; }
         }
         s = rows_total(row_sum(s));
         if (lane == 0) sad[slot] = s;
@@ -140,7 +141,7 @@ md_fullpel_avg_sad_kernel(const PIX* __restrict__ src, int src_stride, int pic_w
                 a[u] = ld4(ps + (ptrdiff_t)yy * src_stride); b[u] = ld4(p0 + (ptrdiff_t)yy * ref0.stride); c[u] = ld4(p1 + (ptrdiff_t)yy * ref1.stride);
             }
 #pragma unroll
-            for (int u = 0; u < 2; u++) { const uint32_t t = sad4(a[u], avg_round_up(b[u], c[u]), s); s = r0 + u * rows + row < h ? t : s; }
+            for (int u = 0; u < 2; u++) { const uint32_t t = sad4(a[u], avg_round_up(b[u], c[u]), s); s = row < rows && r0 + u * rows + row < h ? t : s; }
         }
         s = rows_total(row_sum(s));
         if (lane == 0) sad[slot] = s;

@@ -28,7 +28,8 @@ def run_hip(hip, pkg, src, refs, pus, mv, sb_cols, n_sb, pad, pic_w, pic_h):
 
 @pytest.mark.parametrize("w,h,n_refs", [(336, 208, 3), (64, 64, 1), (200, 152, 7), (1280, 720, 2)])
 def test_md_fullpel_sad_picture(hip, pkg, orc, w, h, n_refs):
-    """whole pictures incl. partial last superblock rows / columns, 1..7 references, missing vectors, vectors that leave the allocation, an odd source stride"""
+    """whole pictures incl. partial last superblock rows / columns, 1..7 references, missing vectors, vectors that leave the allocation; source strides that are no
+    multiple of 64 (odd strides and unaligned planes: test_md_unaligned_planes)"""
     rng = np.random.default_rng(w * 7 + h + n_refs)
     src, refs, pus, mv, sb_cols, n_sb, pad = M.make_case(rng, w, h, n_refs)
     exp = M.oracle_table(orc, src, refs, pus, mv, sb_cols, n_sb, pad, w, h)
@@ -150,3 +151,99 @@ def test_md_subpel_grid_picture(hip, pkg, orc, w, h, n_refs, bank):
     assert (exp == 0xffffffff).any() and (exp != 0xffffffff).any()
     assert np.array_equal(got, exp), np.argwhere(got != exp)[:6]
     assert np.array_equal(got9, exp9), np.argwhere(got9 != exp9)[:6]
+
+
+# ------------------------------------------------------------------------------------------------ the cases of md_common (tests/test_md_ref_cpu.py builds the same ones on the CPU)
+def _device(hip, pkg, c):
+    """uploads a md_common.Case -> (address of source sample (0, 0), PU array, reference planes, vectors, the allocations to free)"""
+    size = c.src.buf.itemsize
+    bufs = [hip.to_device(c.src.buf)] + [hip.to_device(r.buf) for r in c.refs] + [hip.to_device(c.mv)]
+    assert all(b.value % 4 == 0 for b in bufs)                     # Plane.align() counts from an aligned allocation
+    pu_arr = (pkg.MdPu * len(c.pus))(*[pkg.MdPu(*p) for p in c.pus])
+    planes = (pkg.MdRefPlane * len(c.refs))(*[pkg.MdRefPlane(b.value + r.off * size, r.stride, *r.box) for b, r in zip(bufs[1:], c.refs)])
+    return C.c_void_p(bufs[0].value + c.src.off * size), pu_arr, planes, bufs[-1], bufs
+
+
+def _run(hip, pkg, c, what):
+    """the tables of `what` (sad / avg / grid / half) for a md_common.Case, each written into a buffer filled with md_common.SENTINEL"""
+    d_src, pu_arr, planes, d_mv, bufs = _device(hip, pkg, c)
+    hbd = c.src.buf.itemsize == 2
+    head = (hip.h, d_src, c.src.stride, c.pic_w, c.pic_h, c.sb_cols, c.n_sb, len(c.pus), pu_arr, len(c.refs), planes, d_mv)
+    out = {}
+    for k in what:
+        if k == "sad": fn, shape, tail = (hip.L.svt_hip_md_fullpel_sad_picture_hbd_dev if hbd else hip.L.svt_hip_md_fullpel_sad_picture_dev), c.mv.shape, ()
+        elif k == "avg":
+            pr = np.array(c.pairs, np.uint8)
+            fn, shape, tail = (hip.L.svt_hip_md_fullpel_avg_sad_picture_hbd_dev if hbd else hip.L.svt_hip_md_fullpel_avg_sad_picture_dev), c.mv.shape[:2] + (len(c.pairs),), (len(c.pairs), pr.ctypes.data_as(C.c_void_p))
+        elif k == "grid": fn, shape, tail = hip.L.svt_hip_md_subpel_grid_picture_dev, c.mv.shape + (49, 2), (c.bank,)
+        else: fn, shape, tail = hip.L.svt_hip_md_halfpel_grid_picture_dev, c.mv.shape + (9, 2), (c.bank,)
+        d_out = hip.to_device(np.full(shape, M.SENTINEL, np.uint32))
+        try:
+            hip.check(fn(*head, *tail, d_out), "md " + k)
+            out[k] = hip.to_host(d_out, shape, np.uint32)
+        finally:
+            hip.free(d_out)
+    hip.free(*bufs)
+    return out
+
+
+def _same(c, got, exp, what):
+    """device table == expected table, or the first mismatching (sb, pu, w, h, column) with both values and the (w, h) of every PU that has a mismatch"""
+    assert got.shape == exp.shape
+    if np.array_equal(got, exp): return
+    bad = np.argwhere(got != exp)
+    sb, p, k = (int(v) for v in bad[0][:3])
+    sizes = sorted({c.pus[int(i)][2:] for i in np.unique(bad[:, 1])})
+    raise AssertionError(f"{what}: {len(bad)} words differ, first at (sb {sb}, pu {p}, w {c.pus[p][2]}, h {c.pus[p][3]}, ref/pair {k}) {bad[0][3:].tolist()}: "
+                         f"device {int(got[tuple(bad[0])])} expected {int(exp[tuple(bad[0])])}; (w, h) with a difference: {sizes}")
+
+
+def _check(hip, pkg, c, what):
+    got = _run(hip, pkg, c, what)
+    for k in what:
+        _same(c, got[k], getattr(c, "exp_" + k), k)
+
+
+@pytest.mark.parametrize("what", ["sad", "avg"])
+@pytest.mark.parametrize("bits", [8, 16])
+def test_md_every_width_and_row_step(hip, pkg, orc, bits, what):
+    """every width 4 .. 64 at the heights around which the wave's row loop turns over (1, rows, rows + 1, 2 rows + 1, 4 rows, 4 rows + 1, 64; rows = 64 / (w / 4)), PUs in
+    alternating corners of the superblock, odd vectors, all max against all 0 == the oracle == numpy.  The widths whose w / 4 does not divide 64 leave lanes past the last
+    whole row of a step: they must add nothing (they once added the next step's first rows a second time: md_common.FIRST_WRONG_H)."""
+    _check(hip, pkg, M.widths_case(orc, bits), [what])
+
+
+@pytest.mark.parametrize("bits,grid", [(8, False), (16, False), (8, True)])
+def test_md_flush_with_the_box_and_one_past(hip, pkg, orc, bits, grid):
+    """blocks exactly flush with each of the four sides of a reference's allocation box are computed, one sample further they read 0xffffffff: the full-pel block
+    ([0, w + 4) x [0, h)), either reference of a compound pair in turn, and the sub-pel window ([-4, s + 8) x [-4, s + 4)); the boxes lie inside larger buffers"""
+    _check(hip, pkg, M.edges_case(orc, bits, grid), ["grid", "half"] if grid else ["sad", "avg"])
+
+
+@pytest.mark.parametrize("bits,shift", M.UNALIGNED)
+def test_md_unaligned_planes(hip, pkg, orc, bits, shift):
+    """source pointer 1 / 2 / 3 samples off a dword, source stride 203, odd reference strides, references starting at an odd sample: every address & 3 on both sides of
+    load4_any / load4_any16 and of the grid's window staging"""
+    _check(hip, pkg, M.unaligned_case(orc, bits, shift), ["sad", "avg"] + (["grid", "half"] if bits == 8 else []))
+
+
+@pytest.mark.parametrize("bank", range(6))
+def test_md_subpel_grid_every_bank(hip, pkg, orc, bank):
+    """all six interpolation banks on 0 / 255 noise and on flat 255 / 0 halves that meet inside PUs: MULTITAP_SHARP has non-zero taps 0 and 7 (the first and last byte of
+    every 8-tap window count), and both 8-bit clips of both passes bind (tests/test_md_ref_cpu.py::test_banks_case)"""
+    _check(hip, pkg, M.banks_case(orc, bank), ["grid", "half"])
+
+
+@pytest.mark.parametrize("kind", M.CLOSED_KINDS)
+def test_md_subpel_grid_closed_forms(hip, pkg, orc, kind):
+    """every PU size and bank at the zero vector: all 255 against all 0 and the mirror image give (0, s^2 * 65025) at all 49 positions (the largest sse the uint32
+    statistics hold); a reference equal to the source gives (0, 0) at the centre; flat 100 against flat 100 gives (0, 0) everywhere"""
+    for bank in range(6):
+        _check(hip, pkg, M.closed_case(orc, kind, bank), ["grid", "half"])
+
+
+@pytest.mark.parametrize("name", M.GRID_LISTS)
+def test_md_subpel_grid_other_pu_lists(hip, pkg, orc, name):
+    """a list with no PU for the four-wave launch, one with none for the one-wave launch, and a shuffled list with PUs the kernel declines on both sides (4x4 and 12x12;
+    16x32 and 32x16): declined PUs read 0xffffffff, the others are computed, no word keeps the sentinel"""
+    _check(hip, pkg, M.grid_list_case(orc, name), ["grid", "half"])
