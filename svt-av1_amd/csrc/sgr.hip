@@ -941,6 +941,23 @@ __device__ inline bool wn_result(WnWalkState& w, long long err2, int off) {
     }
     return wn_issue(w, off);
 }
+// thread 0's steps of the walk, shared by both kernels (the decision step's sum and the unit's rectangle stay spelled out in each: as helpers they changed the kernels' code)
+__device__ __forceinline__ void wn_publish(const WnWalkState& w, int* taps) {   // taps: the probe the workgroup filters with, [0..7] vertical, [8..15] horizontal
+#pragma unroll
+    for (int k = 0; k < 8; k++) { taps[k] = w.v[k]; taps[8 + k] = w.h[k]; }
+}
+__device__ __forceinline__ void wn_start(WnWalkState& w, const int16_t* __restrict__ unit_wiener, int unit, int* taps) {   // the first probe: the unit's taps as they are
+#pragma unroll
+    for (int k = 0; k < 8; k++) { w.v[k] = unit_wiener[16 * unit + k]; w.h[k] = unit_wiener[16 * unit + 8 + k]; }
+    w.state = 1; w.err = 0; w.s = 0; w.ph = 0; w.p = 0; w.up = 0; w.skip = 0;
+    wn_publish(w, taps);
+}
+__device__ __forceinline__ void wn_store(const WnWalkState& w, int16_t* __restrict__ unit_wiener, long long* __restrict__ err_out, uint32_t* __restrict__ probes_out, int unit, uint32_t n_probes) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) { unit_wiener[16 * unit + k] = w.v[k]; unit_wiener[16 * unit + 8 + k] = w.h[k]; }
+    err_out[unit] = w.err;
+    if (probes_out) probes_out[unit] = n_probes;
+}
 struct WnPlane { const void* dgd; const void* dbl; const void* src; int16_t* unit_wiener; const uint8_t* active; long long* err; uint32_t* probes;
                  int stride, pw, ph, unit_size, units_x, units_y, voff, stripe_h, dbl_stride, src_stride, win; };
 struct WnPic { WnPlane p[3]; };   // blockIdx.y = plane: the planes of a picture walk side by side (a launch lasts as long as its longest walk)
@@ -969,14 +986,7 @@ wiener_walk_kernel(const WnPic a) {
     const int tiles_x = (rx1 - rx0 + S_TW - 1) / S_TW, ty_first = (ry0 + voff) / S_TH, tiles_y = (ry1 + voff + S_TH - 1) / S_TH - ty_first, n_tiles = tiles_x * tiles_y;
     __shared__ WnWalkState w_lds;   // thread 0's walk state: its tap arrays are indexed at run time, which as a private object means scratch memory (a memory round trip per access)
     WnWalkState& w = w_lds;
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) { w.v[k] = unit_wiener[16 * unit + k]; w.h[k] = unit_wiener[16 * unit + 8 + k]; }
-        w.state = 1; w.err = 0; w.s = 0; w.ph = 0; w.p = 0; w.up = 0; w.skip = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { taps[k] = w.v[k]; taps[8 + k] = w.h[k]; }
-        go = 1;
-    }
+    if (tid == 0) { wn_start(w, unit_wiener, unit, taps); go = 1; }
     uint32_t n_probes = 0;
     __syncthreads();
     while (go) {
@@ -1039,17 +1049,11 @@ wiener_walk_kernel(const WnPic a) {
             for (int k = 0; k < 16; k++) tot += part[k];
             n_probes++;
             go = wn_result(w, (long long)tot, off) ? 1 : 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) { taps[k] = w.v[k]; taps[8 + k] = w.h[k]; }
+            wn_publish(w, taps);
         }
         __syncthreads();
     }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) { unit_wiener[16 * unit + k] = w.v[k]; unit_wiener[16 * unit + 8 + k] = w.h[k]; }
-        err_out[unit] = w.err;
-        if (probes_out) probes_out[unit] = n_probes;
-    }
+    if (tid == 0) wn_store(w, unit_wiener, err_out, probes_out, unit, n_probes);
 }
 
 // A workgroup barrier that orders LDS only.  __syncthreads() also waits for every outstanding GLOBAL load (s_waitcnt vmcnt(0) before s_barrier), which puts the full
@@ -1100,6 +1104,7 @@ wiener_walk8w_kernel(const WnPic a) {
             const int b = i / (S_IH * pitch_dw), rem = i - b * (S_IH * pitch_dw), r = rem / pitch_dw, cd = rem - r * pitch_dw;
             const int y0 = (ty_first + b) * S_TH - voff, yy = y0 - 3 + r, xx0 = rx0 - 4 + 4 * cd;
             const StripeCtx<uint8_t> sc = lr_stripe_of<uint8_t>(dbl, dbl_stride, y0, voff, stripe_h, ph);
+            // lr_tile_sample's context-row rule, restated (a helper shared with it changed this kernel's code)
             const bool up = sc.above && yy < sc.sy0, dn = sc.below && yy >= sc.sy1, ctx = up || dn;
             const int  yd = up ? (yy == sc.sy0 - 1 ? sc.sy0 - 1 : sc.sy0 - 2) : min(yy == sc.sy1 ? sc.sy1 : sc.sy1 + 1, ph - 1);
             const uint8_t* row = ctx ? dbl + (ptrdiff_t)yd * dbl_stride : dgd + (ptrdiff_t)min(max(yy, -3), ph + 2) * stride;
@@ -1112,14 +1117,7 @@ wiener_walk8w_kernel(const WnPic a) {
         [&](int i, uint32_t v) { ((uint32_t*)bands)[i] = v; });
     __shared__ WnWalkState w_lds;   // thread 0's walk state: its tap arrays are indexed at run time, which as a private object means scratch memory (a memory round trip per access)
     WnWalkState& w = w_lds;
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) { w.v[k] = unit_wiener[16 * unit + k]; w.h[k] = unit_wiener[16 * unit + 8 + k]; }
-        w.state = 1; w.err = 0; w.s = 0; w.ph = 0; w.p = 0; w.up = 0; w.skip = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { taps[k] = w.v[k]; taps[8 + k] = w.h[k]; }
-        go = 1;
-    }
+    if (tid == 0) { wn_start(w, unit_wiener, unit, taps); go = 1; }
     uint32_t n_probes = 0;
     const int c4 = (lane & 15) << 2, rg = lane >> 4;   // the lane's four columns and its eight rows 8 rg .. 8 rg + 7 of a tile
     const bool src_dwords = ((uintptr_t)src & 3) == 0 && (src_stride & 3) == 0;
@@ -1206,17 +1204,11 @@ wiener_walk8w_kernel(const WnPic a) {
             for (int k = 0; k < 16; k++) tot += part[k];
             n_probes++;
             go = wn_result(w, (long long)tot, off) ? 1 : 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) { taps[k] = w.v[k]; taps[8 + k] = w.h[k]; }
+            wn_publish(w, taps);
         }
         lds_barrier();
     }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) { unit_wiener[16 * unit + k] = w.v[k]; unit_wiener[16 * unit + 8 + k] = w.h[k]; }
-        err_out[unit] = w.err;
-        if (probes_out) probes_out[unit] = n_probes;
-    }
+    if (tid == 0) wn_store(w, unit_wiener, err_out, probes_out, unit, n_probes);
 }
 
 }  // namespace

@@ -258,7 +258,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(percall2) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -1537,6 +1537,7 @@ int svt_hip_cdef_dist_dev(SvtHipCtx* c, int pix_bytes, const void* d_dst, int ds
         return bad_arg(c);
     return launched(c, svt_hip_launch_cdef_dist(c->stream, pix_bytes, d_dst, dstride, d_src, d_list, n, bw_log2, bh_log2, coeff_shift, pli, d_out), "cdef dist launch");
 }
+/* ---------------------------------------------------------------- CDEF strength decision (cdef_select.hip) */
 int svt_hip_cdef_search_one_dual_dev(SvtHipCtx* c, const uint64_t* d_mse0, const uint64_t* d_mse1, int sb_count, int* d_lev0, int* d_lev1, int nb_strengths, int start_gi,
                                      int end_gi, uint64_t* d_work) {
     SVT_HIP_ENTER(c);
@@ -1607,6 +1608,7 @@ int svt_hip_cdef_finish_dev(SvtHipCtx* c, const uint64_t* d_mse0, const uint64_t
     if (!c || !d_mse0 || !d_mse1 || !d_state || !d_out || sb_count < 0) return bad_arg(c);
     return launched(c, svt_hip_launch_cdef_finish(c->stream, d_mse0, d_mse1, sb_count, d_state, lambda, d_sb_fb, d_out, d_sel_gi, d_fb_y, d_fb_uv), "cdef finish launch");
 }
+/* ------------------------------------------------------- per-call forms, continued (percall.hip, cdef.hip, deblock.hip) */
 int svt_hip_sgr_flt_proj_dev(SvtHipCtx* c, int pix_bytes, const void* d_src, int src_stride, const void* d_dat, int dat_stride, const int32_t* d_flt0, int flt0_stride,
                              const int32_t* d_flt1, int flt1_stride, int w, int h, int r0, int r1, int mode, const int32_t* xq, int64_t* d_acc, int32_t* d_xq) {
     SVT_HIP_ENTER(c);

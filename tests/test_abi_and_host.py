@@ -55,6 +55,23 @@ def test_product_does_not_reference_oracle():
                 assert "liboracle" not in txt and "oracle/" not in txt.replace("the oracle", ""), f
 
 
+def test_warmup_list_names_every_kernel_unit():
+    """The Makefile picks the kernel units up by wildcard; svt_hip_warmup's list (SVT_HIP_TUS) is written by hand.  A unit missing from it would load its code
+    object inside the first picture's clock and nothing else would notice: the list is exactly the stems of csrc/*.hip, and every unit defines its own probe."""
+    csrc = os.path.join(ROOT, "svt-av1_amd", "csrc")
+    stems = sorted(f[:-4] for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(stems) >= 20
+    api = open(os.path.join(csrc, "svt_hip_api.cpp")).read()
+    m = re.search(r"^#define SVT_HIP_TUS\(X\)((?:.*\\\n)*.*)$", api, flags=re.M)
+    assert m, "SVT_HIP_TUS not found in svt_hip_api.cpp"
+    listed = re.findall(r"\bX\((\w+)\)", m.group(1))
+    assert len(listed) == len(set(listed)), f"listed twice: {sorted(n for n in set(listed) if listed.count(n) > 1)}"
+    assert sorted(listed) == stems, f"not in SVT_HIP_TUS: {sorted(set(stems) - set(listed))}; no such unit: {sorted(set(listed) - set(stems))}"
+    for s in stems:
+        probes = re.findall(r"^SVT_HIP_TU_PROBE\((\w+)\)", open(os.path.join(csrc, s + ".hip")).read(), flags=re.M)
+        assert probes == [s], f"{s}.hip: SVT_HIP_TU_PROBE({s}) expected, found {probes}"
+
+
 def test_search_window_matches_oracle(pkg, orc):
     import me_common as mc
     L = pkg.lib()

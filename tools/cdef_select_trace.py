@@ -1,4 +1,4 @@
-"""Per-phase wall-clock trace of the one-launch CDEF strength selection (joint_resident_kernel): needs percall2.hip built with -DSVT_RES_TRACE, which makes
+"""Per-phase wall-clock trace of the one-launch CDEF strength selection (joint_resident_kernel): needs cdef_select.hip built with -DSVT_RES_TRACE, which makes
 workgroups 0 and 133 write wall_clock64() at eight points of every step into the state's unused partial[3] rows.  argv[1] = byte offset of those rows in the state
 (offsetof(JointState, partial) + 3 * 64 * 4096 * 8 = 6327624 for the current layout).  Development tool; not part of bench.py or the tests."""
 import ctypes as C, os, sys, numpy as np, torch
