@@ -682,8 +682,11 @@ int svt_hip_obmc_cost_batch_dev(SvtHipCtx *ctx, const uint8_t *d_pre, int pre_st
 
 /* Warped (affine) prediction of a list of blocks of one plane: svt_av1_warp_affine / svt_av1_highbd_warp_affine (Common/Codec/EbWarpedMotion.c:577, :733),
  * the non-compound path of svt_warp_plane / svt_highbd_warp_plane.  mat = EbWarpedMotionParams::wmmat[0..5], alpha .. delta = its shear
- * parameters (svt_get_shear_params, :921, stays on the host); (p_col, p_row, p_width, p_height) = the block in the destination plane, sizes
- * multiples of 8; width / height / stride describe the reference plane (samples outside are clamped to its edges, as in the reference). */
+ * parameters (svt_get_shear_params, :921, stays on the host); (p_col, p_row, p_width, p_height) = the block in the destination plane, any size
+ * from 4 x 4 to 128 x 128: the block is predicted in 8 x 8 cells and the last cell of a row or column is cut to what the block leaves of it
+ * (the reference's AOMMIN(4, p_col + p_width - j - 4)), which is how the 4-wide chroma block of an 8 x 8 luma block is predicted; width /
+ * height / stride describe the reference plane, of any size from 1 x 1 (samples outside are clamped to its edges, as in the reference;
+ * ss_x and ss_y are independent: 4:2:2 is ss_x = 1, ss_y = 0). */
 typedef struct {
     int32_t mat[6];
     int16_t alpha, beta, gamma, delta;

@@ -1045,47 +1045,64 @@ def test_compound_prediction(orc, ref):
             b.src0_x += 64; b.src0_y += 64; b.src1_x += 64; b.src1_y += 64
         dst = np.zeros((H, W), dt); m_orc = masks.copy()
         orc.orc_compound_predict_batch(ref0.itemsize, bd, ptr(ref0), W, ptr(ref1), W, ptr(dst), W, ptr(m_orc), blks, 0, n)
-        pre = "svt_av1_highbd_" if hbd else "svt_av1_"
-        for i, b in enumerate(blks):
-            w, h = b.w, b.h
-            fx = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[b.bank_x])), 8, 16, 0)
-            fy = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[b.bank_y])), 8, 16, 0)
-            d16 = [np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint16)]
-            out = np.zeros((h, w), dt)
-            for r, (plane, sx_, sy_, px, py) in enumerate(((ref0, b.subpel0_x, b.subpel0_y, b.src0_x, b.src0_y), (ref1, b.subpel1_x, b.subpel1_y, b.src1_x, b.src1_y))):
-                cp = _ConvP(); cp.round_0 = r0; cp.round_1 = 7; cp.is_compound = 1; cp.dst = d16[r].ctypes.data; cp.dst_stride = w
-                name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(sx_ != 0), int(sy_ != 0))] + "_c"
-                sp = C.c_void_p(plane.ctypes.data + (py * W + px) * plane.itemsize)
-                args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), sx_, sy_, C.byref(cp)]
-                if hbd: args.append(bd)
-                getattr(ref, name)(*args)
-                mine = np.zeros((h, w), np.uint16)
-                orc.orc_jnt_convolve_d16(sp, W, plane.itemsize, w, h, b.bank_x, b.bank_y, sx_, sy_, bd, ptr(mine), w)
-                assert np.array_equal(mine, d16[r]), (bd, i, r, name)
-            cp = _ConvP(); cp.round_0 = r0; cp.round_1 = 7; cp.is_compound = 1
-            if b.type <= 1:      # second call with do_average: dst holds the first prediction
-                cp.dst = d16[0].ctypes.data; cp.dst_stride = w; cp.do_average = 1; cp.use_jnt_comp_avg = b.type
-                cp.fwd_offset, cp.bck_offset = b.fwd_offset, b.bck_offset
-                name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(b.subpel1_x != 0), int(b.subpel1_y != 0))] + "_c"
-                sp = C.c_void_p(ref1.ctypes.data + (b.src1_y * W + b.src1_x) * ref1.itemsize)
-                args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), b.subpel1_x, b.subpel1_y, C.byref(cp)]
-                if hbd: args.append(bd)
-                getattr(ref, name)(*args)
+        _compound_vs_ref(orc, ref, bd, ref0, ref1, blks, masks, dst, m_orc)
+
+
+def _compound_vs_ref(orc, ref, bd, ref0, ref1, blks, masks, dst, m_orc):
+    """every block of a list: both 16-bit intermediates, the stored DIFFWTD mask and the samples of plane dst against the reference's functions"""
+    dt, W = ref0.dtype, ref0.shape[1]
+    assert ref1.shape[1] == W
+    hbd = dt == np.uint16
+    r0 = 5 if bd == 12 else 3
+    pre = "svt_av1_highbd_" if hbd else "svt_av1_"
+    for i, b in enumerate(blks):
+        w, h = b.w, b.h
+        fx = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[b.bank_x])), 8, 16, 0)
+        fy = _IFP(C.addressof((C.c_int16 * 8 * 16).in_dll(ref, REF_BANKS[b.bank_y])), 8, 16, 0)
+        d16 = [np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint16)]
+        out = np.zeros((h, w), dt)
+        for r, (plane, sx_, sy_, px, py) in enumerate(((ref0, b.subpel0_x, b.subpel0_y, b.src0_x, b.src0_y), (ref1, b.subpel1_x, b.subpel1_y, b.src1_x, b.src1_y))):
+            cp = _ConvP(); cp.round_0 = r0; cp.round_1 = 7; cp.is_compound = 1; cp.dst = d16[r].ctypes.data; cp.dst_stride = w
+            name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(sx_ != 0), int(sy_ != 0))] + "_c"
+            sp = C.c_void_p(plane.ctypes.data + (py * W + px) * plane.itemsize)
+            args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), sx_, sy_, C.byref(cp)]
+            if hbd: args.append(bd)
+            getattr(ref, name)(*args)
+            mine = np.zeros((h, w), np.uint16)
+            orc.orc_jnt_convolve_d16(sp, W, plane.itemsize, w, h, b.bank_x, b.bank_y, sx_, sy_, bd, ptr(mine), w)
+            assert np.array_equal(mine, d16[r]), (bd, i, r, name)
+        cp = _ConvP(); cp.round_0 = r0; cp.round_1 = 7; cp.is_compound = 1
+        if b.type <= 1:      # second call with do_average: dst holds the first prediction
+            cp.dst = d16[0].ctypes.data; cp.dst_stride = w; cp.do_average = 1; cp.use_jnt_comp_avg = b.type
+            cp.fwd_offset, cp.bck_offset = b.fwd_offset, b.bck_offset
+            name = pre + "jnt_convolve_" + {(0, 0): "2d_copy", (1, 0): "x", (0, 1): "y", (1, 1): "2d"}[(int(b.subpel1_x != 0), int(b.subpel1_y != 0))] + "_c"
+            sp = C.c_void_p(ref1.ctypes.data + (b.src1_y * W + b.src1_x) * ref1.itemsize)
+            args = [sp, W, ptr(out), w, w, h, C.byref(fx), C.byref(fy), b.subpel1_x, b.subpel1_y, C.byref(cp)]
+            if hbd: args.append(bd)
+            getattr(ref, name)(*args)
+        else:
+            if b.type == 2:
+                seg = np.zeros((h, w), np.uint8)
+                ref.svt_av1_build_compound_diffwtd_mask_d16_c(ptr(seg), int(b.mask_type), ptr(d16[0]), w, ptr(d16[1]), w, h, w, C.byref(cp), bd)
+                if b.mask_off >= 0:
+                    assert np.array_equal(m_orc[b.mask_off:b.mask_off + w * h].reshape(h, w), seg), (bd, i, "seg mask")
+                mptr, mstride, sub = ptr(seg), w, 0
             else:
-                if b.type == 2:
-                    seg = np.zeros((h, w), np.uint8)
-                    ref.svt_av1_build_compound_diffwtd_mask_d16_c(ptr(seg), int(b.mask_type), ptr(d16[0]), w, ptr(d16[1]), w, h, w, C.byref(cp), bd)
-                    if b.mask_off >= 0:
-                        assert np.array_equal(m_orc[b.mask_off:b.mask_off + w * h].reshape(h, w), seg), (bd, i, "seg mask")
-                    mptr, mstride, sub = ptr(seg), w, 0
-                else:
-                    mptr, mstride, sub = C.c_void_p(masks.ctypes.data + b.mask_off), b.mask_stride, int(b.mask_sub)
-                if not hbd:
-                    ref.svt_aom_lowbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp))
-                else:
-                    ref.svt_aom_highbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp), bd)
-            got = dst[b.dst_y:b.dst_y + h, b.dst_x:b.dst_x + w]
-            assert np.array_equal(got, out), (bd, i, b.type, w, h, np.argwhere(got != out)[:4])
+                mptr, mstride, sub = C.c_void_p(masks.ctypes.data + b.mask_off), b.mask_stride, int(b.mask_sub)
+            if not hbd:
+                ref.svt_aom_lowbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp))
+            else:
+                ref.svt_aom_highbd_blend_a64_d16_mask_c(ptr(out), w, ptr(d16[0]), w, ptr(d16[1]), w, mptr, mstride, w, h, sub, sub, C.byref(cp), bd)
+        got = dst[b.dst_y:b.dst_y + h, b.dst_x:b.dst_x + w]
+        assert np.array_equal(got, out), (bd, i, b.type, w, h, np.argwhere(got != out)[:4])
+
+
+def test_compound_prediction_every_size_type_flavour(orc, ref):
+    """the same proof on the full product the device test launches (comp_common.compound_cases: 22 sizes x 4 types x 16 flavour pairs), every format"""
+    for bd, dt in ((8, None), (10, None), (12, None), (8, np.uint16)):
+        c = cmc.compound_cases(bd, dt)
+        _, _, exp, m_exp = cmc.compound_expected(orc, bd, dt)
+        _compound_vs_ref(orc, ref, bd, c.ref0, c.ref1, c.blks, c.masks, exp, m_exp)
 
 
 def test_obmc_sad_variance(orc, ref):
@@ -1102,15 +1119,30 @@ def test_obmc_sad_variance(orc, ref):
             xo, yo = (0, 0) if it < 3 else (int(rng.integers(0, 8)), int(rng.integers(0, 8)))
             out = np.zeros(3, np.uint32)
             orc.orc_obmc_block(ptr(pre), pre.shape[1], ptr(wsrc), ptr(mask), w, h, xo, yo, ptr(out))
-            sad = getattr(ref, f"svt_aom_obmc_sad{w}x{h}_c")(ptr(pre), pre.shape[1], ptr(wsrc), ptr(mask))
-            sse = C.c_uint32(0)
-            if xo == 0 and yo == 0:
-                var = getattr(ref, f"svt_aom_obmc_variance{w}x{h}_c")(ptr(pre), pre.shape[1], ptr(wsrc), ptr(mask), C.byref(sse))
-                var2 = getattr(ref, f"svt_aom_obmc_sub_pixel_variance{w}x{h}_c")(ptr(pre), pre.shape[1], 0, 0, ptr(wsrc), ptr(mask), C.byref(sse))
-                assert (var & 0xFFFFFFFF) == (var2 & 0xFFFFFFFF)
-            else:
-                var = getattr(ref, f"svt_aom_obmc_sub_pixel_variance{w}x{h}_c")(ptr(pre), pre.shape[1], xo, yo, ptr(wsrc), ptr(mask), C.byref(sse))
-            assert (int(out[0]), int(out[1]), int(out[2])) == (sad & 0xFFFFFFFF, sse.value, var & 0xFFFFFFFF), (w, h, it, xo, yo)
+            assert (int(out[0]), int(out[1]), int(out[2])) == _obmc_ref(ref, pre, wsrc, mask, w, h, xo, yo), (w, h, it, xo, yo)
+
+
+def _obmc_ref(ref, pre, wsrc, mask, w, h, xo, yo):
+    """(sad, sse, variance) of the reference's three functions; pre: a 2-D view whose first sample is the block's, wsrc / mask: the block's w * h values"""
+    pp, stride = C.c_void_p(pre.ctypes.data), pre.strides[0]
+    sad = getattr(ref, f"svt_aom_obmc_sad{w}x{h}_c")(pp, stride, ptr(wsrc), ptr(mask))
+    sse = C.c_uint32(0)
+    if xo == 0 and yo == 0:
+        var = getattr(ref, f"svt_aom_obmc_variance{w}x{h}_c")(pp, stride, ptr(wsrc), ptr(mask), C.byref(sse))
+        var2 = getattr(ref, f"svt_aom_obmc_sub_pixel_variance{w}x{h}_c")(pp, stride, 0, 0, ptr(wsrc), ptr(mask), C.byref(sse))
+        assert (var & 0xFFFFFFFF) == (var2 & 0xFFFFFFFF)
+    else:
+        var = getattr(ref, f"svt_aom_obmc_sub_pixel_variance{w}x{h}_c")(pp, stride, xo, yo, ptr(wsrc), ptr(mask), C.byref(sse))
+    return sad & 0xFFFFFFFF, sse.value, var & 0xFFFFFFFF
+
+
+def test_obmc_every_size_offset_content(orc, ref):
+    """the oracle's results on comp_common.obmc_cases (22 sizes x four offset classes x four contents, what the device test launches) == the reference's"""
+    c = cmc.obmc_cases()
+    exp = cmc.obmc_expected(orc)
+    for i, (b, d) in enumerate(zip(c.blks, c.desc)):
+        got = _obmc_ref(ref, c.pre[b.pre_y:, b.pre_x:], c.wsrc[b.wm_off:b.wm_off + b.w * b.h], c.mask[b.wm_off:b.wm_off + b.w * b.h], b.w, b.h, b.xoffset, b.yoffset)
+        assert tuple(int(v) for v in exp[i]) == got, (i, d)
 
 
 def test_warp_affine(orc, ref):
@@ -1127,15 +1159,65 @@ def test_warp_affine(orc, ref):
         for ss in (0, 1):
             for i, b in enumerate(blks):
                 w, h = b.p_width, b.p_height
-                a = np.zeros((h, w), dt); e = np.zeros((h, w), dt)
+                a = np.zeros((h, w), dt)
                 mat = (C.c_int32 * 8)(*list(b.mat), 0, 0)
-                cp = _ConvP(); cp.round_0 = 5 if bd == 12 else 3; cp.round_1 = 2 * 7 - cp.round_0
-                if dt == np.uint8:
-                    ref.svt_av1_warp_affine_c(mat, ptr(plane), W, H, W, ptr(e), b.p_col, b.p_row, w, h, w, ss, ss, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)
-                else:
-                    ref.svt_av1_highbd_warp_affine_c(mat, ptr(plane), W, H, W, ptr(e), b.p_col, b.p_row, w, h, w, ss, ss, bd, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)
+                e = _warp_ref(ref, b, plane, W, H, W, bd, (ss, ss))
                 orc.orc_warp_affine(mat, ptr(plane), plane.itemsize, bd, W, H, W, ptr(a), b.p_col, b.p_row, w, h, w, ss, ss, b.alpha, b.beta, b.gamma, b.delta)
                 assert np.array_equal(a, e), (bd, ss, i, w, h, np.argwhere(a != e)[:4])
+
+
+def _warp_ref(ref, b, plane, width, height, stride, bd, ss, comp=None):
+    """one record through svt_av1_[highbd_]warp_affine_c -> its w x h samples.  comp = (convbuf, cb_off, cb_stride, do_average, use_jnt_comp_avg, fwd, bck): the
+    is_compound branches on the 16-bit buffer convbuf (written in place when do_average is 0)"""
+    w, h = b.p_width, b.p_height
+    e = np.zeros((h, w), plane.dtype)
+    mat = (C.c_int32 * 8)(*list(b.mat), 0, 0)
+    cp = _ConvP(); cp.round_0 = 5 if bd == 12 else 3; cp.round_1 = 2 * 7 - cp.round_0
+    if comp:
+        cb, off, cbs, avg, jnt, fwd, bck = comp
+        cp.round_1 = 7; cp.is_compound = 1; cp.dst = cb.ctypes.data + 2 * off; cp.dst_stride = cbs
+        cp.do_average, cp.use_jnt_comp_avg, cp.fwd_offset, cp.bck_offset = avg, jnt, fwd, bck
+    args = (mat, ptr(plane), width, height, stride, ptr(e), b.p_col, b.p_row, w, h, w, ss[0], ss[1])
+    if plane.dtype == np.uint8: ref.svt_av1_warp_affine_c(*args, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)
+    else: ref.svt_av1_highbd_warp_affine_c(*args, bd, C.byref(cp), b.alpha, b.beta, b.gamma, b.delta)
+    return e
+
+
+WARP_FMTS = ((8, np.uint8), (10, np.uint16), (12, np.uint16), (8, np.uint16))
+
+
+def test_warp_every_size_edge_ss(orc, ref):
+    """the oracle on comp_common.warp_cases == the reference: 4-wide and 4-high blocks (the reference cuts the last cell of a row or column with
+    AOMMIN(4, p_col + p_width - j - 4), so any size is within what it accepts), cells beyond and astride every edge, a 6 x 5 plane (every index is clamped: any
+    plane from 1 x 1 up is accepted), 4:4:4, 4:2:0 and 4:2:2"""
+    for bd, dt in WARP_FMTS:
+        for ss in cmc.WARP_SS:
+            for lst in cmc.warp_cases(ss):
+                plane, _, exp = cmc.warp_expected(orc, lst, ss, bd, dt)
+                w, h, stride = lst.plane
+                for i, (b, d) in enumerate(zip(lst.blks, lst.desc)):
+                    e = _warp_ref(ref, b, plane, w, h, stride, bd, ss)
+                    a = exp[b.p_row:b.p_row + b.p_height, b.p_col:b.p_col + b.p_width]
+                    assert np.array_equal(a, e), (bd, ss, lst.name, i, d, np.argwhere(a != e)[:4])
+
+
+def test_warp_compound_batch(orc, ref):
+    """orc_warp_compound_batch == the is_compound branches of svt_av1_[highbd_]warp_affine_c (Common/Codec/EbWarpedMotion.c:660-683, :812-835) on the four
+    launches of comp_common.warp_comp_cases: first pass into the compound buffer, second pass averaged or distance-weighted into pixels, both mixed, no
+    destination plane"""
+    w, h, stride = cmc.WARP_PLANE
+    for bd, dt in WARP_FMTS:
+        for ss in cmc.WARP_SS:
+            c = cmc.warp_comp_cases(ss)
+            planes, steps = cmc.warp_comp_expected(orc, c, bd, dt)
+            for n, l in enumerate(c.lists):
+                cb, dst = steps[n][0].copy(), steps[n][1].copy()
+                for b in l.blks:
+                    e = _warp_ref(ref, b.blk, planes[l.which], w, h, stride, bd, ss, (cb, b.cb_off, b.cb_stride, b.do_average, b.use_jnt_comp_avg, b.fwd_offset, b.bck_offset))
+                    if b.do_average: dst[b.blk.p_row:b.blk.p_row + b.blk.p_height, b.blk.p_col:b.blk.p_col + b.blk.p_width] = e
+                    else: assert not e.any()                       # a first pass leaves the pixels alone
+                assert np.array_equal(cb, steps[n + 1][0]) and np.array_equal(dst, steps[n + 1][1]), (bd, ss, l.name)
+                assert not np.array_equal(cb, steps[n][0]) or not np.array_equal(dst, steps[n][1])
 
 
 def test_warp_filter_table_headers(ref):
@@ -1161,21 +1243,40 @@ def test_blend_a64_masks(orc, ref):
         out = a.copy()                      # dst plane = src0 plane, so that the "in place" blocks really alias
         orc.orc_blend_a64_batch(a.itemsize, ptr(out), W, ptr(b1), W, ptr(out), W, ptr(masks), blks, n)
         run = a.copy()                      # the same sequence through the reference functions, block by block
-        for i, b in enumerate(blks):
-            w, h = b.w, b.h
-            s0 = np.ascontiguousarray(run[b.src0_y:b.src0_y + h, b.src0_x:b.src0_x + w]); s1 = np.ascontiguousarray(b1[b.src1_y:b.src1_y + h, b.src1_x:b.src1_x + w])
-            e = np.zeros((h, w), dt)
-            mp = C.c_void_p(masks.ctypes.data + b.mask_off)
-            if bd == 8:
-                if b.mode == 0: ref.svt_aom_blend_a64_mask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, b.mask_stride, w, h, int(b.subw), int(b.subh))
-                elif b.mode == 1: ref.svt_aom_blend_a64_hmask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h)
-                else: ref.svt_aom_blend_a64_vmask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h)
-            else:
-                if b.mode == 0: ref.svt_aom_highbd_blend_a64_mask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, b.mask_stride, w, h, int(b.subw), int(b.subh), bd)
-                elif b.mode == 1: ref.svt_aom_highbd_blend_a64_hmask_8bit_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h, bd)
-                else: ref.svt_aom_highbd_blend_a64_vmask_8bit_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h, bd)
-            run[b.dst_y:b.dst_y + h, b.dst_x:b.dst_x + w] = e
+        _blend_ref(ref, bd, run, b1, run, masks, blks)
         assert np.array_equal(out, run) and (out != a).any(), bd
+
+
+def _blend_ref(ref, bd, src0, b1, run, masks, blks):
+    """a block list through the reference's blend functions in order: src0 / b1 -> run (src0 may be run itself: in place)"""
+    dt = run.dtype
+    for i, b in enumerate(blks):
+        w, h = b.w, b.h
+        s0 = np.ascontiguousarray(src0[b.src0_y:b.src0_y + h, b.src0_x:b.src0_x + w]); s1 = np.ascontiguousarray(b1[b.src1_y:b.src1_y + h, b.src1_x:b.src1_x + w])
+        e = np.zeros((h, w), dt)
+        mp = C.c_void_p(masks.ctypes.data + b.mask_off)
+        if bd == 8:
+            if b.mode == 0: ref.svt_aom_blend_a64_mask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, b.mask_stride, w, h, int(b.subw), int(b.subh))
+            elif b.mode == 1: ref.svt_aom_blend_a64_hmask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h)
+            else: ref.svt_aom_blend_a64_vmask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h)
+        else:
+            if b.mode == 0: ref.svt_aom_highbd_blend_a64_mask_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, b.mask_stride, w, h, int(b.subw), int(b.subh), bd)
+            elif b.mode == 1: ref.svt_aom_highbd_blend_a64_hmask_8bit_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h, bd)
+            else: ref.svt_aom_highbd_blend_a64_vmask_8bit_c(ptr(e), w, ptr(s0), w, ptr(s1), w, mp, w, h, bd)
+        run[b.dst_y:b.dst_y + h, b.dst_x:b.dst_x + w] = e
+
+
+def test_blend_every_size_mode_mask(orc, ref):
+    """the oracle on comp_common.blend_cases, in place and out of place, 8-bit and 16-bit samples up to 4095 (bd 12) == the reference"""
+    for in_place in (True, False):
+        c = cmc.blend_cases(in_place)
+        for bd, dt in ((8, np.uint8), (12, np.uint16)):
+            a, b1, dst0 = cmc.blend_planes(c, dt)
+            exp = dst0.copy()
+            orc.orc_blend_a64_batch(a.itemsize, ptr(exp if in_place else a), c.w, ptr(b1), c.w, ptr(exp), c.w, ptr(c.masks), c.blks, c.n)
+            run = dst0.copy()
+            _blend_ref(ref, bd, run if in_place else a, b1, run, c.masks, c.blks)
+            assert np.array_equal(exp, run) and (exp != dst0).any(), (in_place, bd)
 
 
 def test_picture_format_conversions(orc, ref):
