@@ -1,6 +1,7 @@
 /*
  * svt_hip.h — C ABI of libsvtav1_hip.so: the MI355X (gfx950) implementation of SVT-AV1's
- * per-superblock hot path (open-loop ME, transform/quant, in-loop filters).
+ * per-superblock hot path (open-loop ME, transform/quant, in-loop filters) and of the look-ahead's source-side chain
+ * (open-loop intra search, TPL flow dispenser, TPL flow synthesizer with r0 / beta / lambda factors, global motion).
  *
  * This is the drop-in boundary.  The reference binds kernels through global function pointers
  * (Source/Lib/Encoder/Codec/aom_dsp_rtcd.h, Source/Lib/Common/Codec/common_dsp_rtcd.h) that are
@@ -1102,6 +1103,73 @@ int svt_hip_tpl_dispenser_picture_dev(SvtHipCtx *ctx, const SvtHipTplParams *p, 
 /* Measurement only (tools/tpl_time.py): which parts svt_hip_tpl_dispenser_picture_dev launches, bit 0 = phase A (inter search, decisions, inter macroblocks),
  * bit 1 = phase B (the intra steps), bit 2 = the padding.  The default, 7, is the only value that computes the dispenser. */
 int svt_hip_tpl_set_phases(SvtHipCtx *ctx, int mask);
+
+/* ------------------------------------------------------------------ TPL flow synthesizer, r0 / beta / lambda factors -------------------------
+ * The rest of tpl_mc_flow (Encoder/Codec/EbRateControlProcess.c:1154-1197) after the dispenser, on the records the dispenser left on the device:
+ * tpl_mc_flow_synthesizer -> tpl_model_update -> tpl_model_update_b (:887-998) for every picture of the sliding window, last picture first, then
+ * generate_r0beta (:1000-1075) with generate_lambda_scaling_factor (:39-84) on the window's first picture.  The accumulators TplStats.mc_dep_rate and
+ * mc_dep_dist are int64_t (Encoder/Codec/EbCodingUnit.h:421-430) and every scatter adds an integer computed from the scattering block alone (:940-944), so
+ * 64-bit atomic adds give the reference's sums in any order; the floating point is per block (:911-914, :73-79, :1020-1022, :1065-1071) and IEEE exact.
+ *
+ * Grid.  cell_log2 is 4 (the reference's is_720p_or_larger, min(w, h) >= 720: EbPictureControlSet.c:1252) or 3; s = 4 - cell_log2.  A picture's grid is
+ * [mb_rows << s][mb_cols << s] cells (mb_cols = (w + 15) / 16, mb_rows = (h + 15) / 16: the reference's mi_cols_sr >> shift stride), a cell is
+ * int64_t[2] = {mc_dep_rate, mc_dep_dist}; svt_hip_tpl_dep_bytes(w, h, cell_log2) is its size (0 for arguments the entry points refuse).  The other TplStats
+ * fields of a cell are those of its macroblock's SvtHipTplMbStats record (result_model_store replicates them, :130-161).
+ *
+ * Source blocks.  One per cell: a macroblock, or each of its four 8x8 quarters (the quarters past mi_rows / mi_cols of a trailing half macroblock too, as
+ * the reference's loops at :966-967 run them).  A block reads its macroblock's record and the mc_dep_* of ITS OWN cell, moves by GET_MV_RAWPEL of the
+ * record's vector (Common/Codec/EbBlockStructures.h:41-60) and adds into the up to four cells of the target picture it overlaps (round_floor, :847-855; a
+ * target cell is accepted only inside the aligned picture, 0 <= row < h and 0 <= col < w in samples, :927-928).
+ *   rf_idx == -1: the reference's ref_frame_poc keeps its memset value 0 with a zero vector (:579, :795-798): the target is ref_window[0] and the record's
+ *                 vector is not read.  rf_idx outside -1 .. 6: no target.
+ *   recrf_dist == 0: the reference divides by zero; here the propagated part mc_dep_dist' is 0.  A double outside int64_t converts to INT64_MIN, NaN to 0.
+ *
+ * rate must be 0 (the reference's tpl_opt_flag == 1): delta_rate_cost (:857-883) goes through libm's log and pow on doubles and is not built; mc_dep_rate'
+ * is 0, the records' recrf_rate - srcrf_rate is still scattered and the full RDCOST (EbRateDistortionCost.h:104-107) is still evaluated.
+ *
+ * Stream-ordered and asynchronous: no host synchronisation, no allocation, no read-back.  The frame descriptors are host memory, read during the call. */
+#define SVT_HIP_TPL_MAX_WINDOW 60   /* MAX_TPL_LA_SW */
+
+typedef struct {
+    const SvtHipTplMbStats *d_stats;   /* [n_mb] the dispenser's records of this picture */
+    int64_t *d_dep;                    /* this picture's grid, svt_hip_tpl_dep_bytes(w, h, cell_log2) bytes; no two pictures share one */
+    int32_t on;                        /* the reference's tpl_on (:1182-1191): 0 = not synthesized, d_stats is never read as a source; still a target */
+    int32_t ref_window[8];             /* [rf_idx + 1] = window index of the picture that slot names (the first i with picture_number == the slot's POC,
+                                          :972-976), -1 = not in the window.  Entry 0 serves rf_idx == -1: the index of the picture whose picture_number is
+                                          0; it may be this picture's own index (the zero vector then adds into the block's own cell only).  An entry
+                                          1..7 equal to this picture's own index is refused: the result would depend on the order of the blocks. */
+    int32_t reserved;
+} SvtHipTplWindowFrame;
+
+typedef struct {
+    int32_t w, h;                      /* luma size: multiples of 8, >= 16 */
+    int32_t cell_log2;                 /* 4 or 3 */
+    int32_t sb_size;                   /* 64 or 128 */
+    int32_t base_rdmult;               /* pcs->base_rdmult, >= 0 */
+    int32_t rate;                      /* must be 0 */
+    double r0_in;                      /* pcs->r0 before the call: kept when mc_dep_cost_base == 0 (:1020-1022) */
+} SvtHipTplSynthParams;
+
+typedef struct {                       /* the head of d_out */
+    double r0;
+    int64_t intra_cost_base, mc_dep_cost_base;   /* the reference's DEBUG_TPL values (:1023-1030) */
+} SvtHipTplR0BetaHeader;
+
+size_t svt_hip_tpl_dep_bytes(int w, int h, int cell_log2);
+/* d_out: SvtHipTplR0BetaHeader, then double factors[mb_rows * mb_cols] (tpl_rdmult_scaling_factors), then double beta[sb_rows * sb_cols] (tpl_beta),
+ * sb_cols = (w + sb_size - 1) / sb_size.  0 for arguments the entry points refuse. */
+size_t svt_hip_tpl_r0beta_out_bytes(int w, int h, int sb_size);
+size_t svt_hip_tpl_r0beta_scratch_bytes(void);
+/* The scatter of window picture frame_idx (tpl_mc_flow_synthesizer(pcs_array, frame_idx, frames_in_sw)); nothing is launched when that picture is off. */
+int svt_hip_tpl_synth_picture_dev(SvtHipCtx *ctx, const SvtHipTplSynthParams *params, const SvtHipTplWindowFrame *frames, int n_frames, int frame_idx);
+/* generate_r0beta on one picture: d_stats its records (only recrf_dist is read; the reference has zeros there for a picture that is off), d_dep its grid. */
+int svt_hip_tpl_r0beta_dev(SvtHipCtx *ctx, const SvtHipTplSynthParams *params, const SvtHipTplMbStats *d_stats, const int64_t *d_dep, void *d_out,
+                           void *d_scratch);
+/* The whole window: every grid zeroed (:1159-1163), the scatters of pictures n_frames - 1 .. 0 that are on, generate_r0beta on picture 0.  Every grid stays
+ * on the device. */
+int svt_hip_tpl_window_dev(SvtHipCtx *ctx, const SvtHipTplSynthParams *params, const SvtHipTplWindowFrame *frames, int n_frames, void *d_out, void *d_scratch);
+/* The same contract on host pointers (d_stats, d_dep and out are host memory), serial, no context. */
+int svt_hip_tpl_window_host(const SvtHipTplSynthParams *params, const SvtHipTplWindowFrame *frames, int n_frames, void *out);
 
 /* ------------------------------------------------------------------ global motion: warp error and parameter refinement -----------------------
  * The source-only arithmetic of compute_global_motion (Encoder/Codec/EbGlobalMotionEstimation.c:171-405) after the model fit: the warp error of

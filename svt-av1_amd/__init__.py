@@ -176,6 +176,22 @@ class TplMbStats(C.Structure):
                 ("pad1", C.c_uint16)]
 
 
+class TplWindowFrame(C.Structure):
+    """SvtHipTplWindowFrame (include/svt_hip.h): d_stats / d_dep are device pointers for the *_dev entry points, host pointers for tpl_window_host."""
+    _fields_ = [("d_stats", C.c_void_p), ("d_dep", C.c_void_p), ("on", C.c_int32), ("ref_window", C.c_int32 * 8), ("reserved", C.c_int32)]
+
+
+class TplSynthParams(C.Structure):
+    """SvtHipTplSynthParams (include/svt_hip.h)."""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("cell_log2", C.c_int32), ("sb_size", C.c_int32), ("base_rdmult", C.c_int32), ("rate", C.c_int32),
+                ("r0_in", C.c_double)]
+
+
+class TplR0BetaHeader(C.Structure):
+    """SvtHipTplR0BetaHeader (include/svt_hip.h)."""
+    _fields_ = [("r0", C.c_double), ("intra_cost_base", C.c_int64), ("mc_dep_cost_base", C.c_int64)]
+
+
 class GmModel(C.Structure):
     """SvtHipGmModel (include/svt_hip.h)."""
     _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16), ("valid", C.c_int32)]
@@ -230,6 +246,7 @@ GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
 GM_FIT_MAX_JOBS = 64   # SVT_HIP_GM_FIT_MAX_JOBS
 GM_MAX_CORNERS = 4096   # SVT_HIP_GM_MAX_CORNERS
 TPL_MAX_REFS = 7   # MAX_PA_ME_MV: slots 0..3 list 0, 4..6 list 1
+TPL_MAX_WINDOW = 60   # SVT_HIP_TPL_MAX_WINDOW (MAX_TPL_LA_SW)
 
 
 def tpl_stats_grid(stats, is_720p_or_larger):
@@ -239,6 +256,68 @@ def tpl_stats_grid(stats, is_720p_or_larger):
     import numpy as np
     rep = 1 if is_720p_or_larger else 2
     return np.repeat(np.repeat(stats, rep, axis=0), rep, axis=1)
+
+
+def tpl_cell_log2(w, h):
+    """The reference's is_720p_or_larger (EbPictureControlSet.c:1252): 16x16 cells when min(w, h) >= 720, else 8x8."""
+    return 4 if min(w, h) >= 720 else 3
+
+
+def tpl_ref_window(window_pocs, slot_pocs):
+    """SvtHipTplWindowFrame.ref_window of one picture: `window_pocs` the picture_number of every window picture in window order, `slot_pocs` the POC of the
+    picture's up to 7 reference slots (None = slot unused).  Entry rf_idx + 1 = the first window index with that POC (tpl_model_update's search,
+    EbRateControlProcess.c:972-976), -1 when there is none; entry 0 serves rf_idx == -1, whose ref_frame_poc is the memset's 0 (:579)."""
+    pocs = list(window_pocs)
+    first = lambda poc: pocs.index(poc) if poc is not None and poc in pocs else -1
+    slots = list(slot_pocs) + [None] * (TPL_MAX_REFS - len(slot_pocs))
+    return [first(0)] + [first(p) for p in slots[:TPL_MAX_REFS]]
+
+
+def tpl_synth_params(w, h, base_rdmult, r0_in=0.0, sb_size=64, cell_log2=None, rate=0):
+    P = TplSynthParams()
+    P.w, P.h, P.cell_log2, P.sb_size, P.base_rdmult, P.rate, P.r0_in = w, h, tpl_cell_log2(w, h) if cell_log2 is None else cell_log2, sb_size, base_rdmult, rate, r0_in
+    return P
+
+
+def tpl_window_frames(frames):
+    """A ctypes array of TplWindowFrame from (stats pointer, grid pointer, on, ref_window) tuples; pointers are ints, c_void_p or None."""
+    arr = (TplWindowFrame * len(frames))()
+    for f, (d_stats, d_dep, on, ref_window) in zip(arr, frames):
+        f.d_stats = getattr(d_stats, "value", d_stats)
+        f.d_dep = getattr(d_dep, "value", d_dep)
+        f.on = int(on)
+        f.ref_window[:] = list(ref_window)
+    return arr
+
+
+def tpl_split_out(raw, params):
+    """The bytes of d_out -> dict(r0, intra_cost_base, mc_dep_cost_base, factors [mb_rows][mb_cols], beta [sb_rows][sb_cols])."""
+    import numpy as np
+    mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
+    sbw, sbh = (params.w + params.sb_size - 1) // params.sb_size, (params.h + params.sb_size - 1) // params.sb_size
+    raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+    hd = TplR0BetaHeader.from_buffer_copy(raw[:C.sizeof(TplR0BetaHeader)].tobytes())
+    body = raw[C.sizeof(TplR0BetaHeader):].view(np.float64)
+    return dict(r0=hd.r0, intra_cost_base=hd.intra_cost_base, mc_dep_cost_base=hd.mc_dep_cost_base, factors=body[:mbw * mbh].reshape(mbh, mbw).copy(),
+                beta=body[mbw * mbh:mbw * mbh + sbw * sbh].reshape(sbh, sbw).copy())
+
+
+def tpl_window_host(params, stats, on, ref_windows):
+    """svt_hip_tpl_window_host: `stats` one [mb_rows][mb_cols] structured array (TplMbStats fields) per window picture (None allowed for a picture that is
+    off, except picture 0), `on` and `ref_windows` per picture.  Returns (the tpl_split_out dict, the grids as [n][rows][cols][2] int64)."""
+    import numpy as np
+    L = lib()
+    s = 4 - params.cell_log2
+    mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
+    n = len(stats)
+    held = [None if a is None else np.ascontiguousarray(a, np.dtype(TplMbStats)) for a in stats]
+    dep = np.full((n, mbh << s, mbw << s, 2), 0x5A5A5A5A5A5A5A5A, np.int64)
+    out = np.zeros(max(L.svt_hip_tpl_r0beta_out_bytes(params.w, params.h, params.sb_size), 8) // 8, np.float64)
+    frames = tpl_window_frames([(None if a is None else a.ctypes.data, dep[i].ctypes.data, on[i], ref_windows[i]) for i, a in enumerate(held)])
+    rc = L.svt_hip_tpl_window_host(C.byref(params), frames, n, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_tpl_window_host refused its arguments: status {rc}")
+    return tpl_split_out(out, params), dep
 
 
 INTRA_EDGE_RECORD = 320   # samples of one edge record: 160 "above" + 160 "left", sample 0 at element 16 of each
@@ -400,6 +479,16 @@ def lib():
     L.svt_hip_tpl_dispenser_scratch_bytes.restype = C.c_size_t
     L.svt_hip_tpl_set_phases.argtypes = [vp, i32]
     L.svt_hip_tpl_dispenser_picture_dev.argtypes = [vp, C.POINTER(TplParams), u8p, i32, C.POINTER(TplRef), vp, u8p, u8p, vp, u8p, i32, vp, vp]
+    L.svt_hip_tpl_dep_bytes.argtypes = [i32, i32, i32]
+    L.svt_hip_tpl_dep_bytes.restype = C.c_size_t
+    L.svt_hip_tpl_r0beta_out_bytes.argtypes = [i32, i32, i32]
+    L.svt_hip_tpl_r0beta_out_bytes.restype = C.c_size_t
+    L.svt_hip_tpl_r0beta_scratch_bytes.argtypes = []
+    L.svt_hip_tpl_r0beta_scratch_bytes.restype = C.c_size_t
+    L.svt_hip_tpl_synth_picture_dev.argtypes = [vp, C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, i32]
+    L.svt_hip_tpl_r0beta_dev.argtypes = [vp, C.POINTER(TplSynthParams), vp, vp, vp, vp]
+    L.svt_hip_tpl_window_dev.argtypes = [vp, C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, vp, vp]
+    L.svt_hip_tpl_window_host.argtypes = [C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, vp]
     L.svt_hip_gm_error_table.argtypes = [vp]
     L.svt_hip_gm_shear_params_batch_dev.argtypes = [vp, vp, i32, vp]
     L.svt_hip_gm_warp_error_batch_dev.argtypes = [vp, u8p, i32, i32, i32, u8p, i32, i32, i32, vp, i32, vp]
@@ -598,6 +687,45 @@ class Context:
         top_left = C.c_void_p(d_recon.value - pad * recon_stride - pad)
         self.check(self.L.svt_hip_memcpy2d_d2h(self.h, out.ctypes.data_as(C.c_void_p), out.shape[1], top_left, recon_stride, out.shape[1], out.shape[0]), "d2h 2d")
         return out
+
+    # ---- TPL flow synthesizer, r0 / beta / lambda factors
+    def tpl_window(self, params, frames, d_out=None, d_scratch=None):
+        """svt_hip_tpl_window_dev on resident records and grids: `frames` a TplWindowFrame array (tpl_window_frames) of device pointers.  Every grid stays on
+        the device.  Returns the tpl_split_out dict; with the caller's d_out / d_scratch nothing is allocated here."""
+        import numpy as np
+        nbytes = self.L.svt_hip_tpl_r0beta_out_bytes(params.w, params.h, params.sb_size)
+        own = [] if d_out is not None else [self.empty(nbytes)]
+        own += [] if d_scratch is not None else [self.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())]
+        o = d_out if d_out is not None else own[0]
+        sc = d_scratch if d_scratch is not None else own[-1]
+        try:
+            self.check(self.L.svt_hip_tpl_window_dev(self.h, C.byref(params), frames, len(frames), o, sc), "tpl_window")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return tpl_split_out(self.to_host(o, (nbytes,), np.uint8), params)
+        finally:
+            self.free(*own)
+
+    def tpl_synth_picture(self, params, frames, frame_idx):
+        """svt_hip_tpl_synth_picture_dev: the scatter of window picture frame_idx into the grids the descriptors name (nothing is zeroed)."""
+        self.check(self.L.svt_hip_tpl_synth_picture_dev(self.h, C.byref(params), frames, len(frames), frame_idx), "tpl_synth_picture")
+
+    def tpl_r0beta(self, params, d_stats, d_dep):
+        """svt_hip_tpl_r0beta_dev on one picture's resident records and grid -> the tpl_split_out dict."""
+        import numpy as np
+        nbytes = self.L.svt_hip_tpl_r0beta_out_bytes(params.w, params.h, params.sb_size)
+        d_out, d_scratch = self.empty(nbytes), self.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())
+        try:
+            self.check(self.L.svt_hip_tpl_r0beta_dev(self.h, C.byref(params), d_stats, d_dep, d_out, d_scratch), "tpl_r0beta")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return tpl_split_out(self.to_host(d_out, (nbytes,), np.uint8), params)
+        finally:
+            self.free(d_out, d_scratch)
+
+    def tpl_dep_to_host(self, params, d_dep):
+        """One picture's grid: [rows][cols][2] int64 = {mc_dep_rate, mc_dep_dist} per cell."""
+        import numpy as np
+        s = 4 - params.cell_log2
+        return self.to_host(d_dep, (((params.h + 15) // 16) << s, ((params.w + 15) // 16) << s, 2), np.int64)
 
     # ---- global motion
     def gm_shear_params_batch(self, wmmat):

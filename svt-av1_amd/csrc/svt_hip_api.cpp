@@ -10,6 +10,7 @@
 #include <vector>
 #include "svt_hip_internal.h"
 #include "svt_hip_host.h"
+#include "tpl_synth.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -259,7 +260,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     return SVT_HIP_OK;
 }
 #define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
-    X(tfilter) X(tpl) X(txfm2d) X(warp) X(wiener)
+    X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
 #undef X
@@ -354,6 +355,82 @@ int svt_hip_tpl_set_phases(SvtHipCtx* c, int mask) {
     if (!c || mask < 0 || mask > 7) return bad_arg(c);
     c->tpl_phases = mask;
     return SVT_HIP_OK;
+}
+
+/* ---------------------------------------------------------------------------------- TPL synthesizer, r0 / beta */
+size_t svt_hip_tpl_dep_bytes(int w, int h, int cell_log2) {
+    if (!tplsyn::size_ok(w, h) || (cell_log2 != 3 && cell_log2 != 4)) return 0;
+    return tplsyn::dep_cells(tplsyn::geom(w, h, cell_log2)) * 2 * sizeof(int64_t);
+}
+size_t svt_hip_tpl_r0beta_out_bytes(int w, int h, int sb_size) {
+    if (!tplsyn::size_ok(w, h) || (sb_size != 64 && sb_size != 128)) return 0;
+    return tplsyn::out_bytes(w, h, sb_size);
+}
+size_t svt_hip_tpl_r0beta_scratch_bytes(void) { return 256; }   // the two base sums, a cache line of their own
+
+// what the entry points refuse alike, as one test (docs/design/kernels-overview.md); the texts stay literals at the call sites
+enum { TPL_SYNTH_FINE = 0, TPL_SYNTH_RATE, TPL_SYNTH_PARAMS, TPL_SYNTH_SELF, TPL_SYNTH_FRAMES };
+static int tpl_synth_refusal(const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int n_frames, bool with_frames) {
+    if (p && p->rate != 0) return TPL_SYNTH_RATE;
+    if (!tplsyn::params_ok(p)) return TPL_SYNTH_PARAMS;
+    const int bad = with_frames ? tplsyn::frames_check(frames, n_frames) : 0;
+    return bad == 2 ? TPL_SYNTH_SELF : bad ? TPL_SYNTH_FRAMES : TPL_SYNTH_FINE;
+}
+
+static int tpl_synth_launch(SvtHipCtx* c, const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int idx) {
+    const SvtHipTplWindowFrame& f = frames[idx];
+    int64_t* target[8];
+    for (int k = 0; k < 8; k++) target[k] = f.ref_window[k] < 0 ? nullptr : frames[f.ref_window[k]].d_dep;
+    return launched(c, svt_hip_launch_tpl_synth(c->stream, p->w, p->h, p->cell_log2, f.d_stats, f.d_dep, target), "tpl synthesizer launch");
+}
+
+int svt_hip_tpl_synth_picture_dev(SvtHipCtx* c, const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int n_frames, int frame_idx) {
+    SVT_HIP_ENTER(c);
+    if (!c) return bad_arg(c);
+    switch (tpl_synth_refusal(p, frames, n_frames, true)) {
+    case TPL_SYNTH_RATE: return bad_arg(c, "svt_hip_tpl_synth_picture_dev: rate must be 0 (the reference's tpl_opt_flag == 1; delta_rate_cost is not built)");
+    case TPL_SYNTH_PARAMS: return bad_arg(c, "svt_hip_tpl_synth_picture_dev: bad argument (w, h multiples of 8 and >= 16, cell_log2 3 or 4, sb_size 64 or 128, base_rdmult >= 0)");
+    case TPL_SYNTH_SELF: return bad_arg(c, "svt_hip_tpl_synth_picture_dev: ref_window[1..7] names the picture itself (the result would depend on the order of the blocks)");
+    case TPL_SYNTH_FRAMES:
+        return bad_arg(c, "svt_hip_tpl_synth_picture_dev: bad argument (1 <= n_frames <= 60, every d_dep distinct and non-NULL, d_stats of picture 0 and of every picture "
+                          "that is on, -1 <= ref_window[k] < n_frames)");
+    }
+    if (frame_idx < 0 || frame_idx >= n_frames) return bad_arg(c, "svt_hip_tpl_synth_picture_dev: bad argument (0 <= frame_idx < n_frames)");
+    if (!frames[frame_idx].on) return SVT_HIP_OK;
+    return tpl_synth_launch(c, p, frames, frame_idx);
+}
+
+int svt_hip_tpl_r0beta_dev(SvtHipCtx* c, const SvtHipTplSynthParams* p, const SvtHipTplMbStats* d_stats, const int64_t* d_dep, void* d_out, void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    if (!c) return bad_arg(c);
+    switch (tpl_synth_refusal(p, nullptr, 0, false)) {
+    case TPL_SYNTH_RATE: return bad_arg(c, "svt_hip_tpl_r0beta_dev: rate must be 0 (the reference's tpl_opt_flag == 1; delta_rate_cost is not built)");
+    case TPL_SYNTH_PARAMS: return bad_arg(c, "svt_hip_tpl_r0beta_dev: bad argument (w, h multiples of 8 and >= 16, cell_log2 3 or 4, sb_size 64 or 128, base_rdmult >= 0)");
+    }
+    if (!d_stats || !d_dep || !d_out || !d_scratch || ((uintptr_t)d_out & 7) || ((uintptr_t)d_scratch & 7))
+        return bad_arg(c, "svt_hip_tpl_r0beta_dev: bad argument (d_stats, d_dep, d_out, d_scratch non-NULL, d_out and d_scratch 8-byte aligned)");
+    return launched(c, svt_hip_launch_tpl_r0beta(c->stream, p, d_stats, d_dep, d_out, d_scratch), "tpl r0/beta launch");
+}
+
+int svt_hip_tpl_window_dev(SvtHipCtx* c, const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int n_frames, void* d_out, void* d_scratch) {
+    SVT_HIP_ENTER(c);
+    if (!c) return bad_arg(c);
+    switch (tpl_synth_refusal(p, frames, n_frames, true)) {
+    case TPL_SYNTH_RATE: return bad_arg(c, "svt_hip_tpl_window_dev: rate must be 0 (the reference's tpl_opt_flag == 1; delta_rate_cost is not built)");
+    case TPL_SYNTH_PARAMS: return bad_arg(c, "svt_hip_tpl_window_dev: bad argument (w, h multiples of 8 and >= 16, cell_log2 3 or 4, sb_size 64 or 128, base_rdmult >= 0)");
+    case TPL_SYNTH_SELF: return bad_arg(c, "svt_hip_tpl_window_dev: ref_window[1..7] names the picture itself (the result would depend on the order of the blocks)");
+    case TPL_SYNTH_FRAMES:
+        return bad_arg(c, "svt_hip_tpl_window_dev: bad argument (1 <= n_frames <= 60, every d_dep distinct and non-NULL, d_stats of picture 0 and of every picture that is "
+                          "on, -1 <= ref_window[k] < n_frames)");
+    }
+    if (!d_out || !d_scratch || ((uintptr_t)d_out & 7) || ((uintptr_t)d_scratch & 7))
+        return bad_arg(c, "svt_hip_tpl_window_dev: bad argument (d_out, d_scratch non-NULL and 8-byte aligned)");
+    const size_t bytes = svt_hip_tpl_dep_bytes(p->w, p->h, p->cell_log2);
+    for (int i = 0; i < n_frames; i++) HIPCHK(c, hipMemsetAsync(frames[i].d_dep, 0, bytes, c->stream));   // :1159-1163
+    for (int i = n_frames - 1; i >= 0; i--)                                                                // :1181-1194
+        if (frames[i].on)
+            if (int rc = tpl_synth_launch(c, p, frames, i)) return rc;
+    return launched(c, svt_hip_launch_tpl_r0beta(c->stream, p, frames[0].d_stats, frames[0].d_dep, d_out, d_scratch), "tpl r0/beta launch");   // :1197
 }
 
 /* ---------------------------------------------------------------------------------- global motion */

@@ -6,6 +6,7 @@
 #include "../../include/svt_hip.h"
 #include "svt_hip_host.h"
 #include "gm_walk.h"
+#include "tpl_synth.h"
 
 extern "C" {
 
@@ -286,6 +287,14 @@ int svt_hip_gm_decide_host(const SvtHipGmModelRecord models[2], int64_t ref_fram
     }
     for (int k = 0; k < 8; k++) wmmat_out[k] = gm[k];
     *wmtype_out = gm_type;
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- TPL synthesizer, r0 / beta */
+/* svt_hip_tpl_window_dev's contract on host pointers: tpl_synth.h run serially in the reference's order */
+int svt_hip_tpl_window_host(const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int n_frames, void* out) {
+    if (!tplsyn::params_ok(p) || p->rate != 0 || tplsyn::frames_check(frames, n_frames) || !out || ((uintptr_t)out & 7)) return SVT_HIP_ERR_BAD_ARG;
+    tplsyn::window_host(*p, frames, n_frames, out);
     return SVT_HIP_OK;
 }
 

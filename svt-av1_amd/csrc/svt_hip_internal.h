@@ -215,6 +215,9 @@ int svt_hip_launch_tf_noise(hipStream_t st, const void* src, int pix_bytes, int 
 int svt_hip_launch_tpl_dispenser(hipStream_t st, const SvtHipTplParams* p, const uint8_t* cur, int cur_stride, const SvtHipTplRef* refs, const uint32_t* mv,
                                  const uint8_t* ref_mask, const uint8_t* ois_mode, const int32_t* ois_cost, uint8_t* recon, int recon_stride,
                                  SvtHipTplMbStats* stats, uint8_t* decision, int phases);
+/* tpl_synth.hip; target[rf_idx + 1] = the grid of the picture that slot names, NULL = not in the window */
+int svt_hip_launch_tpl_synth(hipStream_t st, int w, int h, int cell_log2, const SvtHipTplMbStats* stats, const int64_t* own, int64_t* const target[8]);
+int svt_hip_launch_tpl_r0beta(hipStream_t st, const SvtHipTplSynthParams* p, const SvtHipTplMbStats* stats, const int64_t* dep, void* out, void* scratch);
 /* txfm2d.hip */
 int svt_hip_launch_fwd_txfm_quant(hipStream_t st, int tx_size, int pix_bytes, const void* src, int src_stride, const void* pred,
                                   int pred_stride, const uint32_t* descs, int nblk, const SvtHipQuantParams* qp,

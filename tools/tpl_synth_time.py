@@ -1,0 +1,61 @@
+"""Times svt_hip_tpl_window_dev at 3840x2160 with 3, 17 and 33 pictures (HIP events around back-to-back calls on resident records and grids, windows of at
+least --window-ms), beside launches x 1.45 us: the call is a chain of dependent launches on one stream (one memset and one scatter per picture, then one
+memset and two kernels for r0 / beta), and the microarchitecture guide's figure for a dependent kernel boundary is what such a chain costs at the least.
+Records: the seeded generator of tests/tpl_synth_common.py; picture k references k - 1 and, from the third on, k - 2 and picture 0.
+    python tools/tpl_synth_time.py [--window-ms 150] [--size 3840x2160] [--pictures 3,17,33]"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+from conftest import load_package  # noqa: E402
+import tpl_synth_common as S  # noqa: E402
+
+BOUNDARY_US = 1.45   # a dependent kernel boundary on one stream (the microarchitecture guide's figure)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--window-ms", type=float, default=150.0)
+ap.add_argument("--size", default="3840x2160")
+ap.add_argument("--pictures", default="3,17,33")
+args = ap.parse_args()
+w, h = (int(v) for v in args.size.split("x"))
+counts = [int(v) for v in args.pictures.split(",")]
+pkg = load_package()
+hip = pkg.Context(0)
+L = hip.L
+P = pkg.tpl_synth_params(w, h, 1234, r0_in=0.75)
+dep_bytes = L.svt_hip_tpl_dep_bytes(w, h, P.cell_log2)
+rng = np.random.default_rng(1)
+n_max = max(counts)
+pocs = [16 * k for k in range(n_max)]
+d_stats = [hip.to_device(S.random_stats(rng, w, h, 3)) for _ in range(n_max)]
+d_dep = [hip.empty(dep_bytes) for _ in range(n_max)]
+d_out = hip.empty(L.svt_hip_tpl_r0beta_out_bytes(w, h, P.sb_size))
+d_scratch = hip.empty(L.svt_hip_tpl_r0beta_scratch_bytes())
+ms = C.c_float()
+print(f"tpl_window {w}x{h}, {1 << P.cell_log2}x{1 << P.cell_log2} cells, {dep_bytes // 16} source blocks per picture, grid {dep_bytes / 1e6:.2f} MB")
+for n in counts:
+    slots = [[pocs[k - 1] if k >= 1 else 999, pocs[k - 2] if k >= 2 else 999, pocs[0] if k >= 2 else 999] for k in range(n)]
+    F = pkg.tpl_window_frames([(d_stats[k], d_dep[k], 1, pkg.tpl_ref_window(pocs[:n], slots[k])) for k in range(n)])
+
+    def once():
+        hip.check(L.svt_hip_tpl_window_dev(hip.h, C.byref(P), F, n, d_out, d_scratch), "tpl_window")
+
+    for _ in range(2): once()
+    hip.check(L.svt_hip_sync(hip.h), "sync")
+    reps = 2
+    while True:   # grow the window until it is long enough
+        L.svt_hip_timer_start(hip.h)
+        for _ in range(reps): once()
+        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
+        if ms.value >= args.window_ms: break
+        reps = max(reps * 2, int(reps * 1.3 * args.window_ms / max(ms.value, 1e-3)))
+    t = ms.value / reps
+    launches = 2 * n + 3
+    print(f"  {n:2d} pictures: {t:.4f} ms per window  (window {ms.value:.0f} ms, {reps} calls); {launches} launches ({n} memsets + {n} scatters + 1 memset + 2 kernels) "
+          f"x {BOUNDARY_US} us = {launches * BOUNDARY_US / 1e3:.4f} ms; {1e3 * t / launches:.2f} us per launch")
+hip.free(*d_stats, *d_dep, d_out, d_scratch)
+hip.close()
