@@ -18,6 +18,8 @@
 #include "svt_hip_internal.h"
 #include "txfm_1d.h"
 #include "quant_dev.h"
+#include "txfm_plan.h"
+#include <type_traits>
 
 namespace {
 
@@ -329,10 +331,11 @@ inv_txfm_add_kernel(const int32_t* __restrict__ dqcoeff, const PIX* pred, int pr
 }
 
 // ================================================================== mixed-size launches ==========
-// One launch over several (transform size, plane) job lists: a frame's transform work is 15-20 short lists (a few hundred to a few
-// thousand blocks each), too small to fill 256 CUs one at a time.  Every workgroup finds its job by its index (uniform scalar scan
-// over <= 16 prefix sums held in the kernel argument), then runs the size's body; LDS and registers are those of the largest size.
-constexpr int kMultiJobs = 16, kMultiTileDw = 8448;   // max over sizes of TEAMS * H * (W + 1)
+// A call over several (transform size, plane) job lists: a frame's transform work is 15-20 short lists (a few hundred to a few thousand blocks each), too small to
+// fill 256 CUs one at a time.  The lists are sorted into size classes (txfm_plan.h) and each class gets launches of its own kernel instance, which holds the bodies
+// of that class alone: its registers and its LDS tile are the class's, not those of the 64-point body.  Every workgroup finds its job by its index (uniform scalar
+// scan over <= 16 prefix sums held in the kernel argument), then runs the size's body.
+constexpr int kMultiJobs = kTxPlanJobs;
 struct FwdMulti { int njobs; int first_wg[kMultiJobs + 1]; SvtHipFwdTxJob job[kMultiJobs]; };
 struct InvMulti { int njobs; int first_wg[kMultiJobs + 1]; SvtHipInvTxJob job[kMultiJobs]; };
 
@@ -340,10 +343,22 @@ struct InvMulti { int njobs; int first_wg[kMultiJobs + 1]; SvtHipInvTxJob job[kM
     X(0, 4, 4) X(1, 8, 8) X(2, 16, 16) X(3, 32, 32) X(4, 64, 64) X(5, 4, 8) X(6, 8, 4) X(7, 8, 16) X(8, 16, 8) X(9, 16, 32) \
     X(10, 32, 16) X(11, 32, 64) X(12, 64, 32) X(13, 4, 16) X(14, 16, 4) X(15, 8, 32) X(16, 32, 8) X(17, 16, 64) X(18, 64, 16)
 
-template <typename PIX>
+#define X(id, w, h) static_assert(kTxPlanW[id] == w && kTxPlanH[id] == h && tx_plan_teams(id) == threads_of(w, h) / (w > h ? w : h), "txfm_plan.h disagrees");
+FOR_ALL_TX_SIZES_DEV(X)
+#undef X
+// dwords of LDS of a class's instance: the largest TEAMS * H * (W + 1) among its sizes
+constexpr int class_tile_dw(int cls) {
+    int m = 0;
+#define X(id, w, h) if (tx_plan_class(id) == cls && tx_plan_teams(id) * h * (w + 1) > m) m = tx_plan_teams(id) * h * (w + 1);
+    FOR_ALL_TX_SIZES_DEV(X)
+#undef X
+    return m;
+}
+
+template <typename PIX, int CLS>
 __global__ void __launch_bounds__(256)
 fwd_txfm_quant_multi_kernel(const FwdMulti a) {
-    __shared__ int32_t tile[kMultiTileDw];
+    __shared__ int32_t tile[class_tile_dw(CLS)];
     int j = 0;
     while (j + 1 < a.njobs && (int)blockIdx.x >= a.first_wg[j + 1]) j++;
     const int wg = (int)blockIdx.x - a.first_wg[j];
@@ -358,8 +373,9 @@ fwd_txfm_quant_multi_kernel(const FwdMulti a) {
     switch (tx_size) {
 #define X(id, w, h)                                                                                                                            \
     case id:                                                                                                                                   \
-        fwd_block<w, h, PIX>(tile, wg, threadIdx.x, src, src_stride, pred, pred_stride, descs, nblk, qp, scans, coeff, qcoeff, dqcoeff, eob,  \
-                             cul, energy);                                                                                                     \
+        if constexpr (tx_plan_class(id) == CLS)                                                                                                \
+            fwd_block<w, h, PIX>(tile, wg, threadIdx.x, src, src_stride, pred, pred_stride, descs, nblk, qp, scans, coeff, qcoeff, dqcoeff,   \
+                                 eob, cul, energy);                                                                                            \
         break;
         FOR_ALL_TX_SIZES_DEV(X)
 #undef X
@@ -368,10 +384,10 @@ fwd_txfm_quant_multi_kernel(const FwdMulti a) {
 }
 // the same job lists with the reconstruction fused in (FBD = bit depth): recon[j] / recon_stride[j] per job
 struct EncMulti { FwdMulti f; void* recon[kMultiJobs]; int recon_stride[kMultiJobs]; };
-template <typename PIX, int BD>
+template <typename PIX, int BD, int CLS>
 __global__ void __launch_bounds__(256)
 enc_txfm_multi_kernel(const EncMulti e) {
-    __shared__ int32_t tile[kMultiTileDw];
+    __shared__ int32_t tile[class_tile_dw(CLS)];
     int j = 0;
     while (j + 1 < e.f.njobs && (int)blockIdx.x >= e.f.first_wg[j + 1]) j++;
     const int wg = (int)blockIdx.x - e.f.first_wg[j];
@@ -385,37 +401,47 @@ enc_txfm_multi_kernel(const EncMulti e) {
     switch (tx_size) {
 #define X(id, w, h)                                                                                                                                  \
     case id:                                                                                                                                         \
-        fwd_block<w, h, PIX, BD>(tile, wg, threadIdx.x, src, src_stride, pred, pred_stride, descs, nblk, qp, scans, coeff, qcoeff, dqcoeff, eob, cul, \
-                                 energy, recon, recon_stride);                                                                                       \
+        if constexpr (tx_plan_class(id) == CLS)                                                                                                      \
+            fwd_block<w, h, PIX, BD>(tile, wg, threadIdx.x, src, src_stride, pred, pred_stride, descs, nblk, qp, scans, coeff, qcoeff, dqcoeff, eob, \
+                                     cul, energy, recon, recon_stride);                                                                              \
         break;
         FOR_ALL_TX_SIZES_DEV(X)
 #undef X
     default: break;
     }
 }
-template <typename PIX, int BD>
+template <typename PIX, int BD, int CLS>
 __global__ void __launch_bounds__(256)
 inv_txfm_add_multi_kernel(const InvMulti a) {
-    __shared__ int32_t tile[kMultiTileDw];
+    __shared__ int32_t tile[class_tile_dw(CLS)];
     int j = 0;
     while (j + 1 < a.njobs && (int)blockIdx.x >= a.first_wg[j + 1]) j++;
     const SvtHipInvTxJob& J = a.job[j];
     const int wg = (int)blockIdx.x - a.first_wg[j];
     switch (J.tx_size) {
-#define X(id, w, h)                                                                                                                     \
-    case id:                                                                                                                            \
-        inv_block<w, h, BD, PIX>(tile, wg, threadIdx.x, J.d_dqcoeff, (const PIX*)J.d_pred, J.pred_stride, (PIX*)J.d_recon, J.recon_stride, \
-                                 J.d_descs, J.nblk);                                                                                     \
+#define X(id, w, h)                                                                                                                            \
+    case id:                                                                                                                                   \
+        if constexpr (tx_plan_class(id) == CLS)                                                                                                \
+            inv_block<w, h, BD, PIX>(tile, wg, threadIdx.x, J.d_dqcoeff, (const PIX*)J.d_pred, J.pred_stride, (PIX*)J.d_recon, J.recon_stride, \
+                                     J.d_descs, J.nblk);                                                                                       \
         break;
         FOR_ALL_TX_SIZES_DEV(X)
 #undef X
     default: break;
     }
 }
-__host__ constexpr int teams_of(int ts) {
-    constexpr int w[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
-    constexpr int h[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
-    return threads_of(w[ts], h[ts]) / (w[ts] > h[ts] ? w[ts] : h[ts]);
+// the instance of a class chosen at run time: f(std::integral_constant<int, cls>)
+template <int C = 0, typename F> void for_tx_class(int cls, F&& f) {
+    if constexpr (C < kTxClasses) {
+        if (cls == C) f(std::integral_constant<int, C>{});
+        else for_tx_class<C + 1>(cls, f);
+    }
+}
+// the launches of a call: tx_plan() over the jobs' (tx_size, nblk)
+template <typename JOB, typename GET> std::vector<TxPlanLaunch> plan_jobs(const JOB* jobs, int njobs, GET&& fwd_of) {
+    std::vector<int> ts(njobs > 0 ? njobs : 0), nblk(ts.size());
+    for (size_t j = 0; j < ts.size(); j++) { ts[j] = fwd_of(jobs[j]).tx_size; nblk[j] = fwd_of(jobs[j]).nblk; }
+    return tx_plan(ts.data(), nblk.data(), (int)ts.size());
 }
 
 template <int W, int H>
@@ -479,54 +505,47 @@ extern "C" int svt_hip_launch_inv_txfm_add(hipStream_t st, int tx_size, int pix_
 }
 
 extern "C" int svt_hip_launch_fwd_txfm_quant_multi(hipStream_t st, int pix_bytes, const SvtHipFwdTxJob* jobs, int njobs) {
-    for (int j0 = 0; j0 < njobs; j0 += kMultiJobs) {
+    for (const TxPlanLaunch& l : plan_jobs(jobs, njobs, [](const SvtHipFwdTxJob& J) -> const SvtHipFwdTxJob& { return J; })) {
         FwdMulti a = {};
-        int wg = 0;
-        for (int j = j0; j < njobs && j < j0 + kMultiJobs; j++) {
-            if (jobs[j].nblk <= 0) continue;
-            const int t = teams_of(jobs[j].tx_size);
-            a.first_wg[a.njobs] = wg;
-            a.job[a.njobs++] = jobs[j];
-            wg += (jobs[j].nblk + t - 1) / t;
-        }
-        a.first_wg[a.njobs] = wg;
-        if (!wg) continue;
-        svt_for_pix(pix_bytes, [&](auto f) { hipLaunchKernelGGL((fwd_txfm_quant_multi_kernel<typename decltype(f)::pix>), dim3(wg), dim3(256), 0, st, a); });
+        a.njobs = l.njobs;
+        for (int k = 0; k <= l.njobs; k++) a.first_wg[k] = l.first_wg[k];
+        for (int k = 0; k < l.njobs; k++) a.job[k] = jobs[l.job[k]];
+        svt_for_pix(pix_bytes, [&](auto f) {
+            for_tx_class(l.cls, [&](auto c) {
+                hipLaunchKernelGGL((fwd_txfm_quant_multi_kernel<typename decltype(f)::pix, decltype(c)::value>), dim3(l.first_wg[l.njobs]), dim3(256), 0, st, a);
+            });
+        });
     }
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_enc_txfm_multi(hipStream_t st, int pix_bytes, int bd, const SvtHipEncTxJob* jobs, int njobs) {
-    for (int j0 = 0; j0 < njobs; j0 += kMultiJobs) {
+    for (const TxPlanLaunch& l : plan_jobs(jobs, njobs, [](const SvtHipEncTxJob& J) -> const SvtHipFwdTxJob& { return J.fwd; })) {
         EncMulti e = {};
-        int wg = 0;
-        for (int j = j0; j < njobs && j < j0 + kMultiJobs; j++) {
-            if (jobs[j].fwd.nblk <= 0) continue;
-            const int t = teams_of(jobs[j].fwd.tx_size);
-            e.f.first_wg[e.f.njobs] = wg;
-            e.recon[e.f.njobs] = jobs[j].d_recon; e.recon_stride[e.f.njobs] = jobs[j].recon_stride;
-            e.f.job[e.f.njobs++] = jobs[j].fwd;
-            wg += (jobs[j].fwd.nblk + t - 1) / t;
+        e.f.njobs = l.njobs;
+        for (int k = 0; k <= l.njobs; k++) e.f.first_wg[k] = l.first_wg[k];
+        for (int k = 0; k < l.njobs; k++) {
+            e.f.job[k] = jobs[l.job[k]].fwd;
+            e.recon[k] = jobs[l.job[k]].d_recon; e.recon_stride[k] = jobs[l.job[k]].recon_stride;
         }
-        e.f.first_wg[e.f.njobs] = wg;
-        if (!wg) continue;
-        svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((enc_txfm_multi_kernel<typename decltype(f)::pix, decltype(f)::bd>), dim3(wg), dim3(256), 0, st, e); });
+        svt_for_fmt(pix_bytes, bd, [&](auto f) {
+            for_tx_class(l.cls, [&](auto c) {
+                hipLaunchKernelGGL((enc_txfm_multi_kernel<typename decltype(f)::pix, decltype(f)::bd, decltype(c)::value>), dim3(l.first_wg[l.njobs]), dim3(256), 0, st, e);
+            });
+        });
     }
     return (int)hipGetLastError();
 }
 extern "C" int svt_hip_launch_inv_txfm_add_multi(hipStream_t st, int pix_bytes, int bd, const SvtHipInvTxJob* jobs, int njobs) {
-    for (int j0 = 0; j0 < njobs; j0 += kMultiJobs) {
+    for (const TxPlanLaunch& l : plan_jobs(jobs, njobs, [](const SvtHipInvTxJob& J) -> const SvtHipInvTxJob& { return J; })) {
         InvMulti a = {};
-        int wg = 0;
-        for (int j = j0; j < njobs && j < j0 + kMultiJobs; j++) {
-            if (jobs[j].nblk <= 0) continue;
-            const int t = teams_of(jobs[j].tx_size);
-            a.first_wg[a.njobs] = wg;
-            a.job[a.njobs++] = jobs[j];
-            wg += (jobs[j].nblk + t - 1) / t;
-        }
-        a.first_wg[a.njobs] = wg;
-        if (!wg) continue;
-        svt_for_fmt(pix_bytes, bd, [&](auto f) { hipLaunchKernelGGL((inv_txfm_add_multi_kernel<typename decltype(f)::pix, decltype(f)::bd>), dim3(wg), dim3(256), 0, st, a); });
+        a.njobs = l.njobs;
+        for (int k = 0; k <= l.njobs; k++) a.first_wg[k] = l.first_wg[k];
+        for (int k = 0; k < l.njobs; k++) a.job[k] = jobs[l.job[k]];
+        svt_for_fmt(pix_bytes, bd, [&](auto f) {
+            for_tx_class(l.cls, [&](auto c) {
+                hipLaunchKernelGGL((inv_txfm_add_multi_kernel<typename decltype(f)::pix, decltype(f)::bd, decltype(c)::value>), dim3(l.first_wg[l.njobs]), dim3(256), 0, st, a);
+            });
+        });
     }
     return (int)hipGetLastError();
 }
