@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "lds_stage.h"
 
 namespace {
@@ -73,11 +74,11 @@ __device__ __constant__ uint8_t kDirBinPix[8][16][8] = {
     {{0,8,16,24,32,40,48,56},{1,9,17,25,33,41,49,57},{2,10,18,26,34,42,50,58},{3,11,19,27,35,43,51,59},{4,12,20,28,36,44,52,60},{5,13,21,29,37,45,53,61},{6,14,22,30,38,46,54,62},{7,15,23,31,39,47,55,63},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
     {{0,8,255,255,255,255,255,255},{1,9,16,24,255,255,255,255},{2,10,17,25,32,40,255,255},{3,11,18,26,33,41,48,56},{4,12,19,27,34,42,49,57},{5,13,20,28,35,43,50,58},{6,14,21,29,36,44,51,59},{7,15,22,30,37,45,52,60},{23,31,38,46,53,61,255,255},{39,47,54,62,255,255,255,255},{55,63,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}}};
 __device__ __constant__ int kDirBinWeight[8][16] = {{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0}};
-__device__ __forceinline__ int row_sum16(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);  // row_mirror
+__device__ __forceinline__ int row_sum16(int v) {   // row16_sum in the builtin's other spelling: the header's gives the kernels that find a direction other code
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP1, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP2, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_HALF_MIRROR, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_MIRROR, 0xF, 0xF, false);
     return v;
 }
 __device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out) {
@@ -315,16 +316,6 @@ template <> struct Dots<uint16_t> {
         }
     }
 };
-
-// total of v over the 64 lanes of a wave (wave-uniform result): DPP inside the 16-lane rows, then the four row totals
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
-    int v = (int)x;
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);   // row_mirror
-    return (uint32_t)(__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
 
 // ------------------------------------------------------------------------------- search, luma ---
 template <typename PIX>

@@ -25,6 +25,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 
 namespace {
 
@@ -313,8 +314,8 @@ joint_transpose_kernel(const uint64_t* __restrict__ mse0, const uint64_t* __rest
 }
 // sum over the lanes l, l ^ 4, l ^ 8, ... ^ 32 (the 16 lanes of a wave that share l & 3)
 __device__ __forceinline__ unsigned long long sum_stride4(uint32_t v) {   // every partial sum of one 16-lane row fits 32 bits (narrow tables)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false);   // row_ror:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);   // row_ror:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DPP_ROW_ROR4, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DPP_ROW_ROR8, 0xf, 0xf, false);
     unsigned long long r = v;
     r += (unsigned long long)__shfl_xor((long long)r, 16);
     r += (unsigned long long)__shfl_xor((long long)r, 32);

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "interp_kernels.h"
 
 namespace {
@@ -144,7 +145,7 @@ obmc_cost_kernel(const uint8_t* __restrict__ pre, int pre_stride, const int32_t*
         sum += d; sse += (uint32_t)(d * d);
     }
 #pragma unroll
-    for (int s = 1; s < 64; s <<= 1) { sad += (uint32_t)__shfl_xor((int)sad, s, 64); sse += (uint32_t)__shfl_xor((int)sse, s, 64); sum += __shfl_xor(sum, s, 64); }
+    for (int s = 1; s < 64; s <<= 1) { sad += lane_xor(sad, s); sse += lane_xor(sse, s); sum += lane_xor(sum, s); }
     if (lane == 0) {
         out[3 * (size_t)blk] = sad; out[3 * (size_t)blk + 1] = sse;
         out[3 * (size_t)blk + 2] = sse - (uint32_t)(((long long)sum * sum) / (b.w * b.h));

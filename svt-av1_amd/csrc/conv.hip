@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "interp_kernels.h"
 
 namespace {
@@ -106,7 +107,7 @@ block_sad_kernel(const PIX* __restrict__ a, int a_stride, const PIX* __restrict_
         s += (uint32_t)abs(va - vb);
     }
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) s += (uint32_t)__shfl_xor((int)s, m, 64);
+    for (int m = 1; m < 64; m <<= 1) s += lane_xor(s, m);
     if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 template <typename PIX, int BD>

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "intra_dev.h"
 #include "filter_intra_taps.h"
 
@@ -44,10 +45,10 @@ IPD int round_signed(int v, int n) { return v < 0 ? -((-v + (1 << (n - 1))) >> n
 IPD int wave_group(int need) { return __any(need > 32) ? 64 : (__any(need > 16) ? 32 : (__any(need > 8) ? 16 : 8)); }
 
 IPD int group_sum(int v, int G) {
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-    if (G >= 16) v += __shfl_xor(v, 8, 64);
-    if (G >= 32) v += __shfl_xor(v, 16, 64);
-    if (G >= 64) v += __shfl_xor(v, 32, 64);
+    v += lane_xor(v, 1); v += lane_xor(v, 2); v += lane_xor(v, 4);
+    if (G >= 16) v += lane_xor(v, 8);
+    if (G >= 32) v += lane_xor(v, 16);
+    if (G >= 64) v += lane_xor(v, 32);
     return v;
 }
 

@@ -15,6 +15,7 @@
 // HBM-bound in principle (algorithmic bytes per (SB, reference): 4096 source + ~4 x 4096 reference samples + 85 x 8 table bytes), launch-bound in practice:
 // a 1080p picture with 7 references is 3 570 workgroups of ~30 iterations.
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "lds_stage.h"
 #include "interp_kernels.h"
 
@@ -45,18 +46,6 @@ __device__ __forceinline__ uint32_t sad4(U16x4 a, U16x4 b, uint32_t acc) { retur
 __device__ __forceinline__ uint32_t ld4(const uint8_t* p) { return load4_any(p); }
 __device__ __forceinline__ U16x4 ld4(const uint16_t* p) { return load4_any16(p); }
 __device__ __forceinline__ uint32_t avg2_round_up16(uint32_t a, uint32_t b) { return (a | b) - (((a ^ b) >> 1) & 0x7fff7fffu); }   // per 16-bit half (a + b + 1) >> 1
-
-__device__ __forceinline__ uint32_t row_sum(uint32_t x) {      // every lane: the total of its 16-lane row
-    int v = (int)x;
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);   // row_mirror
-    return (uint32_t)v;
-}
-__device__ __forceinline__ uint32_t rows_total(uint32_t v) {   // the four row totals of a wave added up (wave-uniform)
-    return (uint32_t)(__builtin_amdgcn_readlane((int)v, 0) + __builtin_amdgcn_readlane((int)v, 16) + __builtin_amdgcn_readlane((int)v, 32) + __builtin_amdgcn_readlane((int)v, 48));
-}
 
 // PIX = uint8_t: the 8-bit planes; uint16_t: the 16-bit planes a 10-bit encode's mode decision works on (sad_16b_kernel, Encoder/C_DEFAULT/EbComputeSAD_C.c:39; strides and the
 // reference boxes in samples, d_plane = sample (0, 0) of the 16-bit plane)
@@ -95,7 +84,7 @@ md_fullpel_sad_kernel(const PIX* __restrict__ src, int src_stride, int pic_w, in
 #pragma unroll
             for (int u = 0; u < 4; u++) { const uint32_t t = sad4(a[u], b[u], s); s = row < rows && r0 + u * rows + row < h ? t : s; }
         }
-        s = rows_total(row_sum(s));
+        s = wave_sum_u32(s);
         if (lane == 0) sad[slot] = s;
     }
 }
@@ -143,7 +132,7 @@ md_fullpel_avg_sad_kernel(const PIX* __restrict__ src, int src_stride, int pic_w
 #pragma unroll
             for (int u = 0; u < 2; u++) { const uint32_t t = sad4(a[u], avg_round_up(b[u], c[u]), s); s = row < rows && r0 + u * rows + row < h ? t : s; }
         }
-        s = rows_total(row_sum(s));
+        s = wave_sum_u32(s);
         if (lane == 0) sad[slot] = s;
     }
 }
@@ -233,7 +222,7 @@ md_subpel_grid_kernel(const uint8_t* __restrict__ src, int src_stride, int pic_w
             for (int q = 0; q < 4; q++) Sc[(c + q) * s + rr] = (uint8_t)(v >> (8 * q));
             ss += __builtin_amdgcn_udot4(v, 0x01010101u, 0u, false); ss2 += __builtin_amdgcn_udot4(v, v, 0u, false);
         }
-        ss = rows_total(row_sum(ss)); ss2 = rows_total(row_sum(ss2));
+        ss = wave_sum_u32(ss); ss2 = wave_sum_u32(ss2);
         if ((tid & 63) == 0) { atomicAdd(&sstat[0], ss); atomicAdd(&sstat[1], ss2); }
     }
     // ---- horizontal pass, once per horizontal offset: Hc[a][col][row] over all WIN rows
@@ -277,7 +266,7 @@ md_subpel_grid_kernel(const uint8_t* __restrict__ src, int src_stride, int pic_w
             const uint32_t S = *(const uint32_t*)(&Sc[j * s + i]);
             sp = __builtin_amdgcn_udot4(P, 0x01010101u, 0u, false); sp2 = __builtin_amdgcn_udot4(P, P, 0u, false); sps = __builtin_amdgcn_udot4(P, S, 0u, false);
         }
-        sp = row_sum(sp); sp2 = row_sum(sp2); sps = row_sum(sps);          // DPP inside the 16-lane rows (G = 16: a row is a grid position's lanes)
+        sp = row16_sum(sp); sp2 = row16_sum(sp2); sps = row16_sum(sps);          // DPP inside the 16-lane rows (G = 16: a row is a grid position's lanes)
         if (G == 64) { sp = rows_total(sp); sp2 = rows_total(sp2); sps = rows_total(sps); }
         if (t < kGridN * per && (tid & (G - 1)) == 0) { atomicAdd(&stat[c][0], sp); atomicAdd(&stat[c][1], sp2); atomicAdd(&stat[c][2], sps); }
     }

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "lds_stage.h"
 
 #ifndef ME_R_UNROLL
@@ -41,18 +42,6 @@ constexpr int kRefRows = kTile + 63;   // window rows per tile
 constexpr int kRefRowDw = 36;          // dwords staged per window row (64+63 px + 8 over-read = 135 B -> 144 B)
 constexpr int kRefStrideDw = 48;       // LDS row stride in dwords (192 B): rows y..y+3 of a 32-lane group hit
                                        // disjoint 16-bank quarters for ds_read_b64 (banks = dword % 64)
-
-// Wave-wide unsigned minimum, result uniform.  4 DPP steps inside each 16-lane row, then the four
-// row results are combined through SGPRs.
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
-    uint32_t a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    uint32_t c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    return min(min(a, b), min(c, d));
-}
 
 // index of the 8x8 block (bx,by) in the reference's 85-PU layout (EbMotionEstimationContext.h:51-137;
 // z-order of 16x16 blocks from the `offsets` table, EbMotionEstimation.c:367)

@@ -26,13 +26,13 @@
 #include <cstddef>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "interp_kernels.h"
 #include "quant_dev.h"
 
 namespace {
 
 __constant__ int16_t kTaps[6][16][8] = SVT_HIP_INTERP_TABLE;
-__device__ __forceinline__ long long wave_sum_i64(long long v) { return (long long)wave_sum_u64((unsigned long long)v); }
 __device__ __forceinline__ int clip_px(int v, int bd) { const int mx = (1 << bd) - 1; return v < 0 ? 0 : (v > mx ? mx : v); }
 
 // ------------------------------------------------------------------------------------------------ quantizers
@@ -150,7 +150,7 @@ ext_sad_16_kernel(const uint8_t* __restrict__ src, int ss, const uint8_t* __rest
         if (!j.sub_sad || !(y & 1)) acc += (unsigned)abs((int)s[(size_t)(qy + y) * ss + qx + x] - (int)r[(size_t)(qy + y) * rs + qx + x]);
     }
 #pragma unroll
-    for (int m = 1; m < 16; m <<= 1) acc += (unsigned)__shfl_xor((int)acc, m, 64);
+    for (int m = 1; m < 16; m <<= 1) acc += lane_xor(acc, m);
     if (j.sub_sad) acc <<= 1;   // compute8x4_sad_kernel on every other row, doubled
     const unsigned s0 = (unsigned)__shfl((int)acc, 0, 64), s1 = (unsigned)__shfl((int)acc, 16, 64), s2 = (unsigned)__shfl((int)acc, 32, 64), s3 = (unsigned)__shfl((int)acc, 48, 64);
     if (lane == 0) {

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "lds_stage.h"
 
 namespace {
@@ -27,10 +28,6 @@ downsample_kernel(const uint8_t* __restrict__ in, int in_stride, int w, int h, u
     }
 }
 
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
-    return ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64);
-}
-
 // one wave per 64x64 SB; lane = 8x8 block in raster order; outputs [sb][85]: 64x64, 32x32 x4, 16x16 x16, 8x8 x64 (raster per level)
 __global__ void __launch_bounds__(64)
 variance_pyramid_kernel(const uint8_t* __restrict__ plane, int stride, int sb_cols, int full_precision, uint8_t* __restrict__ mean_out,
@@ -47,12 +44,12 @@ variance_pyramid_kernel(const uint8_t* __restrict__ plane, int stride, int sb_co
     uint64_t m8 = full_precision ? ((uint64_t)s << 8) / 64 : (uint64_t)s << 3;
     uint64_t q8 = full_precision ? ((uint64_t)s2 << 16) / 64 : (uint64_t)s2 << 11;
     // raster lanes: 16x16 = lanes {l, l^1, l^8, l^9}; 32x32 adds {^2, ^16}; 64x64 adds {^4, ^32}
-    uint64_t t = m8 + shfl_xor64(m8, 1); const uint64_t m16 = (t + shfl_xor64(t, 8)) >> 2;
-    t = q8 + shfl_xor64(q8, 1);          const uint64_t q16 = (t + shfl_xor64(t, 8)) >> 2;
-    t = m16 + shfl_xor64(m16, 2);        const uint64_t m32 = (t + shfl_xor64(t, 16)) >> 2;
-    t = q16 + shfl_xor64(q16, 2);        const uint64_t q32 = (t + shfl_xor64(t, 16)) >> 2;
-    t = m32 + shfl_xor64(m32, 4);        const uint64_t m64 = (t + shfl_xor64(t, 32)) >> 2;
-    t = q32 + shfl_xor64(q32, 4);        const uint64_t q64 = (t + shfl_xor64(t, 32)) >> 2;
+    uint64_t t = m8 + lane_xor(m8, 1); const uint64_t m16 = (t + lane_xor(t, 8)) >> 2;
+    t = q8 + lane_xor(q8, 1);          const uint64_t q16 = (t + lane_xor(t, 8)) >> 2;
+    t = m16 + lane_xor(m16, 2);        const uint64_t m32 = (t + lane_xor(t, 16)) >> 2;
+    t = q16 + lane_xor(q16, 2);        const uint64_t q32 = (t + lane_xor(t, 16)) >> 2;
+    t = m32 + lane_xor(m32, 4);        const uint64_t m64 = (t + lane_xor(t, 32)) >> 2;
+    t = q32 + lane_xor(q32, 4);        const uint64_t q64 = (t + lane_xor(t, 32)) >> 2;
     uint8_t* mo = mean_out + (size_t)sb * 85;
     uint16_t* vo = var_out + (size_t)sb * 85;
 #define PUT(i, m, q) do { mo[i] = (uint8_t)((m) >> 8); vo[i] = (uint16_t)(((q) - (m) * (m)) >> 16); } while (0)
@@ -128,7 +125,7 @@ __device__ __forceinline__ void sad_loop_fast(const SvtHipSadLoop& d, const uint
                 }
                 for (int m = 1; m < P; m <<= 1)   // P adjacent lanes hold the parts of one unit (groups never straddle the loop bound)
 #pragma unroll
-                    for (int c = 0; c < 8; c++) acc32[c] += (uint32_t)__shfl_xor((int)acc32[c], m, 64);
+                    for (int c = 0; c < 8; c++) acc32[c] += lane_xor(acc32[c], m);
                 const uint32_t idx0 = (uint32_t)((ty + y) * d.sa_w + tx + 8 * g);
                 if (part == 0) {
 #pragma unroll
@@ -176,7 +173,7 @@ sad_loop_kernel(const uint8_t* __restrict__ src, int src_stride, const uint8_t* 
         }
     }
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = shfl_xor64(best, m); best = o < best ? o : best; }
+    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = lane_xor(best, m); best = o < best ? o : best; }
     if ((tid & 63) == 0) s_best[tid >> 6] = best;
     __syncthreads();
     if (tid == 0) {
@@ -217,7 +214,7 @@ __device__ void sad_loop16_generic(uint16_t* __restrict__ s_blk, unsigned long l
         best = key < best ? key : best;
     }
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = shfl_xor64(best, m); best = o < best ? o : best; }
+    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = lane_xor(best, m); best = o < best ? o : best; }
     if ((tid & 63) == 0) s_best[tid >> 6] = best;
     __syncthreads();
     if (tid == 0) {
@@ -338,7 +335,7 @@ sad_loop16_lds_kernel(const uint16_t* __restrict__ src, int src_stride, const ui
         }
     }
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = shfl_xor64(best, m); best = o < best ? o : best; }
+    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = lane_xor(best, m); best = o < best ? o : best; }
     if (lane == 0) s_best[wave] = best;
     __syncthreads();
     if (tid == 0) {

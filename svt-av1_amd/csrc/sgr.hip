@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "lds_stage.h"
 
 // the difference planes are written once and read back much later by the walk: SVT_SGR_NT (A/B) marks those accesses non-temporal
@@ -190,14 +191,6 @@ constexpr int S_PW = S_TW + 2, S_P1H = S_TH + 2, S_P2H = S_TH / 2 + 1;
 constexpr int S_N1 = S_PW * S_P1H, S_N2 = S_PW * S_P2H, S_NP = S_N1 + S_N2;
 constexpr int S_KP = (S_NP + 255) / 256;
 
-__device__ __forceinline__ int32_t row16_sum(int32_t v) {   // every lane of a 16-lane row gets the row total
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);   // row_mirror
-    return v;
-}
-
 // ---- building blocks shared by the 8-bit search and apply kernels (64 x 32 tiles) --------------------------------------------
 // `in`: staged tile [S_IH][S_IW]; abmem: 2 * S_NP dwords of scratch that later hold A'/B' (two barriers inside)
 template <int BD = 8>
@@ -359,18 +352,14 @@ __device__ __forceinline__ void sgr10_filter(const uint32_t* __restrict__ abw, i
     }
 }
 
-// 16-lane row total of p0 + p1 as a 64-bit value (|p0|, |p1| < 2^31): the low 16 bits and the signed upper halves are reduced separately
-__device__ __forceinline__ long long row16_sum_wide(int32_t p0, int32_t p1) {
-    const int32_t lo = row16_sum((p0 & 0xFFFF) + (p1 & 0xFFFF));
-    const int32_t hi = row16_sum((p0 >> 16) + (p1 >> 16));
-    return (long long)hi * 65536 + lo;
-}
-
 // One parameter set of a tile that lies completely inside the picture, bit depth 8, for the sum-only and the 6-byte STORE forms: the same arithmetic as the
 // general loop body below as STRAIGHT-LINE code.  The general body asks `is this row inside the picture` and `does this set have filter 0 / 1` per row and per
 // sum; the compiler turned each into a scalar branch (~30 per set) and serialised the five DPP reductions behind s_nops: the projection sums took 21 % and the
 // stores 15 % of the launch for 11 % and 6 % of its instructions (tools/ubench/sgr_filter_probe.py on the MI355X).  Here the filter pair is a template
 // parameter, every row is valid, and the five reductions advance in lockstep.
+// SGR_ROW_SUMS_: row16_sum of every live x[q], q < n, step by step over all of them: no reduction waits for its own previous step (a function gives other code)
+#define SGR_STEP_(x, n, live, ctl) _Pragma("unroll") for (int q = 0; q < n; q++) if (live) x[q] += __builtin_amdgcn_mov_dpp(x[q], ctl, 0xF, 0xF, true);
+#define SGR_ROW_SUMS_(x, n, live) SGR_STEP_(x, n, live, DPP_QUAD_SWAP1) SGR_STEP_(x, n, live, DPP_QUAD_SWAP2) SGR_STEP_(x, n, live, DPP_ROW_HALF_MIRROR) SGR_STEP_(x, n, live, DPP_ROW_MIRROR)
 template <bool H0, bool H1, int STORE, int BD = 8>
 __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, const uint32_t* __restrict__ xt, const uint32_t (&P)[S_KP], const uint32_t (&M)[S_KP], uint32_t s0,
                                                   uint32_t s1, int tid, int i0, int j, const uint32_t (&X)[8], const int32_t (&CX)[8], const int32_t (&SV)[8],
@@ -396,6 +385,7 @@ __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, co
 #pragma unroll
         for (int r = 0; r < 8; r++) SGR_ST(&pairs_px[(size_t)r * dstride], ((uint32_t)(H0 ? D0[r] : 0) & 0xFFFFu) | ((uint32_t)(H1 ? D1[r] : 0) << 16));
     }
+    constexpr bool use[5] = {H0, H0 && H1, H1, H0, H1};   // which of H00, H01, H11, C0, C1 this filter pair has
     if (BD > 8) {
         // bit depth 10: |flt - u| < 2^14.1, a product < 2^28.1 -> four rows per int32 partial; the low 16 bits and the signed upper halves of the two partials are
         // reduced separately (ten values in lockstep), first inside the 16-lane rows, then over the four rows (row_bcast), and the wave's two totals per sum go to
@@ -407,23 +397,19 @@ __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, co
             if (H1) { g[2][r >> 2] += __mul24(D1[r], D1[r]); g[4][r >> 2] += __mul24(D1[r], SV[r]); }
             if (H0 && H1) g[1][r >> 2] += __mul24(D0[r], D1[r]);
         }
-        constexpr bool use10[5] = {H0, H0 && H1, H1, H0, H1};
         int32_t v[10];
 #pragma unroll
         for (int q = 0; q < 5; q++) { v[2 * q] = (g[q][0] & 0xFFFF) + (g[q][1] & 0xFFFF); v[2 * q + 1] = (g[q][0] >> 16) + (g[q][1] >> 16); }
-#define SGR_RED10_(ctl)                                                                     \
-        _Pragma("unroll") for (int q = 0; q < 10; q++) if (use10[q >> 1]) v[q] += __builtin_amdgcn_mov_dpp(v[q], ctl, 0xF, 0xF, true);
-        SGR_RED10_(0xB1) SGR_RED10_(0x4E) SGR_RED10_(0x141) SGR_RED10_(0x140)
-#undef SGR_RED10_
+        SGR_ROW_SUMS_(v, 10, use[q >> 1])
 #pragma unroll
         for (int q = 0; q < 10; q++)
-            if (use10[q >> 1]) {   // every lane of a row holds the row's total: rows 1 and 3 add the row before them, rows 2 and 3 add rows 0 + 1 -> the lanes of row 3 hold the wave's
-                v[q] += __builtin_amdgcn_update_dpp(0, v[q], 0x142, 0xA, 0xF, false);   // row_bcast:15
-                v[q] += __builtin_amdgcn_update_dpp(0, v[q], 0x143, 0xC, 0xF, false);   // row_bcast:31
+            if (use[q >> 1]) {   // every lane of a row holds the row's total: rows 1 and 3 add the row before them, rows 2 and 3 add rows 0 + 1 -> the lanes of row 3 hold the wave's
+                v[q] += __builtin_amdgcn_update_dpp(0, v[q], DPP_ROW_BCAST15, 0xA, 0xF, false);
+                v[q] += __builtin_amdgcn_update_dpp(0, v[q], DPP_ROW_BCAST31, 0xC, 0xF, false);
             }
         if ((tid & 63) == 63) {
 #pragma unroll
-            for (int q = 0; q < 10; q++) if (use10[q >> 1]) part_ep[(q >> 1) * 8 + (tid >> 6) * 2 + (q & 1)] = v[q];
+            for (int q = 0; q < 10; q++) if (use[q >> 1]) part_ep[(q >> 1) * 8 + (tid >> 6) * 2 + (q & 1)] = v[q];
         }
         return;
     }
@@ -434,12 +420,7 @@ __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, co
         if (H1) { h[2] += __mul24(D1[r], D1[r]); h[4] += __mul24(D1[r], SV[r]); }
         if (H0 && H1) h[1] += __mul24(D0[r], D1[r]);
     }
-    constexpr bool use[5] = {H0, H0 && H1, H1, H0, H1};
-    // the 16-lane row totals of the live sums, step by step over all of them: no reduction waits for its own previous step
-#define SGR_RED_(ctl)                                                                       \
-    _Pragma("unroll") for (int q = 0; q < 5; q++) if (use[q]) h[q] += __builtin_amdgcn_mov_dpp(h[q], ctl, 0xF, 0xF, true);
-    SGR_RED_(0xB1) SGR_RED_(0x4E) SGR_RED_(0x141) SGR_RED_(0x140)
-#undef SGR_RED_
+    SGR_ROW_SUMS_(h, 5, use[q])   // the 16-lane row totals of the live sums
     // the sixteen row totals of the workgroup go to slots of their own (plain stores): an LDS atomicAdd with a wave-uniform address is compiled into a
     // scalar loop over the active lanes (5 sums x 4 lanes x ~10 instructions per set); the tile's last step adds the sixteen slots
     if ((tid & 15) == 0) {
@@ -447,6 +428,8 @@ __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, co
         for (int q = 0; q < 5; q++) if (use[q]) part_ep[q * 16 + (tid >> 4)] = h[q];
     }
 }
+#undef SGR_ROW_SUMS_
+#undef SGR_STEP_
 
 // STORE: additionally leaves, per pixel, (flt0 - u) | (flt1 - u) << 16 (pairs[ep], int16 halves; sets 11 / 12 / 13 use the plane of 2 / 5 / 8), dat - src (sd,
 // int16) and per unit the sum of (dat - src)^2 (d2) for the on-device unit search (sgr_walk.hip): a probe pass then re-reads 6 bytes per pixel instead of
@@ -1190,13 +1173,8 @@ wiener_walk8w_kernel(const WnPic a) {
             sse += e;
         }
         // 64-lane sums, then the sixteen waves' partials
-        {   // DPP inside the 16-lane rows, the four row totals through scalar registers
-            int v = (int)sse;
-            v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);
-            v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true); v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);
-            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane(v, 0) + (uint32_t)__builtin_amdgcn_readlane(v, 16) + (uint32_t)__builtin_amdgcn_readlane(v, 32) + (uint32_t)__builtin_amdgcn_readlane(v, 48);
-            if (lane == 0) part[wave] = tot;
-        }
+        const uint32_t wave_tot = wave_sum_u32((uint32_t)sse);
+        if (lane == 0) part[wave] = wave_tot;
         lds_barrier();
         if (tid == 0) {
             unsigned long long tot = 0;

@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 
 #ifdef SVT_SGR_NT
 typedef int sgr_v4i __attribute__((ext_vector_type(4)));
@@ -194,13 +195,13 @@ __device__ bool replay(RegStore& K, WalkState& W, int ep, const ModelSums& MS) {
     return !spec;
 }
 
-// sum of a non-negative value below 2^48 over the wave, without LDS traffic: two 24-bit limbs, each reduced with four DPP adds (within a row of 16
-// lanes) and four v_readlane.  Uniform result.
+// sum of a non-negative value below 2^48 over the wave, without LDS traffic: two 24-bit limbs, each reduced with four DPP adds (within a row of 16 lanes: < 2^28)
+// and four v_readlane (< 2^30).  Uniform result.  row_sum_dpp: row16_sum in the builtin's other spelling (the header's gives the walk kernels other code).
 __device__ __forceinline__ int row_sum_dpp(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);    // quad_perm [1 0 3 2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);    // quad_perm [2 3 0 1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);   // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);   // row_mirror
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP1, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP2, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_HALF_MIRROR, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_MIRROR, 0xF, 0xF, false);
     return v;
 }
 __device__ __forceinline__ long long wave_sum_u48(long long v) {
@@ -209,7 +210,7 @@ __device__ __forceinline__ long long wave_sum_u48(long long v) {
     const long long shi = (long long)__builtin_amdgcn_readlane(hi, 0) + __builtin_amdgcn_readlane(hi, 16) + __builtin_amdgcn_readlane(hi, 32) + __builtin_amdgcn_readlane(hi, 48);
     return slo + (shi << 24);
 }
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
+__device__ __forceinline__ long long wave_sum_i64_down(long long v) {   // the 64-bit __shfl_xor from 32 down to 1: wave_sum_i64 gives the walk kernels other code
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -547,7 +548,7 @@ sgr_walk_resident_kernel(const WalkPic a) {
                         const int q = (xq * L.cx[o] + 1024) >> 11;
                         acc += (long long)q * q + 2ll * q * L.cy[o];
                     }
-                    const long long sum = wave_sum_i64(acc);
+                    const long long sum = wave_sum_i64_down(acc);
                     if (lane == 0) L.part[wave][c] = sum + r2w;
                 }
                 __syncthreads();   // B
@@ -877,7 +878,7 @@ sgr_walk_packed_kernel(const WalkPic a) {
                         const int q = (xq * L.cx[o] + 1024) >> 11;
                         acc += (long long)q * q + 2ll * q * L.cy[o];
                     }
-                    const long long sum = wave_sum_i64(acc);
+                    const long long sum = wave_sum_i64_down(acc);
                     if (lane == 0) L.part[wave][c] = sum + r2w;
                 }
                 __syncthreads();   // B

@@ -23,12 +23,6 @@ __device__ __forceinline__ int svt_xcd_order(int b, int n) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + s;
 #endif
 }
-// The sum of a 64-bit value over the 64 lanes of a wave, in every lane (__shfl_xor moves 32 bits: the halves travel apart).
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
 #endif
 #define SVT_HIP_TU_PROBE(name)                                                                                                    \
     namespace { __global__ void tu_probe_kernel_##name() {} }                                                                      \

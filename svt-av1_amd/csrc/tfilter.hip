@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 
 namespace {
 

@@ -21,6 +21,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "txfm_1d.h"
 #include "quant_dev.h"
 #include "intra_dev.h"
@@ -63,20 +64,10 @@ struct TplArgs {
     uint8_t* decision;
 };
 
-__device__ __forceinline__ int row_add(int v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int row_max(int v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int64_t row_add64(int64_t v) {
+__device__ __forceinline__ int64_t row_add64(int64_t v) {   // lanes_sum<16> with the low half shuffled first: the header's order gives the kernels other code
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)v >> 32), o, 64);
+        const uint32_t lo = lane_xor((uint32_t)v, o), hi = lane_xor((uint32_t)((uint64_t)v >> 32), o);
         v += (int64_t)(((uint64_t)hi << 32) | lo);
     }
     return v;
@@ -122,13 +113,13 @@ __device__ __forceinline__ void quant16(const SvtHipQuantParams& qp_arg, int lan
         const int64_t d = (int64_t)coef[c] - dq[c];
         se += d * d;
     }
-    e = row_max(e);
+    e = lanes_max<16>(e);
     se = row_add64(se);
     int bits = 0;
 #pragma unroll
     for (int c = 0; c < 16; c++)
         if ((int)kIscan16.v[lane * 16 + c] < e) bits += 32 - __clz(lv[c] + 1);
-    bits = row_add(bits);
+    bits = lanes_sum<16>(bits);
     eob = e;
     err = max(se >> 2, (int64_t)1);
     rate = want_rate ? (int64_t)(1 + bits) << 9 : 0;
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(TPL_ROWS_A * 16) void tpl_inter_kernel(const TplArg
             int sad = 0;
 #pragma unroll
             for (int r = 0; r < 16; r++) sad += abs(cur[r] - (int)p[(ptrdiff_t)r * stride]);
-            sad = row_add(sad);
+            sad = lanes_sum<16>(sad);
             if (valid && (uint32_t)sad < best_sad) { best_sad = (uint32_t)sad; win = s; }
         }
     }
@@ -249,7 +240,7 @@ __global__ __launch_bounds__(TPL_ROWS_A * 16) void tpl_inter_kernel(const TplArg
         int sum = 0;
 #pragma unroll
         for (int c = 0; c < 16; c++) sum += abs(coef[c]);
-        sum = row_add(sum);
+        sum = lanes_sum<16>(sum);
         if (valid && sum < best_cost) {
             best_cost = sum; best_rf = s; best_bx = bx; best_by = by; best_mvx = mvx; best_mvy = mvy;
 #pragma unroll
@@ -351,7 +342,7 @@ __global__ __launch_bounds__(TPL_ROWS_B * 16) void tpl_intra_step_kernel(const T
         }
     }
     int sa = ra[lane], sl = rl[lane];
-    sa = row_add(sa); sl = row_add(sl);
+    sa = lanes_sum<16>(sa); sl = lanes_sum<16>(sl);
     __syncthreads();
     const uint8_t* a = need_a ? fa : ra;
     const uint8_t* l = need_l ? fl : rl;

@@ -17,6 +17,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "tpl_synth.h"
 
 namespace {

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "lane_reduce.h"
 #include "txfm_1d.h"
 #include "quant_dev.h"
 #include "txfm_plan.h"
@@ -85,20 +86,10 @@ template <int N, int BIT, int CB> __device__ __forceinline__ void inv_1d(int kin
     }
 }
 
-template <int L> __device__ __forceinline__ uint32_t team_max(uint32_t v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
-    return v;
-}
-template <int L> __device__ __forceinline__ uint32_t team_add(uint32_t v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-template <int L> __device__ __forceinline__ uint64_t team_add64(uint64_t v) {
+template <int L> __device__ __forceinline__ uint64_t team_add64(uint64_t v) {   // lanes_sum<L> with the low half shuffled first: the header's order gives the kernels other code
 #pragma unroll
     for (int m = 1; m < L; m <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+        const uint32_t lo = lane_xor((uint32_t)v, m), hi = lane_xor((uint32_t)(v >> 32), m);
         v += ((uint64_t)hi << 32) | lo;
     }
     return v;
@@ -262,8 +253,8 @@ __device__ __forceinline__ void fwd_block(int32_t* __restrict__ tile, int wg, in
         }
     }
     // team reductions (all 64 lanes of each wave execute the shuffles)
-    eobmax = team_max<L>(eobmax);
-    sumabs = team_add<L>(sumabs);
+    eobmax = lanes_max<L>(eobmax);
+    sumabs = lanes_sum<L>(sumabs);
     if constexpr (KW != W || KH != H) energy = team_add64<L>(energy);
     if (live && t == 0) {
         if (eob_out && qcoeff) eob_out[blk] = (uint16_t)eobmax;
