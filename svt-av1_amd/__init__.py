@@ -127,6 +127,68 @@ class TfRef(C.Structure):     # SvtHipTfRef
     _fields_ = [("pred", C.c_void_p * 3), ("pred_stride", C.c_int * 3), ("blocks", C.c_void_p)]
 
 
+class CompBlk(C.Structure):
+    """SvtHipCompBlk (include/svt_hip.h)."""
+    _fields_ = [("src0_x", C.c_int32), ("src0_y", C.c_int32), ("src1_x", C.c_int32), ("src1_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
+                ("w", C.c_uint8), ("h", C.c_uint8), ("bank_x", C.c_uint8), ("bank_y", C.c_uint8),
+                ("subpel0_x", C.c_uint8), ("subpel0_y", C.c_uint8), ("subpel1_x", C.c_uint8), ("subpel1_y", C.c_uint8),
+                ("type", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("mask_type", C.c_uint8),
+                ("mask_sub", C.c_uint8), ("reserved", C.c_uint8 * 3), ("mask_off", C.c_int32), ("mask_stride", C.c_int32)]
+
+
+class ObmcBlk(C.Structure):
+    """SvtHipObmcBlk (include/svt_hip.h)."""
+    _fields_ = [("pre_x", C.c_int32), ("pre_y", C.c_int32), ("w", C.c_uint8), ("h", C.c_uint8), ("xoffset", C.c_uint8), ("yoffset", C.c_uint8), ("wm_off", C.c_int32)]
+
+
+class WarpBlk(C.Structure):
+    """SvtHipWarpBlk (include/svt_hip.h)."""
+    _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16),
+                ("p_col", C.c_int32), ("p_row", C.c_int32), ("p_width", C.c_uint8), ("p_height", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class WarpCompBlk(C.Structure):
+    """SvtHipWarpCompBlk (include/svt_hip.h)."""
+    _fields_ = [("blk", WarpBlk), ("cb_off", C.c_int32), ("cb_stride", C.c_int32), ("do_average", C.c_uint8), ("use_jnt_comp_avg", C.c_uint8),
+                ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8)]
+
+
+class BlendBlk(C.Structure):
+    """SvtHipBlendBlk (include/svt_hip.h)."""
+    _fields_ = [("src0_x", C.c_int32), ("src0_y", C.c_int32), ("src1_x", C.c_int32), ("src1_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
+                ("w", C.c_uint8), ("h", C.c_uint8), ("mode", C.c_uint8), ("subw", C.c_uint8), ("subh", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("mask_off", C.c_int32), ("mask_stride", C.c_int32)]
+
+
+class ExtSadJob(C.Structure):
+    """SvtHipExtSadJob (include/svt_hip.h)."""
+    _fields_ = [("src_off", C.c_int32), ("ref_off", C.c_int32), ("mv", C.c_uint32), ("sub_sad", C.c_int32)]
+
+
+class CdefSelectResult(C.Structure):
+    """SvtHipCdefSelectResult (include/svt_hip.h): the head of the selection's state."""
+    _fields_ = [("lev0", (C.c_int32 * 8) * 4), ("lev1", (C.c_int32 * 8) * 4), ("status", C.c_uint32 * 4), ("tot_mse", C.c_uint64 * 4)]
+
+
+CDEF_SELECT_STATE_BYTES = C.sizeof(CdefSelectResult) + 8192 + 4 * 128 * 4096 * 8   # SVT_HIP_CDEF_SELECT_STATE_BYTES
+
+
+class CdefFinish(C.Structure):
+    """SvtHipCdefFinish (include/svt_hip.h)."""
+    _fields_ = [("cdef_bits", C.c_int32), ("nb_strengths", C.c_int32), ("y_strength", C.c_int32 * 8), ("uv_strength", C.c_int32 * 8), ("best_cost", C.c_uint64)]
+
+
+class CdefBlk(C.Structure):
+    """SvtHipCdefBlk (include/svt_hip.h)."""
+    _fields_ = [("in_off", C.c_int32), ("dst_off", C.c_int32), ("pri_strength", C.c_int32), ("sec_strength", C.c_int32), ("dir", C.c_int32),
+                ("pri_damping", C.c_int32), ("sec_damping", C.c_int32), ("bw_log2", C.c_int32), ("bh_log2", C.c_int32), ("coeff_shift", C.c_int32)]
+
+
+class LpfEdge(C.Structure):
+    """SvtHipLpfEdge (include/svt_hip.h)."""
+    _fields_ = [("off", C.c_int32), ("dir", C.c_uint8), ("len", C.c_uint8), ("blimit", C.c_uint8), ("limit", C.c_uint8), ("thresh", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 class DlfSearch(C.Structure):
     """SvtHipDlfSearch (include/svt_hip.h)."""
     _fields_ = [("plane", C.c_int), ("dir", C.c_int), ("other_level", C.c_int), ("start_level", C.c_int), ("loop_filter_mode", C.c_int),
@@ -327,190 +389,208 @@ def tx_desc(x, y, tx_type):
     return (x & 0x3FFF) | ((y & 0x3FFF) << 14) | (tx_type << 28)
 
 
+vp, i32, sz, P = C.c_void_p, C.c_int, C.c_size_t, C.POINTER
+P3, I3 = vp * 3, i32 * 3   # `void *const p[3]`, `const int v[3]`
+_MEMCPY, _MEMCPY2D = [vp, vp, vp, sz], [vp, vp, sz, vp, sz, sz, sz]   # ctx, dst, src, bytes / ctx, dst, dst_pitch, src, src_pitch, width_bytes, rows
+# the head the restoration plane calls share: ctx, pix_bytes, bd, d_dgd, stride, d_src or d_dst, its stride, pw, ph, unit_size, ss_y
+_SGR = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32]
+# ... and the mode-decision tables: ctx, d_src, src_stride, pic_w, pic_h, sb_cols, n_sb, n_pus, pus, n_refs, refs, d_mv
+_MD = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]
+
+# name -> (restype, argtypes) of every function include/svt_hip.h declares, in the header's order, and svt_hip_setup_rtcd of include/svt_hip_rtcd.h.
+# tests/test_abi_binding.py compares each entry with the declaration (count, and pointer / integer width and sign / float per position).
+PROTOTYPES = {
+    # ---- context / memory
+    "svt_hip_init": (i32, [i32, P(vp)]),
+    "svt_hip_destroy": (None, [vp]),
+    "svt_hip_last_error": (C.c_char_p, [vp]),
+    "svt_hip_set_stream": (i32, [vp, vp]),
+    "svt_hip_sync": (i32, [vp]),
+    "svt_hip_malloc": (i32, [vp, P(vp), sz]),
+    "svt_hip_free": (i32, [vp, vp]),
+    "svt_hip_memcpy_h2d": (i32, _MEMCPY),
+    "svt_hip_memcpy_d2h": (i32, _MEMCPY),
+    "svt_hip_memcpy_d2d": (i32, _MEMCPY),
+    "svt_hip_memcpy2d_h2d": (i32, _MEMCPY2D),
+    "svt_hip_memcpy2d_d2h": (i32, _MEMCPY2D),
+    "svt_hip_memcpy_h2d_async": (i32, _MEMCPY),
+    "svt_hip_memcpy_d2h_async": (i32, _MEMCPY),
+    "svt_hip_memcpy2d_h2d_async": (i32, _MEMCPY2D),
+    "svt_hip_memcpy2d_d2h_async": (i32, _MEMCPY2D),
+    "svt_hip_host_register": (i32, [vp, vp, sz]),
+    "svt_hip_host_unregister": (i32, [vp, vp]),
+    "svt_hip_host_alloc": (i32, [vp, P(vp), sz]),
+    "svt_hip_host_free": (i32, [vp, vp]),
+    "svt_hip_device_count": (i32, [P(i32)]),
+    "svt_hip_warmup": (i32, [vp]),
+    "svt_hip_timer_start": (i32, [vp]),
+    "svt_hip_timer_stop_ms": (i32, [vp, P(C.c_float)]),
+    # ---- open-loop ME
+    "svt_hip_me_search_window": (SbSearch, [i32] * 8),
+    "svt_hip_me_fullpel_frame_dev": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
+    "svt_hip_me_fullpel_frame": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
+    "svt_hip_me_set_big_windows": (i32, [vp, i32]),
+    "svt_hip_me_get_big_windows": (i32, [vp, P(i32)]),
+    "svt_hip_me_set_waves_per_sb": (i32, [vp, i32]),
+    # ---- residual + transform + quantisation
+    "svt_hip_fwd_txfm_quant_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, P(QuantParams), P(ScanTables), vp, vp, vp, vp, vp, vp]),
+    "svt_hip_inv_txfm_add_batch_dev": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32]),
+    "svt_hip_iwht4x4_add_batch_dev": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]),
+    "svt_hip_fwd_txfm_quant_multi_dev": (i32, [vp, i32, vp, i32]),
+    "svt_hip_enc_txfm_multi_dev": (i32, [vp, i32, i32, P(EncTxJob), i32]),
+    "svt_hip_inv_txfm_add_multi_dev": (i32, [vp, i32, i32, vp, i32]),
+    # ---- deblocking loop filter
+    "svt_hip_dlf_build_edges": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "svt_hip_dlf_filtered_units": (i32, [i32, i32, i32, i32]),
+    "svt_hip_dlf_build_edges_crop": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "svt_hip_dlf_build_edges_picture_dev": (i32, [vp, vp, i32, i32, i32, i32, I3, I3, I3, I3, vp, P3, P3]),
+    "svt_hip_deblock_plane_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32]),
+    "svt_hip_deblock_frame_dev": (i32, [vp, P3, i32, I3, i32, P3, P3, I3, I3, i32]),
+    "svt_hip_deblock_frame_fused_dev": (i32, [vp, P3, P3, i32, I3, i32, I3, I3, P3, P3, I3, I3, i32]),
+    "svt_hip_plane_sse_dev": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
+    "svt_hip_dlf_search_level_dev": (i32, [vp, P(DlfSearch), vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, P(C.c_int), P(C.c_int64)]),
+    "svt_hip_dlf_search_levels_picture_dev": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+    # ---- CDEF
+    "svt_hip_cdef_search_frame_dev": (i32, [vp, i32, P3, I3, P3, I3, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "svt_hip_cdef_apply_frame_dev": (i32, [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]),
+    # ---- sub-pel prediction, block SAD / variance
+    "svt_hip_subpel_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32]),
+    "svt_hip_subpel_jobs_from_me_dev": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "svt_hip_block_sad_batch_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp]),
+    "svt_hip_block_variance_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
+    "svt_hip_coeff_distortion_batch_dev": (i32, [vp, vp, vp, i32, i32, vp]),
+    "svt_hip_block_sse_batch_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp]),
+    # ---- HME pyramids, variance pyramid, HME search
+    "svt_hip_downsample_2d_dev": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32]),
+    "svt_hip_variance_pyramid_dev": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "svt_hip_sad_loop_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp]),
+    "svt_hip_sad_loop16_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp]),
+    # ---- self-guided restoration
+    "svt_hip_sgr_filter_plane_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32]),
+    "svt_hip_sgr_search_plane_dev": (i32, _SGR + [C.c_uint32, vp]),
+    "svt_hip_sgr_apply_plane_dev": (i32, _SGR + [vp, i32, vp, vp]),
+    "svt_hip_sgr_proj_error_plane_dev": (i32, _SGR + [C.c_uint32, i32, vp, vp]),
+    "svt_hip_sgr_search_units_scratch_bytes": (sz, [i32, i32, i32]),
+    "svt_hip_sgr_search_units_plane_dev": (i32, _SGR + [C.c_uint32, vp, vp, vp, vp, vp, sz]),
+    "svt_hip_sgr_search_units_picture_dev": (i32, [vp, i32, i32, i32, P(SgrUnitsPlaneDev)]),
+    "svt_hip_sgr_search_units_plane": (i32, _SGR + [C.c_uint32, vp, vp, vp, vp]),
+    "svt_hip_sgr_search_units_picture": (i32, [vp, i32, i32, i32, P(SgrSearchPlane), vp]),
+    "svt_hip_lr_apply_plane_dev": (i32, _SGR + [vp, i32, vp, vp, vp]),
+    "svt_hip_lr_try_unit_dev": (i32, _SGR + [vp, i32, vp, vp, vp, vp, i32, i32, vp]),
+    "svt_hip_lr_try_units_dev": (i32, _SGR + [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp]),
+    "svt_hip_wiener_walk_units_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+    "svt_hip_wiener_walk_units_picture_dev": (i32, [vp, i32, i32, i32, P(WienerWalkPlane)]),
+    # ---- Wiener restoration search
+    "svt_hip_wiener_stats_plane_dev": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "svt_hip_wiener_init_units_dev": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
+    # ---- alt-ref temporal filtering
+    "svt_hip_tf_filter_frame_dev": (i32, [vp, i32, i32, P3, I3, P3, I3, i32, i32, i32, i32, i32, P(TfRef), i32, P(C.c_double), i32, i32, vp]),
+    "svt_hip_tf_estimate_noise_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svt_hip_tf_noise_sigma": (C.c_double, [C.c_int64, C.c_int64]),
+    "svt_hip_tf_subpel_frame_dev": (i32, [vp, i32, i32, P3, I3, P3, I3, P3, I3, i32, i32, C.c_uint64, i32, i32, vp, i32, vp]),
+    # ---- compound inter prediction
+    "svt_hip_compound_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]),
+    "svt_hip_obmc_cost_batch_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, vp]),
+    "svt_hip_warp_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32]),
+    "svt_hip_warp_compound_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, i32]),
+    "svt_hip_blend_a64_batch_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]),
+    # ---- picture formats around the high-bit-depth path
+    "svt_hip_picture_format_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]),
+    "svt_hip_generate_padding_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, i32]),
+    # ---- per-call forms
+    "svt_hip_quantize_batch_dev": (i32, [vp, vp, i32, i32, P(QuantParams), vp, vp, vp, vp]),
+    "svt_hip_residual_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]),
+    "svt_hip_ext_all_sad_8x8_16x16_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, i32, vp]),
+    "svt_hip_ext_eight_sad_32x32_64x64_batch_dev": (i32, [vp, vp, i32, vp]),
+    "svt_hip_interm_var_four8x8_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, vp]),
+    "svt_hip_handle_transform64_batch_dev": (i32, [vp, i32, vp, i32, vp]),
+    "svt_hip_handle_transform64_n2n4_batch_dev": (i32, [vp, i32, vp, i32]),
+    "svt_hip_upsampled_pred_batch_dev": (i32, [vp, vp, i32, vp, vp, i32]),
+    "svt_hip_jnt_convolve_dev": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32]),
+    "svt_hip_diffwtd_mask_dev": (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32]),
+    "svt_hip_blend_a64_d16_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32]),
+    "svt_hip_block_mean_batch_dev": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "svt_hip_ext_sad_16x16_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, i32, vp]),
+    "svt_hip_ext_sad_32x32_64x64_batch_dev": (i32, [vp, vp, vp, i32]),
+    "svt_hip_cdef_dist_dev": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svt_hip_cdef_search_one_dual_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "svt_hip_cdef_joint_strength_search_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "svt_hip_set_cdef_select_form": (i32, [vp, i32]),
+    "svt_hip_cdef_strength_select_dev": (i32, [vp, vp, vp, i32, i32, i32, vp, sz]),
+    "svt_hip_cdef_strength_select_multi_dev": (i32, [vp, i32, P(vp), P(vp), i32, i32, i32, P(vp), sz]),
+    "svt_hip_cdef_finish_dev": (i32, [vp, vp, vp, i32, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "svt_hip_sgr_flt_proj_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "svt_hip_convolve8_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32]),
+    "svt_hip_wiener_convolve_add_src_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32]),
+    "svt_hip_cdef_find_dir_batch_dev": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
+    "svt_hip_cdef_filter_block_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, i32]),
+    "svt_hip_lpf_edges_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32]),
+    # ---- mode decision: picture-level precompute
+    "svt_hip_md_fullpel_sad_picture_dev": (i32, _MD + [vp]),
+    "svt_hip_md_fullpel_avg_sad_picture_dev": (i32, _MD + [i32, vp, vp]),
+    "svt_hip_md_fullpel_sad_picture_hbd_dev": (i32, _MD + [vp]),
+    "svt_hip_md_fullpel_avg_sad_picture_hbd_dev": (i32, _MD + [i32, vp, vp]),
+    "svt_hip_md_subpel_grid_picture_dev": (i32, _MD + [i32, vp]),
+    "svt_hip_md_halfpel_grid_picture_dev": (i32, _MD + [i32, vp]),
+    # ---- intra prediction
+    "svt_hip_intra_predict_batch_dev": (i32, [vp, i32, i32, vp, vp, i32, vp, i32]),
+    "svt_hip_cfl_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp]),
+    "svt_hip_filter_intra_predict_batch_dev": (i32, [vp, i32, i32, vp, vp, i32, vp, i32]),
+    "svt_hip_intra_ois_picture_dev": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    # ---- TPL flow dispenser
+    "svt_hip_tpl_dispenser_scratch_bytes": (sz, [i32, i32]),
+    "svt_hip_tpl_dispenser_picture_dev": (i32, [vp, P(TplParams), vp, i32, P(TplRef), vp, vp, vp, vp, vp, i32, vp, vp]),
+    "svt_hip_tpl_set_phases": (i32, [vp, i32]),
+    # ---- TPL flow synthesizer, r0 / beta / lambda factors
+    "svt_hip_tpl_dep_bytes": (sz, [i32, i32, i32]),
+    "svt_hip_tpl_r0beta_out_bytes": (sz, [i32, i32, i32]),
+    "svt_hip_tpl_r0beta_scratch_bytes": (sz, []),
+    "svt_hip_tpl_synth_picture_dev": (i32, [vp, P(TplSynthParams), P(TplWindowFrame), i32, i32]),
+    "svt_hip_tpl_r0beta_dev": (i32, [vp, P(TplSynthParams), vp, vp, vp, vp]),
+    "svt_hip_tpl_window_dev": (i32, [vp, P(TplSynthParams), P(TplWindowFrame), i32, vp, vp]),
+    "svt_hip_tpl_window_host": (i32, [P(TplSynthParams), P(TplWindowFrame), i32, vp]),
+    # ---- global motion
+    "svt_hip_gm_shear_params_batch_dev": (i32, [vp, vp, i32, vp]),
+    "svt_hip_gm_warp_error_batch_dev": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]),
+    "svt_hip_gm_frame_error_batch_dev": (i32, [vp, vp, i32, i32, i32, P(GmRef), i32, vp]),
+    "svt_hip_gm_refine_scratch_bytes": (sz, [i32]),
+    "svt_hip_gm_refine_picture_dev": (i32, [vp, vp, i32, i32, i32, P(GmRef), i32, vp, i32, vp, vp, P(i32)]),
+    "svt_hip_gm_error_table": (i32, [vp]),
+    "svt_hip_gm_corners_scratch_bytes": (sz, [P(GmRef), i32]),
+    "svt_hip_gm_corners_batch_dev": (i32, [vp, P(GmRef), i32, i32, vp, vp, vp, vp]),
+    "svt_hip_gm_cross_correlation_batch_dev": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp]),
+    "svt_hip_gm_correspondences_batch_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, P(GmRef), i32, vp, vp, i32, vp, vp]),
+    "svt_hip_gm_fit_scratch_bytes": (sz, [i32, i32]),
+    "svt_hip_gm_fit_batch_dev": (i32, [vp, vp, vp, i32, i32, P(GmFitJob), i32, i32, i32, vp, vp, vp, vp]),
+    "svt_hip_gm_params_cost_host": (i32, [P(C.c_int32), i32, i32]),
+    "svt_hip_gm_decide_host": (i32, [P(GmModelRecord), C.c_int64, i32, i32, P(C.c_int32), P(C.c_int32)]),
+    "svt_hip_gm_estimate_scratch_bytes": (sz, [i32, i32, i32, P(GmEstimateOptions)]),
+    "svt_hip_gm_estimate_picture_dev": (i32, [vp, vp, i32, i32, i32, P(GmRef), i32, P(GmEstimateOptions), P(GmEstimate), vp]),
+    # ---- include/svt_hip_rtcd.h
+    "svt_hip_setup_rtcd": (i32, [vp, vp]),
+}
+
+
+def bind(L):
+    """Attach PROTOTYPES to every function of them that the loaded library `L` exports (a test double may export only part of the ABI) -> L."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+    return L
+
+
 _lib = None
 
 
-CDEF_SELECT_STATE_BYTES = 304 + 8192 + 4 * 128 * 4096 * 8   # SVT_HIP_CDEF_SELECT_STATE_BYTES (include/svt_hip.h)
-
-
 def lib():
-    """Load libsvtav1_hip.so (once) and attach prototypes. Raises if the library was not built."""
+    """Load libsvtav1_hip.so (once) and attach the prototypes. Raises if the library was not built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(LIB_PATH)
-    vp, i32, u8p, u32p = C.c_void_p, C.c_int, C.c_void_p, C.c_void_p
-    P3, I3 = C.c_void_p * 3, C.c_int * 3
-    L.svt_hip_init.argtypes = [i32, C.POINTER(vp)]
-    L.svt_hip_destroy.argtypes = [vp]
-    L.svt_hip_destroy.restype = None
-    L.svt_hip_last_error.argtypes = [vp]
-    L.svt_hip_last_error.restype = C.c_char_p
-    L.svt_hip_set_stream.argtypes = [vp, vp]
-    L.svt_hip_sync.argtypes = [vp]
-    L.svt_hip_malloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
-    L.svt_hip_free.argtypes = [vp, vp]
-    L.svt_hip_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy_d2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy2d_h2d.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.svt_hip_memcpy2d_d2h.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.svt_hip_memcpy_h2d_async.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy_d2h_async.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy2d_h2d_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.svt_hip_memcpy2d_d2h_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.svt_hip_host_register.argtypes = [vp, vp, C.c_size_t]
-    L.svt_hip_host_unregister.argtypes = [vp, vp]
-    L.svt_hip_host_alloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
-    L.svt_hip_host_free.argtypes = [vp, vp]
-    L.svt_hip_device_count.argtypes = [C.POINTER(i32)]
-    L.svt_hip_warmup.argtypes = [vp]
-    L.svt_hip_timer_start.argtypes = [vp]
-    L.svt_hip_timer_stop_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    L.svt_hip_me_search_window.argtypes = [i32] * 8
-    L.svt_hip_me_search_window.restype = SbSearch
-    L.svt_hip_me_fullpel_frame_dev.argtypes = [vp, u8p, u8p, i32, i32, i32, vp, i32, i32, u32p, u32p]
-    L.svt_hip_me_fullpel_frame.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, vp, i32, i32, u32p, u32p]
-    L.svt_hip_me_set_waves_per_sb.argtypes = [vp, i32]
-    L.svt_hip_me_set_big_windows.argtypes = [vp, i32]
-    L.svt_hip_me_get_big_windows.argtypes = [vp, C.POINTER(i32)]
-    L.svt_hip_cdef_strength_select_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_size_t]
-    L.svt_hip_cdef_strength_select_multi_dev.argtypes = [vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i32, i32, i32, C.POINTER(C.c_void_p), C.c_size_t]
-    L.svt_hip_set_cdef_select_form.argtypes = [vp, i32]
-    L.svt_hip_cdef_finish_dev.argtypes = [vp, vp, vp, i32, vp, C.c_uint64, vp, vp, vp, vp, vp]
-    L.svt_hip_dlf_filtered_units.argtypes = [i32, i32, i32, i32]
-    L.svt_hip_subpel_jobs_from_me_dev.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.svt_hip_fwd_txfm_quant_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(QuantParams),
-                                                   C.POINTER(ScanTables), vp, vp, vp, vp, vp, vp]
-    L.svt_hip_inv_txfm_add_batch_dev.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32]
-    L.svt_hip_iwht4x4_add_batch_dev.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]
-    L.svt_hip_fwd_txfm_quant_multi_dev.argtypes = [vp, i32, vp, i32]
-    L.svt_hip_enc_txfm_multi_dev.argtypes = [vp, i32, i32, C.POINTER(EncTxJob), i32]
-    L.svt_hip_inv_txfm_add_multi_dev.argtypes = [vp, i32, i32, vp, i32]
-    L.svt_hip_dlf_build_edges.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    L.svt_hip_wiener_init_units_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.svt_hip_dlf_build_edges_picture_dev.argtypes = [vp, vp, i32, i32, i32, i32, I3, I3, I3, I3, vp, P3, P3]
-    L.svt_hip_deblock_plane_dev.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32]
-    L.svt_hip_subpel_predict_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32]
-    L.svt_hip_block_sad_batch_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp]
-    L.svt_hip_md_fullpel_sad_picture_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
-    L.svt_hip_md_fullpel_avg_sad_picture_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp]
-    L.svt_hip_md_fullpel_sad_picture_hbd_dev.argtypes = L.svt_hip_md_fullpel_sad_picture_dev.argtypes
-    L.svt_hip_md_fullpel_avg_sad_picture_hbd_dev.argtypes = L.svt_hip_md_fullpel_avg_sad_picture_dev.argtypes
-    L.svt_hip_md_subpel_grid_picture_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp]
-    L.svt_hip_md_halfpel_grid_picture_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp]
-    L.svt_hip_block_variance_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]
-    L.svt_hip_coeff_distortion_batch_dev.argtypes = [vp, vp, vp, i32, i32, vp]
-    L.svt_hip_block_sse_batch_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp]
-    L.svt_hip_downsample_2d_dev.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, i32]
-    L.svt_hip_variance_pyramid_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    L.svt_hip_sad_loop_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp]
-    L.svt_hip_sgr_filter_plane_dev.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32]
-    L.svt_hip_sgr_search_plane_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint32, vp]
-    L.svt_hip_sgr_apply_plane_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]
-    L.svt_hip_sgr_proj_error_plane_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint32, i32, vp, vp]
-    L.svt_hip_sgr_search_units_plane.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp, vp]
-    L.svt_hip_sgr_search_units_scratch_bytes.argtypes = [i32, i32, i32]
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_sgr_search_units_plane_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t]
-    L.svt_hip_sgr_search_units_picture_dev.argtypes = [vp, i32, i32, i32, C.POINTER(SgrUnitsPlaneDev)]
-    L.svt_hip_sgr_search_units_picture.argtypes = [vp, i32, i32, i32, C.POINTER(SgrSearchPlane), vp]
-    L.svt_hip_lr_apply_plane_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
-    L.svt_hip_lr_try_units_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp]
-    L.svt_hip_lr_try_unit_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp]
-    L.svt_hip_wiener_stats_plane_dev.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]
-    L.svt_hip_tf_filter_frame_dev.argtypes = [vp, i32, i32, P3, I3, P3, I3, i32, i32, i32, i32, i32, C.POINTER(TfRef), i32,
-                                              C.POINTER(C.c_double), i32, i32, vp]
-    L.svt_hip_tf_subpel_frame_dev.argtypes = [vp, i32, i32, P3, I3, P3, I3, P3, I3, i32, i32, C.c_uint64, i32, i32, vp, i32, vp]
-    L.svt_hip_compound_predict_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]
-    L.svt_hip_obmc_cost_batch_dev.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp]
-    L.svt_hip_warp_predict_batch_dev.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32]
-    L.svt_hip_warp_compound_batch_dev.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, i32]
-    L.svt_hip_blend_a64_batch_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]
-    L.svt_hip_deblock_frame_dev.argtypes = [vp, P3, i32, I3, i32, P3, P3, I3, I3, i32]
-    L.svt_hip_wiener_walk_units_dev.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp]
-    L.svt_hip_wiener_walk_units_picture_dev.argtypes = [vp, i32, i32, i32, C.POINTER(WienerWalkPlane)]
-    L.svt_hip_deblock_frame_fused_dev.argtypes = [vp, P3, P3, i32, I3, i32, I3, I3, P3, P3, I3, I3, i32]
-    L.svt_hip_picture_format_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]
-    L.svt_hip_generate_padding_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32]
-    L.svt_hip_sad_loop16_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp]
-    L.svt_hip_tf_estimate_noise_dev.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.svt_hip_tf_noise_sigma.argtypes = [C.c_int64, C.c_int64]
-    L.svt_hip_tf_noise_sigma.restype = C.c_double
-    L.svt_hip_plane_sse_dev.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
-    # per-call forms
-    L.svt_hip_quantize_batch_dev.argtypes = [vp, vp, i32, i32, C.POINTER(QuantParams), vp, vp, vp, vp]
-    L.svt_hip_residual_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]
-    L.svt_hip_ext_all_sad_8x8_16x16_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp]
-    L.svt_hip_ext_eight_sad_32x32_64x64_batch_dev.argtypes = [vp, vp, i32, vp]
-    L.svt_hip_interm_var_four8x8_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, vp]
-    L.svt_hip_handle_transform64_batch_dev.argtypes = [vp, i32, vp, i32, vp]
-    L.svt_hip_upsampled_pred_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32]
-    L.svt_hip_handle_transform64_n2n4_batch_dev.argtypes = [vp, i32, vp, i32]
-    L.svt_hip_diffwtd_mask_dev.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32]
-    L.svt_hip_blend_a64_d16_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32]
-    L.svt_hip_jnt_convolve_dev.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32]
-    L.svt_hip_block_mean_batch_dev.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, vp]
-    L.svt_hip_ext_sad_16x16_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp]
-    L.svt_hip_ext_sad_32x32_64x64_batch_dev.argtypes = [vp, vp, vp, i32]
-    L.svt_hip_cdef_dist_dev.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.svt_hip_cdef_search_one_dual_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]
-    L.svt_hip_cdef_joint_strength_search_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]
-    L.svt_hip_cdef_strength_select_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_size_t]
-    L.svt_hip_sgr_flt_proj_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.svt_hip_convolve8_dev.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32]
-    L.svt_hip_wiener_convolve_add_src_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32]
-    L.svt_hip_cdef_find_dir_batch_dev.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
-    L.svt_hip_cdef_filter_block_batch_dev.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32]
-    L.svt_hip_lpf_edges_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, i32]
-    L.svt_hip_dlf_search_levels_picture_dev.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
-    L.svt_hip_dlf_search_level_dev.argtypes = [vp, C.POINTER(DlfSearch), vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp,
-                                               C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-    L.svt_hip_setup_rtcd.argtypes = [vp, vp]
-    L.svt_hip_cdef_search_frame_dev.argtypes = [vp, i32, P3, I3, P3, I3, i32, i32, vp, i32, i32, vp, vp, vp]
-    L.svt_hip_cdef_apply_frame_dev.argtypes = [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]
-    L.svt_hip_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
-    L.svt_hip_intra_ois_picture_dev.argtypes = [vp, u8p, i32, i32, i32, i32, u8p, vp]
-    L.svt_hip_cfl_predict_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp]
-    L.svt_hip_filter_intra_predict_batch_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32]
-    L.svt_hip_tpl_dispenser_scratch_bytes.argtypes = [i32, i32]
-    L.svt_hip_tpl_dispenser_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_tpl_set_phases.argtypes = [vp, i32]
-    L.svt_hip_tpl_dispenser_picture_dev.argtypes = [vp, C.POINTER(TplParams), u8p, i32, C.POINTER(TplRef), vp, u8p, u8p, vp, u8p, i32, vp, vp]
-    L.svt_hip_tpl_dep_bytes.argtypes = [i32, i32, i32]
-    L.svt_hip_tpl_dep_bytes.restype = C.c_size_t
-    L.svt_hip_tpl_r0beta_out_bytes.argtypes = [i32, i32, i32]
-    L.svt_hip_tpl_r0beta_out_bytes.restype = C.c_size_t
-    L.svt_hip_tpl_r0beta_scratch_bytes.argtypes = []
-    L.svt_hip_tpl_r0beta_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_tpl_synth_picture_dev.argtypes = [vp, C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, i32]
-    L.svt_hip_tpl_r0beta_dev.argtypes = [vp, C.POINTER(TplSynthParams), vp, vp, vp, vp]
-    L.svt_hip_tpl_window_dev.argtypes = [vp, C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, vp, vp]
-    L.svt_hip_tpl_window_host.argtypes = [C.POINTER(TplSynthParams), C.POINTER(TplWindowFrame), i32, vp]
-    L.svt_hip_gm_error_table.argtypes = [vp]
-    L.svt_hip_gm_shear_params_batch_dev.argtypes = [vp, vp, i32, vp]
-    L.svt_hip_gm_warp_error_batch_dev.argtypes = [vp, u8p, i32, i32, i32, u8p, i32, i32, i32, vp, i32, vp]
-    L.svt_hip_gm_frame_error_batch_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, vp]
-    L.svt_hip_gm_refine_scratch_bytes.argtypes = [i32]
-    L.svt_hip_gm_refine_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_gm_refine_picture_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, vp, i32, vp, vp, C.POINTER(i32)]
-    L.svt_hip_gm_corners_scratch_bytes.argtypes = [C.POINTER(GmRef), i32]
-    L.svt_hip_gm_corners_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_gm_corners_batch_dev.argtypes = [vp, C.POINTER(GmRef), i32, i32, vp, vp, vp, vp]
-    L.svt_hip_gm_cross_correlation_batch_dev.argtypes = [vp, u8p, i32, u8p, i32, i32, i32, vp, i32, vp]
-    L.svt_hip_gm_correspondences_batch_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp, C.POINTER(GmRef), i32, vp, vp, i32, vp, vp]
-    L.svt_hip_gm_fit_scratch_bytes.argtypes = [i32, i32]
-    L.svt_hip_gm_fit_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_gm_fit_batch_dev.argtypes = [vp, vp, vp, i32, i32, C.POINTER(GmFitJob), i32, i32, i32, vp, vp, vp, vp]
-    L.svt_hip_gm_params_cost_host.argtypes = [C.POINTER(C.c_int32), i32, i32]
-    L.svt_hip_gm_decide_host.argtypes = [C.POINTER(GmModelRecord), C.c_int64, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.svt_hip_gm_estimate_scratch_bytes.argtypes = [i32, i32, i32, C.POINTER(GmEstimateOptions)]
-    L.svt_hip_gm_estimate_scratch_bytes.restype = C.c_size_t
-    L.svt_hip_gm_estimate_picture_dev.argtypes = [vp, u8p, i32, i32, i32, C.POINTER(GmRef), i32, C.POINTER(GmEstimateOptions), C.POINTER(GmEstimate), vp]
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        _lib = bind(C.CDLL(LIB_PATH))
+    return _lib
 
 
 class Context:

@@ -4,15 +4,10 @@ import ctypes as C
 
 import numpy as np
 
+from conftest import load_package
 
-class CompBlk(C.Structure):
-    _fields_ = [("src0_x", C.c_int32), ("src0_y", C.c_int32), ("src1_x", C.c_int32), ("src1_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
-                ("w", C.c_uint8), ("h", C.c_uint8), ("bank_x", C.c_uint8), ("bank_y", C.c_uint8),
-                ("subpel0_x", C.c_uint8), ("subpel0_y", C.c_uint8), ("subpel1_x", C.c_uint8), ("subpel1_y", C.c_uint8),
-                ("type", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("mask_type", C.c_uint8),
-                ("mask_sub", C.c_uint8), ("reserved", C.c_uint8 * 3), ("mask_off", C.c_int32), ("mask_stride", C.c_int32)]
-
-
+_pkg = load_package()
+CompBlk, WarpBlk, WarpCompBlk, BlendBlk, ObmcBlk = _pkg.CompBlk, _pkg.WarpBlk, _pkg.WarpCompBlk, _pkg.BlendBlk, _pkg.ObmcBlk   # the block records of the C ABI
 assert C.sizeof(CompBlk) == 48
 SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (4, 8), (8, 4), (16, 8), (8, 16), (32, 16), (16, 32), (64, 32), (32, 64), (128, 64), (64, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
 # quant_dist_lookup_table[order_idx][..] pairs the encoder uses for COMPOUND_DISTANCE (fwd + bck = 16)
@@ -57,11 +52,6 @@ def make_blocks(rng, W, H, n, mask_bytes):
 
 
 # ---------------------------------------------------------------- warped prediction
-class WarpBlk(C.Structure):
-    _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16),
-                ("p_col", C.c_int32), ("p_row", C.c_int32), ("p_width", C.c_uint8), ("p_height", C.c_uint8), ("reserved", C.c_uint8 * 2)]
-
-
 assert C.sizeof(WarpBlk) == 44
 WARP_SIZES = [(8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (8, 16), (16, 8), (32, 16), (16, 32), (64, 32), (32, 64), (128, 64), (64, 128), (8, 32), (32, 8), (16, 64), (64, 16)]
 
@@ -98,12 +88,6 @@ def warp_blocks(rng, W, H, n):
 
 
 # ---------------------------------------------------------------- pixel-domain mask blends
-class BlendBlk(C.Structure):
-    _fields_ = [("src0_x", C.c_int32), ("src0_y", C.c_int32), ("src1_x", C.c_int32), ("src1_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
-                ("w", C.c_uint8), ("h", C.c_uint8), ("mode", C.c_uint8), ("subw", C.c_uint8), ("subh", C.c_uint8), ("reserved", C.c_uint8 * 3),
-                ("mask_off", C.c_int32), ("mask_stride", C.c_int32)]
-
-
 assert C.sizeof(BlendBlk) == 40
 BLEND_SIZES = [(1, 1), (2, 2), (4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (2, 8), (8, 2), (4, 16), (16, 4), (64, 8), (8, 64), (128, 32), (32, 128), (1, 16), (16, 1)]
 
@@ -419,10 +403,6 @@ def numpy_blend_block(b, s0, s1, masks, ignore_subh=False):
 
 
 # ---------------------------------------------------------------- OBMC costs
-class ObmcBlk(C.Structure):
-    _fields_ = [("pre_x", C.c_int32), ("pre_y", C.c_int32), ("w", C.c_uint8), ("h", C.c_uint8), ("xoffset", C.c_uint8), ("yoffset", C.c_uint8), ("wm_off", C.c_int32)]
-
-
 assert C.sizeof(ObmcBlk) == 16
 OBMC_CONTENTS = ("random", "pre_max", "pre_0", "halves")
 OBMC_OFFSETS = ((0, 0), (1, 0), (0, 1), (1, 1))
@@ -655,11 +635,6 @@ def warp_expected(orc, lst, ss, bd, dt):
     exp = dst0.copy()
     orc.orc_warp_predict_batch(plane.itemsize, bd, _vp(plane), w, h, stride, _vp(exp), lst.dst_w, ss[0], ss[1], lst.blks, lst.n)
     return plane, dst0, exp
-
-
-class WarpCompBlk(C.Structure):
-    _fields_ = [("blk", WarpBlk), ("cb_off", C.c_int32), ("cb_stride", C.c_int32), ("do_average", C.c_uint8), ("use_jnt_comp_avg", C.c_uint8),
-                ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8)]
 
 
 assert C.sizeof(WarpCompBlk) == 56

@@ -77,7 +77,6 @@ def product_host_edges(mi, cols, rows, plane, pw, ph, filt_w=None, filt_h=None):
     ev = np.zeros((uh, uw), np.uint16); eh = np.zeros((uh, uw), np.uint16)
     raw = records(mi, cols, rows)
     L = pkg.lib()
-    L.svt_hip_dlf_build_edges_crop.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 2
     assert L.svt_hip_dlf_build_edges_crop(ptr(raw), cols, rows, plane, ss, ss, pw, ph, uw if filt_w is None else filt_w, uh if filt_h is None else filt_h, ptr(ev), ptr(eh)) == 0
     return ev, eh
 

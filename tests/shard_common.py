@@ -7,31 +7,16 @@ import zlib
 
 import numpy as np
 
-from conftest import ROOT
+from conftest import ROOT, load_package
 
 MOCK_LIB = os.path.join(ROOT, "oracle", "_ref", "mock", "libsvtav1_hip.so")
-STATE_BYTES = 304 + 8192 + 4 * 128 * 4096 * 8   # SVT_HIP_CDEF_SELECT_STATE_BYTES
-vp, i32 = C.c_void_p, C.c_int32
+STATE_BYTES = load_package().CDEF_SELECT_STATE_BYTES
+vp = C.c_void_p
 P3, I3 = C.c_void_p * 3, C.c_int * 3
 
 
 def load(path):
-    L = C.CDLL(path)
-    L.svt_hip_init.argtypes = [i32, C.POINTER(vp)]
-    L.svt_hip_malloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
-    L.svt_hip_free.argtypes = [vp, vp]
-    L.svt_hip_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_memcpy_d2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.svt_hip_me_fullpel_frame.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
-    L.svt_hip_deblock_frame_dev.argtypes = [vp, P3, i32, I3, i32, P3, P3, I3, I3, i32]
-    L.svt_hip_cdef_search_frame_dev.argtypes = [vp, i32, P3, I3, P3, I3, i32, i32, vp, i32, i32, vp, vp, vp]
-    L.svt_hip_cdef_strength_select_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.c_size_t]
-    L.svt_hip_cdef_finish_dev.argtypes = [vp, vp, vp, i32, vp, C.c_uint64, vp, vp, vp, vp, vp]
-    L.svt_hip_cdef_apply_frame_dev.argtypes = [vp, i32, P3, P3, I3, i32, i32, vp, vp, vp, i32, i32, vp, vp]
-    L.svt_hip_last_error.restype = C.c_char_p; L.svt_hip_last_error.argtypes = [vp]
-    L.svt_hip_destroy.argtypes = [vp]
-    return L
+    return load_package().bind(C.CDLL(path))
 
 
 class Dev:

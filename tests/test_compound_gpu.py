@@ -3,8 +3,6 @@ svt_av1_[highbd_]jnt_convolve_*_c calls, svt_av1_build_compound_diffwtd_mask_d16
 All 22 AV1 block sizes, the four convolve flavours per reference, average / distance / diff-weighted / supplied-mask (also sub-sampled).
 The test_*_every_* tests and test_warp_compound_batched launch the deterministic lists of tests/comp_common.py, whose content tests/test_comp_ref_cpu.py proves
 on the CPU: one launch per list and format, every buffer the kernel writes pre-filled with a non-zero pattern that must survive outside the blocks."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -61,21 +59,17 @@ def test_compound_empty_and_bad_args(hip):
     assert hip.L.svt_hip_compound_predict_batch_dev(hip.h, 1, 8, None, 0, None, 0, None, 0, None, None, 3) != 0
 
 
-class ObmcBlk(C.Structure):
-    _fields_ = [("pre_x", C.c_int32), ("pre_y", C.c_int32), ("w", C.c_uint8), ("h", C.c_uint8), ("xoffset", C.c_uint8), ("yoffset", C.c_uint8), ("wm_off", C.c_int32)]
-
-
 def test_obmc_costs(hip, orc):
     """svt_hip_obmc_cost_batch_dev vs the oracle (pinned to svt_aom_obmc_sad / obmc_variance / obmc_sub_pixel_variance for all block sizes)."""
     rng = np.random.default_rng(9)
     W, H = 640, 480
     pre = rng.integers(0, 256, (H, W)).astype(np.uint8); pre[:140, :140] = 255
     n = 4 * len(cmc.SIZES)
-    blks = (ObmcBlk * n)()
+    blks = (cmc.ObmcBlk * n)()
     off = 0
     for i in range(n):
         w, h = cmc.SIZES[i % len(cmc.SIZES)]
-        blks[i] = ObmcBlk(int(rng.integers(0, W - 130)) if i else 0, int(rng.integers(0, H - 130)) if i else 0, w, h,
+        blks[i] = cmc.ObmcBlk(int(rng.integers(0, W - 130)) if i else 0, int(rng.integers(0, H - 130)) if i else 0, w, h,
                           0 if i % 3 == 0 else int(rng.integers(0, 8)), 0 if i % 3 == 0 else int(rng.integers(0, 8)), off)
         off += w * h
     wsrc = rng.integers(0, 255 * 4096 + 1, off).astype(np.int32); mask = rng.integers(0, 4097, off).astype(np.int32)

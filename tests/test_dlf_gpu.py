@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import ptr
+from conftest import load_package, ptr
 import dlf_common as dc
 import fmt_common as fc
 
@@ -369,10 +369,7 @@ def test_edge_planes_built_on_the_device(hip, w, h, pad):
     hip.free(d_mi)
 
 
-class LpfEdge(C.Structure):          # SvtHipLpfEdge (include/svt_hip.h)
-    _fields_ = [("off", C.c_int32), ("dir", C.c_uint8), ("len", C.c_uint8), ("blimit", C.c_uint8), ("limit", C.c_uint8), ("thresh", C.c_uint8), ("reserved", C.c_uint8 * 3)]
-
-
+LpfEdge = load_package().LpfEdge
 assert C.sizeof(LpfEdge) == 12
 
 

@@ -1,5 +1,5 @@
-"""CPU: the entry points of the global-motion front half (corners, cross-correlation, correspondences) are declared, exported and bound, and calls the host can
-see to be wrong are refused with SVT_HIP_ERR_BAD_ARG before anything touches HIP (no device exists here: a call that reached the runtime would fail differently
+"""CPU: the entry points of the global-motion front half (corners, cross-correlation, correspondences) have their Context methods and the header compiles as C99
+(declarations, exports and prototypes: tests/test_abi_binding.py), and calls the host can see to be wrong are refused with SVT_HIP_ERR_BAD_ARG before anything touches HIP (no device exists here: a call that reached the runtime would fail differently
 or crash).  The same bad arguments with a live context are checked in tests/test_gm_front_gpu.py."""
 import ctypes as C
 import os
@@ -8,7 +8,6 @@ import subprocess
 
 from conftest import ROOT
 
-NAMES = ("svt_hip_gm_corners_batch_dev", "svt_hip_gm_cross_correlation_batch_dev", "svt_hip_gm_correspondences_batch_dev")
 BAD_ARG = 2   # SVT_HIP_ERR_BAD_ARG
 
 
@@ -17,16 +16,8 @@ def _header():
 
 
 def test_declared_exported_bound(pkg):
-    L = pkg.lib()
     hdr = _header()
     assert re.search(r"SVT_HIP_ERR_BAD_ARG\s*=\s*%d\b" % BAD_ARG, hdr)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for n in NAMES:
-        assert re.search(r"^int\s+%s\s*\(SvtHipCtx \*ctx" % n, hdr, flags=re.M), f"{n} not declared in include/svt_hip.h"
-        assert re.search(r"\sT\s+%s$" % n, out, flags=re.M), f"{n} not exported"
-        assert getattr(L, n).argtypes, f"{n}: no argtypes"
-    assert re.search(r"^size_t\s+svt_hip_gm_corners_scratch_bytes\s*\(const SvtHipGmRef \*planes, int n_planes\)", hdr, flags=re.M)
-    assert re.search(r"\sT\s+svt_hip_gm_corners_scratch_bytes$", out, flags=re.M)
     for m in ("gm_corners_batch", "gm_cross_correlation_batch", "gm_correspondences_batch"):
         assert hasattr(pkg.Context, m)
     assert int(re.search(r"#define SVT_HIP_GM_MAX_CORNERS (\d+)", hdr).group(1)) == pkg.GM_MAX_CORNERS == 4096

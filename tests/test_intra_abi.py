@@ -1,14 +1,12 @@
-"""CPU: the two intra entry points are declared, exported and bound, the job structure matches the header, and calls the host can see to be wrong are
-refused with SVT_HIP_ERR_BAD_ARG before anything touches HIP (no device exists here: a call that reached the runtime would fail differently or crash).
+"""CPU: the two intra entry points have their Context methods (declarations, exports, prototypes and layouts: tests/test_abi_binding.py), and calls the host
+can see to be wrong are refused with SVT_HIP_ERR_BAD_ARG before anything touches HIP (no device exists here: a call that reached the runtime would fail differently or crash).
 The same bad arguments with a live context are checked in tests/test_intra_ois_gpu.py and tests/test_intra_predict_gpu.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 from conftest import ROOT
 
-NAMES = ("svt_hip_intra_predict_batch_dev", "svt_hip_intra_ois_picture_dev")
 BAD_ARG = 2   # SVT_HIP_ERR_BAD_ARG
 
 
@@ -17,29 +15,8 @@ def _header():
 
 
 def test_declared_exported_bound(pkg):
-    L = pkg.lib()
-    hdr = _header()
-    assert re.search(r"SVT_HIP_ERR_BAD_ARG\s*=\s*%d\b" % BAD_ARG, hdr)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for n in NAMES:
-        assert re.search(r"^int\s+%s\s*\(SvtHipCtx \*ctx" % n, hdr, flags=re.M), f"{n} not declared in include/svt_hip.h"
-        assert re.search(r"\sT\s+%s$" % n, out, flags=re.M), f"{n} not exported"
-        assert getattr(L, n).argtypes, f"{n}: no argtypes"
-    assert "} SvtHipIntraJob;" in hdr
-    assert hasattr(pkg, "IntraJob") and hasattr(pkg.Context, "intra_ois_picture") and hasattr(pkg.Context, "intra_predict_batch")
-
-
-def test_job_structure_matches_the_header(pkg, tmp_path):
-    """sizeof / offsets of the ctypes mirror against a C99 compiler's view of include/svt_hip.h."""
-    fields = [f[0] for f in pkg.IntraJob._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "svt_hip.h"\nint main(void){printf("%d", (int)sizeof(SvtHipIntraJob));' +
-                   "".join(f'printf(" %d", (int)offsetof(SvtHipIntraJob, {f}));' for f in fields) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["cc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(pkg.IntraJob)
-    assert got[1:] == [getattr(pkg.IntraJob, f).offset for f in fields]
+    assert re.search(r"SVT_HIP_ERR_BAD_ARG\s*=\s*%d\b" % BAD_ARG, _header())
+    assert hasattr(pkg.Context, "intra_ois_picture") and hasattr(pkg.Context, "intra_predict_batch")
 
 
 def test_null_context_and_bad_arguments_are_refused(pkg):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ptr
+from conftest import load_package, ptr
 
 
 def _pair(rng, it):
@@ -922,10 +922,8 @@ def test_wiener_tap_refinement_walk(ref, bd, fmt, ss):
     import test_sgr_gpu as tg
     if not os.path.exists(sc.MOCK_LIB):
         pytest.skip("oracle/_ref/mock/libsvtav1_hip.so not built (make -f oracle/Makefile.enc)")
-    M = C.CDLL(sc.MOCK_LIB)
-    sig = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    M.svt_hip_wiener_walk_units_dev.argtypes = sig
-    ref.ref_shim_wiener_finer_search_plane.argtypes = sig[1:]
+    M = sc.load(sc.MOCK_LIB)
+    ref.ref_shim_wiener_finer_search_plane.argtypes = load_package().PROTOTYPES["svt_hip_wiener_walk_units_dev"][1][1:]   # the same walk without the context
     EXT = tg.EXT
     for (w, h, US, win) in ((200, 152, 64, 7), (328, 264, 128, 7), (200, 152, 64, 5), (136, 72, 64, 3)):
         if ss and win == 7: win = 5     # chroma planes search the 5-tap window at most (search_wiener_seg :1352-1358)

@@ -216,9 +216,7 @@ def test_wiener_walk_units(hip, bd, fmt, ss):
     import shard_common as sc
     if not os.path.exists(sc.MOCK_LIB):
         pytest.skip("oracle/_ref/mock/libsvtav1_hip.so not built")
-    M = C.CDLL(sc.MOCK_LIB)
-    sig = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    M.svt_hip_wiener_walk_units_dev.argtypes = sig
+    M = sc.load(sc.MOCK_LIB)
     fc.two_witnesses(_wiener_walk_units, fmt, bd, hip, M, ss)
 
 
@@ -264,9 +262,7 @@ def test_wiener_walk_unit_beyond_the_resident_window(hip):
     import shard_common as sc
     if not os.path.exists(sc.MOCK_LIB):
         pytest.skip("oracle/_ref/mock/libsvtav1_hip.so not built")
-    M = C.CDLL(sc.MOCK_LIB)
-    M.svt_hip_wiener_walk_units_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    M = sc.load(sc.MOCK_LIB)
     _wiener_walk_units(hip, M, 0, 8, np.uint8, False, cases=((380, 380, 256, 7),))
 
 
@@ -522,7 +518,6 @@ def _search_units_plane_dev_chain(hip, orc, bd, dt, wide):
     e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
     orc.orc_sgr_search_units_plane(C.c_void_p(ext.ctypes.data + off), ext.itemsize, st, ptr(src), w, w, h, ss, ss, US, bd, mask, ptr(e_xqd), ptr(e_err), ptr(e_best))
     L = hip.L
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     nbytes = L.svt_hip_sgr_search_units_scratch_bytes(w, h, US)
     assert nbytes > 33 * 2 * w * h
     d_ext, d_src = hip.to_device(ext), hip.to_device(src)
@@ -563,7 +558,6 @@ def test_search_units_histogram_evaluation_and_its_fallback(hip, orc, bd, window
     e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
     orc.orc_sgr_search_units_plane(C.c_void_p(ext.ctypes.data + off), ext.itemsize, st, ptr(src), w, w, h, ss, ss, US, bd, mask, ptr(e_xqd), ptr(e_err), ptr(e_best))
     L = hip.L
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     nbytes = L.svt_hip_sgr_search_units_scratch_bytes(w, h, US)
     d_ext, d_src = hip.to_device(ext), hip.to_device(src)
     d_scr = hip.empty(nbytes); d_xqd = hip.empty(nu * 16 * 8); d_err = hip.empty(nu * 16 * 8); d_best = hip.empty(nu); d_bx = hip.empty(nu * 8)
@@ -609,7 +603,6 @@ def _packed_words_case(hip, orc, lim, ss, dt, w, h, US):
     e_xqd = np.zeros((nu, 16, 2), np.int32); e_err = np.zeros((nu, 16), np.int64); e_best = np.zeros(nu, np.uint8)
     orc.orc_sgr_search_units_plane(C.c_void_p(ext.ctypes.data + off), ext.itemsize, st, ptr(src), w, w, h, ss, ss, US, bd, mask, ptr(e_xqd), ptr(e_err), ptr(e_best))
     L = hip.L
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     os.environ["SVT_HIP_SGR_PACKED"] = "1"   # the size with the experiment's escape lists
     try: nbytes = L.svt_hip_sgr_search_units_scratch_bytes(w, h, US)
     finally: os.environ.pop("SVT_HIP_SGR_PACKED", None)
@@ -646,7 +639,6 @@ def _search_units_picture_dev(hip, pkg, orc, bd, dt, wide):
     planes = [(328, 264, 128, 0, 0xFFFF), (168, 136, 64, 1, 0x0F3C), (200, 96, 64, 1, 0x8001)]
     gots, exps = [], []
     L = hip.L
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     jobs = (pkg.SgrUnitsPlaneDev * 3)()
     keep, expect = [], []
     for i, (w, h, US, ss, mask) in enumerate(planes):
@@ -680,7 +672,6 @@ def test_search_units_several_pictures_one_call(hip, pkg, orc, n_pics):
     shapes = [(328, 264, 128, 0, 0xFFFF), (168, 136, 64, 1, 0x0F3C), (200, 96, 64, 1, 0x8001), (264, 200, 64, 0, 0x4421), (136, 104, 64, 1, 0xFFFF), (136, 104, 64, 1, 0x03C0)]
     planes = [shapes[(3 * q + p) % len(shapes)] for q in range(n_pics) for p in range(3)]
     L = hip.L
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     jobs = (pkg.SgrUnitsPlaneDev * len(planes))()
     keep, expect = [], []
     for i, (w, h, US, ss, mask) in enumerate(planes):

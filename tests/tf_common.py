@@ -6,17 +6,11 @@ import ctypes as C
 import numpy as np
 
 
-class TfBlk64(C.Structure):
-    _fields_ = [("mv16_x", C.c_int16 * 16), ("mv16_y", C.c_int16 * 16), ("err16", C.c_uint64 * 16),
-                ("mv32_x", C.c_int16 * 4), ("mv32_y", C.c_int16 * 4), ("err32", C.c_uint64 * 4), ("split", C.c_int32 * 4)]
+from conftest import load_package
 
-
-class TfRef(C.Structure):
-    _fields_ = [("pred", C.c_void_p * 3), ("pred_stride", C.c_int * 3), ("blocks", C.c_void_p)]
-
-
-BLK_DTYPE = np.dtype([("mv16_x", np.int16, 16), ("mv16_y", np.int16, 16), ("err16", np.uint64, 16),
-                      ("mv32_x", np.int16, 4), ("mv32_y", np.int16, 4), ("err32", np.uint64, 4), ("split", np.int32, 4)], align=True)
+_pkg = load_package()
+TfBlk64, TfRef = _pkg.TfBlk64, _pkg.TfRef
+BLK_DTYPE = np.dtype(TfBlk64)
 assert BLK_DTYPE.itemsize == C.sizeof(TfBlk64) == 256
 
 
@@ -65,8 +59,7 @@ def make_pictures(rng, w, h, bd, ss_x, ss_y, n_refs, noise=6.0, dtype=None, wide
 
 
 # SvtHipTfSubpelBlk (include/svt_hip.h): one (64x64 block, frame) pair of the TF sub-pel stage
-SUBPEL_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("dst_x", np.int32), ("dst_y", np.int32), ("blk_index", np.int32),
-                         ("mv32", np.uint32, 4), ("mv16", np.uint32, 16)], align=True)
+SUBPEL_DTYPE = np.dtype(_pkg.TfSubpelBlk)
 assert SUBPEL_DTYPE.itemsize == 100
 
 

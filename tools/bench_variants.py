@@ -295,7 +295,6 @@ def hbd(reps):
         b_cdef[i][EXT:EXT + p.shape[0], EXT:EXT + p.shape[1]] = d_dbl[i]
     org = lambda b, i: b[i].data_ptr() + (EXT * xs[i] + EXT) * 2
     n_units = [max((p.shape[1] + US[i] // 2) // US[i], 1) * max((p.shape[0] + US[i] // 2) // US[i], 1) for i, p in enumerate(planes_rec)]
-    L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
     scr = [L.svt_hip_sgr_search_units_scratch_bytes(p.shape[1], p.shape[0], US[i]) for i, p in enumerate(planes_rec)]
     d_scr = [torch.zeros(n, dtype=torch.uint8, device=E.dev) for n in scr]
     d_uxqd = [torch.zeros((n, 16, 2), dtype=torch.int32, device=E.dev) for n in n_units]; d_uerr = [torch.zeros((n, 16), dtype=torch.int64, device=E.dev) for n in n_units]

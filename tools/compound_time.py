@@ -9,7 +9,6 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 from conftest import load_package  # noqa: E402
 import comp_common as cmc  # noqa: E402
-from test_compound_gpu import ObmcBlk  # noqa: E402
 
 pkg = load_package()
 hip = pkg.Context(0)
@@ -46,9 +45,9 @@ for bd in (8, 10):
     hip.free(d_r0, d_r1, d_dst, d_m, d_b)
 pre = rng.integers(0, 256, (H + 8, W + 8)).astype(np.uint8)
 n = (W // 16) * (H // 16)
-ob = (ObmcBlk * n)()
+ob = (pkg.ObmcBlk * n)()
 for i in range(n):
-    ob[i] = ObmcBlk((i % (W // 16)) * 16, (i // (W // 16)) * 16, 16, 16, int(rng.integers(0, 8)), int(rng.integers(0, 8)), i * 256)
+    ob[i] = pkg.ObmcBlk((i % (W // 16)) * 16, (i // (W // 16)) * 16, 16, 16, int(rng.integers(0, 8)), int(rng.integers(0, 8)), i * 256)
 wsrc = rng.integers(0, 255 * 4096, n * 256).astype(np.int32); mask = rng.integers(0, 4097, n * 256).astype(np.int32)
 d_pre, d_w, d_mk, d_ob, d_o = hip.to_device(pre), hip.to_device(wsrc), hip.to_device(mask), hip.to_device(np.frombuffer(bytes(ob), np.uint8).copy()), hip.empty(n * 12)
 call = lambda: hip.check(hip.L.svt_hip_obmc_cost_batch_dev(hip.h, d_pre, pre.shape[1], d_w, d_mk, d_ob, n, d_o), "obmc")

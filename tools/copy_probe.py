@@ -4,7 +4,6 @@ ROOT="/root/repo" if os.path.isdir("/root/repo/svt-av1_amd") else os.getcwd()
 spec=importlib.util.spec_from_file_location("pkg", os.path.join(ROOT,"svt-av1_amd","__init__.py")); pkg=importlib.util.module_from_spec(spec); spec.loader.exec_module(pkg)
 ctx=pkg.Context(0); L=ctx.L; h=ctx.h
 W,H,ST=3840,2160,3840+2*160+64
-L.svt_hip_malloc.argtypes=[C.c_void_p,C.POINTER(C.c_void_p),C.c_size_t]
 d=C.c_void_p(); assert L.svt_hip_malloc(h,C.byref(d),ST*H)==0
 def t(fn,n=10):
     fn(); L.svt_hip_sync(h)

@@ -9,7 +9,6 @@ spec = importlib.util.spec_from_file_location("pkg", os.path.join(ROOT, "svt-av1
 ctx = pkg.Context(0); L = ctx.L; h = ctx.h
 W, H, ST = 3840, 2160, 3840 + 2 * 160 + 64
 ROWS = H + 320
-L.svt_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
 d = C.c_void_p(); assert L.svt_hip_malloc(h, C.byref(d), ST * H) == 0
 libc = C.CDLL("libc.so.6"); libc.posix_memalign.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t]; libc.madvise.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
 

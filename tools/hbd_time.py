@@ -154,7 +154,6 @@ dt = (time.perf_counter() - t0) / 3
 print(f"sgr_units_search {W}x{H} bd{bd}: {dt * 1e3:.2f} ms wall per frame (host-output form incl. the result copies; best sets used {sorted(set(int(v) for v in h_best[0]))})")
 
 # the device-output form: two launches per plane, nothing crosses PCIe -- HIP-event time of the whole search
-L.svt_hip_sgr_search_units_scratch_bytes.restype = C.c_size_t
 scr = [L.svt_hip_sgr_search_units_scratch_bytes(rec[p].shape[1], rec[p].shape[0], US[p]) for p in range(3)]
 d_scr = [hip.empty(n) for n in scr]
 d_uxqd = [hip.empty(n * 16 * 8) for n in units]; d_uerr = [hip.empty(n * 16 * 8) for n in units]; d_ubest = [hip.empty(n) for n in units]; d_ubx = [hip.empty(n * 8) for n in units]
