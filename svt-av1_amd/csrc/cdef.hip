@@ -81,21 +81,33 @@ __device__ __forceinline__ int row_sum16(int v) {   // row16_sum in the builtin'
     v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_MIRROR, 0xF, 0xF, false);
     return v;
 }
-__device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out) {
+// A lane's pixel lists and weights of the two passes depend on the lane alone: a kernel that finds the direction of many blocks loads them once
+// (the compiler does not move the loads out of a block loop by itself).
+struct DirBins { uint2 pix[2]; int weight[2]; };
+__device__ __forceinline__ DirBins load_dir_bins(int lane) {
+    DirBins B;
+#pragma unroll
+    for (int pass = 0; pass < 2; pass++) {
+        const int d = 4 * pass + (lane >> 4), b = lane & 15;
+        B.pix[pass] = *(const uint2*)kDirBinPix[d][b];
+        B.weight[pass] = kDirBinWeight[d][b];
+    }
+    return B;
+}
+__device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out, const DirBins& B) {
     xs[lane] = x_px - 128;
     __builtin_amdgcn_wave_barrier();
     int costs[8];
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
-        const int d = 4 * pass + (lane >> 4), b = lane & 15;
-        const uint2 pix = *(const uint2*)kDirBinPix[d][b];
+        const uint2 pix = B.pix[pass];
         int s = 0;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const uint32_t idx = ((k < 4 ? pix.x : pix.y) >> (8 * (k & 3))) & 0xFFu;
             s += idx < 64 ? xs[idx] : 0;
         }
-        const int c = row_sum16(s * s * kDirBinWeight[d][b]);
+        const int c = row_sum16(s * s * B.weight[pass]);
 #pragma unroll
         for (int q = 0; q < 4; q++) costs[4 * pass + q] = __builtin_amdgcn_readlane(c, 16 * q);
     }
@@ -110,6 +122,7 @@ __device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& v
     var_out = (best_cost - orth) >> 10;
     return best;
 }
+__device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out) { return find_dir_wave(x_px, lane, xs, var_out, load_dir_bins(lane)); }
 
 // ---- packed 16-bit search arithmetic ------------------------------------------------------------
 // Everything the 64 strength pairs need for one pixel: primary sums for pri = 1..15, secondary sums
@@ -150,6 +163,12 @@ __device__ __forceinline__ int constrain_pair(const TapPair& p, s16x2 sw, int t,
     const u16x2 v = __builtin_elementwise_min(p.a, hi);
     return __builtin_amdgcn_sdot2(as_s(v), sw, acc, false);
 }
+// the same with |d| >> shift supplied by the caller
+__device__ __forceinline__ int constrain_shifted(u16x2 a, u16x2 a_shifted, s16x2 sw, int t, int acc) {
+    const u16x2 hi = __builtin_elementwise_sub_sat(as_u(dup2(t)), a_shifted);
+    const u16x2 v = __builtin_elementwise_min(a, hi);
+    return __builtin_amdgcn_sdot2(as_s(v), sw, acc, false);
+}
 __device__ __forceinline__ void minmax_pair(int t0, int t1, s16x2& mn, s16x2& mx) {
     const s16x2 v = pack2(t0, t1);
     mn = __builtin_elementwise_min(mn, v);
@@ -163,71 +182,143 @@ struct PixelTerms {
     s16x2 mnA, mxA, mnB, mxB; // duplicated in both halves
 };
 
+// kDirDy / kDirDx of distance K for the 8 directions as packed signed nibbles: a per-lane direction (chroma) costs two v_bfe_i32 and a multiply-add per
+// tap offset instead of two vector loads from the constant tables; a wave-uniform one (luma) stays on the scalar ALU.
+constexpr uint32_t dir_nibbles(int d0, int d1, int d2, int d3, int d4, int d5, int d6, int d7) {
+    return (uint32_t)(d0 & 15) | (uint32_t)(d1 & 15) << 4 | (uint32_t)(d2 & 15) << 8 | (uint32_t)(d3 & 15) << 12 | (uint32_t)(d4 & 15) << 16 |
+           (uint32_t)(d5 & 15) << 20 | (uint32_t)(d6 & 15) << 24 | (uint32_t)(d7 & 15) << 28;
+}
+template <int K>
+__device__ __forceinline__ int dir_offset(int dir, int tstride) {
+    constexpr uint32_t dy8 = K ? dir_nibbles(-2, -1, 0, 1, 2, 2, 2, 2) : dir_nibbles(-1, 0, 0, 0, 1, 1, 1, 1);   // kDirDy[.][K]
+    constexpr uint32_t dx8 = K ? dir_nibbles(2, 2, 2, 2, 2, 1, 0, -1) : dir_nibbles(1, 1, 1, 1, 1, 0, 0, 0);     // kDirDx[.][K]
+    return __builtin_amdgcn_sbfe((int)dy8, 4u * (uint32_t)dir, 4u) * tstride + __builtin_amdgcn_sbfe((int)dx8, 4u * (uint32_t)dir, 4u);
+}
+
+// The A part of a pixel's terms -- everything that filters along the block's direction.
 // tile points at the pixel; tstride in elements.  t_of[idx] = effective primary strength of index idx
-// (luma: adjusted by the block variance), cs = coeff_shift, damping already includes "+ cs - (pli != 0)".
-__device__ __forceinline__ void pixel_terms(const uint16_t* px, int tstride, int dir, const int (&t_of)[16], int cs, int damping,
-                                            PixelTerms& T) {
+// (luma: adjusted by the block variance; PLAIN_T, chroma: idx << cs, not read), cs = coeff_shift, damping already includes "+ cs - (pli != 0)".
+template <bool PLAIN_T>
+__device__ __forceinline__ void pixel_terms_a(const uint16_t* px, int tstride, int dir, const int (&t_of)[16], int cs, int damping,
+                                              PixelTerms& T) {
     const int x = (int)(int16_t)px[0];
     const s16x2 x2 = dup2(x);
     T.x2 = x2;
-    TapPair pp[2], sa[2][2], sb[2][2];
-    s16x2 mnA = x2, mxA = x2, mnB = x2, mxB = x2;
+    TapPair pp[2], sa[2][2];
+    s16x2 mnA = x2, mxA = x2;
+    const int d2 = (dir + 2) & 7, d6 = (dir + 6) & 7;
+    const int o[2] = {dir_offset<0>(dir, tstride), dir_offset<1>(dir, tstride)};
+    const int o2[2] = {dir_offset<0>(d2, tstride), dir_offset<1>(d2, tstride)}, o6[2] = {dir_offset<0>(d6, tstride), dir_offset<1>(d6, tstride)};
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-        const int o = kDirDy[dir][k] * tstride + kDirDx[dir][k];
-        const int d2 = (dir + 2) & 7, d6 = (dir + 6) & 7;
-        const int o2 = kDirDy[d2][k] * tstride + kDirDx[d2][k], o6 = kDirDy[d6][k] * tstride + kDirDx[d6][k];
-        const int p0 = px[o], p1 = px[-o], a0 = px[o2], a1 = px[-o2], a2 = px[o6], a3 = px[-o6];
+        const int p0 = px[o[k]], p1 = px[-o[k]], a0 = px[o2[k]], a1 = px[-o2[k]], a2 = px[o6[k]], a3 = px[-o6[k]];
         pp[k] = make_pair(p0, p1, x2); sa[k][0] = make_pair(a0, a1, x2); sa[k][1] = make_pair(a2, a3, x2);
         minmax_pair(p0, p1, mnA, mxA); minmax_pair(a0, a1, mnA, mxA); minmax_pair(a2, a3, mnA, mxA);
-        // direction 0 variant (pri == 0 -> filter_block is called with dir 0, EbCdef.c:371): its primary taps only feed min/max
-        const int ob = kDirDy[0][k] * tstride + kDirDx[0][k];
-        const int ob2 = kDirDy[2][k] * tstride + kDirDx[2][k], ob6 = kDirDy[6][k] * tstride + kDirDx[6][k];
-        const int q0 = px[ob], q1 = px[-ob], b0 = px[ob2], b1 = px[-ob2], b2 = px[ob6], b3 = px[-ob6];
-        sb[k][0] = make_pair(b0, b1, x2); sb[k][1] = make_pair(b2, b3, x2);
-        minmax_pair(q0, q1, mnB, mxB); minmax_pair(b0, b1, mnB, mxB); minmax_pair(b2, b3, mnB, mxB);
     }
     // fold the two halves of the running min / max and duplicate
     T.mnA = __builtin_elementwise_min(mnA, mnA.yx); T.mxA = __builtin_elementwise_max(mxA, mxA.yx);
-    T.mnB = __builtin_elementwise_min(mnB, mnB.yx); T.mxB = __builtin_elementwise_max(mxB, mxB.yx);
     // primary: eb_cdef_pri_taps (EbCdef.c:198) = {4, 2} or {3, 3} by the parity of (t >> cs)
     const s16x2 w40 = signed_weight(pp[0], 4), w30 = signed_weight(pp[0], 3), w21 = signed_weight(pp[1], 2), w31 = signed_weight(pp[1], 3);
     T.pri2[0] = dup2(0);
+    if (PLAIN_T) {
+        // chroma: t = idx << cs, so |d| >> shift depends on the index only through msb(idx) -- four classes for indices 1..15: one shifted pair per class
+        // instead of one per strength -- and the tap weights through its parity
+        u16x2 sh0 = pp[0].a, sh1 = pp[1].a;
 #pragma unroll
-    for (int idx = 1; idx < 16; idx++) {
-        const int t = t_of[idx];   // wave-uniform
-        // luma: adjust_strength() maps the 16 frame-header strengths onto fewer effective ones in a low-variance block (it is monotone, so equal values are
-        // neighbours): the sum of a repeated value is the previous index's
-        if (t == t_of[idx - 1]) { T.pri2[idx] = T.pri2[idx - 1]; continue; }
-        int s = 0;
-        if (t) {
-            const int shift = max(0, damping - msb(t));
-            const bool odd = (t >> cs) & 1;
-            s = constrain_pair(pp[0], odd ? w30 : w40, t, shift, 0);
-            s = constrain_pair(pp[1], odd ? w31 : w21, t, shift, s);
+        for (int idx = 1; idx < 16; idx++) {
+            if ((idx & (idx - 1)) == 0) {   // first index of a class
+                const int shift = max(0, damping - cs - (31 - __builtin_clz(idx)));   // = damping - msb(idx << cs)
+                sh0 = pp[0].a >> (unsigned short)shift; sh1 = pp[1].a >> (unsigned short)shift;
+            }
+            int s = constrain_shifted(pp[0].a, sh0, (idx & 1) ? w30 : w40, idx << cs, 0);
+            s = constrain_shifted(pp[1].a, sh1, (idx & 1) ? w31 : w21, idx << cs, s);
+            T.pri2[idx] = dup2(s);
         }
-        T.pri2[idx] = dup2(s);
+    } else {
+#pragma unroll
+        for (int idx = 1; idx < 16; idx++) {
+            const int t = t_of[idx];   // wave-uniform
+            // luma: adjust_strength() maps the 16 frame-header strengths onto fewer effective ones in a low-variance block (it is monotone, so equal values are
+            // neighbours): the sum of a repeated value is the previous index's
+            if (t == t_of[idx - 1]) { T.pri2[idx] = T.pri2[idx - 1]; continue; }
+            int s = 0;
+            if (t) {
+                const int shift = max(0, damping - msb(t));
+                const bool odd = (t >> cs) & 1;
+                s = constrain_pair(pp[0], odd ? w30 : w40, t, shift, 0);
+                s = constrain_pair(pp[1], odd ? w31 : w21, t, shift, s);
+            }
+            T.pri2[idx] = dup2(s);
+        }
     }
     // secondary: eb_cdef_sec_taps {2, 1}; strengths 1, 2, 4 (index 3 means 4: "sec += sec == 3")
-    s16x2 wa[2][2], wb[2][2];
+    s16x2 wa[2][2];
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-        for (int h = 0; h < 2; h++) { wa[k][h] = signed_weight(sa[k][h], 2 - k); wb[k][h] = signed_weight(sb[k][h], 2 - k); }
-    int a[3], b[3];
+        for (int h = 0; h < 2; h++) wa[k][h] = signed_weight(sa[k][h], 2 - k);
+    int a[3];
 #pragma unroll
     for (int si = 0; si < 3; si++) {
         const int st = (1 << si) << cs;
         const int shift = max(0, damping - msb(st));
-        int va = 0, vb = 0;
+        int va = 0;
 #pragma unroll
         for (int k = 0; k < 2; k++)
 #pragma unroll
-            for (int h = 0; h < 2; h++) { va = constrain_pair(sa[k][h], wa[k][h], st, shift, va); vb = constrain_pair(sb[k][h], wb[k][h], st, shift, vb); }
-        a[si] = va; b[si] = vb;
+            for (int h = 0; h < 2; h++) va = constrain_pair(sa[k][h], wa[k][h], st, shift, va);
+        a[si] = va;
     }
     T.secA[0] = pack2(0, a[0]); T.secA[1] = pack2(a[1], a[2]);
+}
+
+// The B part: the direction-0 variant that serves primary index 0 (pri == 0 -> filter_block is called with dir 0, EbCdef.c:371): its primary taps only
+// feed min/max.  sums = false (wave-uniform) computes the min/max alone -- for a block of direction 4, whose secondary taps (directions 6 and 2) are B's
+// (2 and 6) with the same weights, so that secB = secA.  A block of direction 0 needs no B part at all: B is A, term for term (pixel_terms_b_is_a).
+__device__ __forceinline__ void pixel_terms_b(const uint16_t* px, int tstride, int cs, int damping, bool sums, PixelTerms& T) {
+    const s16x2 x2 = T.x2;
+    int bt[2][4];
+    s16x2 mnB = x2, mxB = x2;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int ob = (k + 1) * (1 - tstride), ob2 = k + 1, ob6 = (k + 1) * tstride;   // directions 0, 2, 6 of kDirDy / kDirDx at distance k
+        const int q0 = px[ob], q1 = px[-ob];
+        bt[k][0] = px[ob2]; bt[k][1] = px[-ob2]; bt[k][2] = px[ob6]; bt[k][3] = px[-ob6];
+        minmax_pair(q0, q1, mnB, mxB); minmax_pair(bt[k][0], bt[k][1], mnB, mxB); minmax_pair(bt[k][2], bt[k][3], mnB, mxB);
+    }
+    T.mnB = __builtin_elementwise_min(mnB, mnB.yx); T.mxB = __builtin_elementwise_max(mxB, mxB.yx);
+    T.secB[0] = T.secA[0]; T.secB[1] = T.secA[1];
+    if (!sums) return;
+    TapPair sb[2][2];
+    s16x2 wb[2][2];
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) { sb[k][h] = make_pair(bt[k][2 * h], bt[k][2 * h + 1], x2); wb[k][h] = signed_weight(sb[k][h], 2 - k); }
+    int b[3];
+#pragma unroll
+    for (int si = 0; si < 3; si++) {
+        const int st = (1 << si) << cs;
+        const int shift = max(0, damping - msb(st));
+        int vb = 0;
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) vb = constrain_pair(sb[k][h], wb[k][h], st, shift, vb);
+        b[si] = vb;
+    }
     T.secB[0] = pack2(0, b[0]); T.secB[1] = pack2(b[1], b[2]);
+}
+__device__ __forceinline__ void pixel_terms_b_is_a(PixelTerms& T) {
+    T.secB[0] = T.secA[0]; T.secB[1] = T.secA[1]; T.mnB = T.mnA; T.mxB = T.mxA;
+}
+// uniform_dir: the direction every live pixel of the wave has, or -1 when they differ (then, and for every direction but 0 and 4, the whole B part runs)
+template <bool PLAIN_T>
+__device__ __forceinline__ void pixel_terms(const uint16_t* px, int tstride, int dir, int uniform_dir, const int (&t_of)[16], int cs, int damping,
+                                            PixelTerms& T) {
+    pixel_terms_a<PLAIN_T>(px, tstride, dir, t_of, cs, damping, T);
+    if (uniform_dir == 0) pixel_terms_b_is_a(T);
+    else pixel_terms_b(px, tstride, cs, damping, uniform_dir != 4, T);
 }
 
 // filtered values of strengths (pri_idx, 2 * pair) and (pri_idx, 2 * pair + 1): y = x + ((8 + sum - (sum < 0)) >> 4), clamped
@@ -344,6 +435,7 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
     const int damping = pri_damping + cs;  // pli == 0 (EbCdef.c:306-307)
     unsigned long long acc = 0;            // lane g: sum over this wave's blocks of dist(block, strength g)
     const int i = lane >> 3, j = lane & 7;
+    const DirBins bins = load_dir_bins(lane);
     for (int b = wave; b < 64; b += 4) {
         const int by = b >> 3, bx = b & 7;
         if (by >= nby || bx >= nbx || skip8[(8 * fbr + by) * c8 + 8 * fbc + bx]) {
@@ -352,13 +444,13 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
         }
         const uint16_t* px = tile + (8 * by + i + kVB) * TS + 8 * bx + j + kHB;
         int var;
-        const int dir = find_dir_wave(((int)px[0] >> cs), lane, part[wave], var);
+        const int dir = find_dir_wave(((int)px[0] >> cs), lane, part[wave], var, bins);
         if (lane == 0 && dir_out) { dir_out[fb * 64 + b] = (uint8_t)dir; var_out[fb * 64 + b] = var; }
         int t_of[16];
 #pragma unroll
         for (int idx = 0; idx < 16; idx++) t_of[idx] = adjust_strength(idx << cs, var);
         PixelTerms T;
-        pixel_terms(px, TS, dir, t_of, cs, damping, T);
+        pixel_terms<false>(px, TS, dir, dir, t_of, cs, damping, T);   // dir is wave-uniform here
         // Primary indices whose effective strength equals the previous index's filter identically (same sums, same direction, same clamps): only the first index of
         // such a run is combined and stored; rep4 = 16 x 4 bits, the first index of every index's run (wave-uniform).  A block of low directional variance has 5 .. 9
         // distinct effective strengths out of 16 (adjust_strength, EbCdef.c:112-116).
@@ -433,14 +525,16 @@ cdef_search_chroma_kernel(const PIX* __restrict__ rec_u, const PIX* __restrict__
         const PIX* sp = pl ? src_v : src_u;
         const int sy = min(32 * fbr + 4 * by + i, (h >> 1) - 1), sx = min(32 * fbc + 4 * bx + j, (w >> 1) - 1);
         const PIX s = sp[(size_t)sy * src_stride + sx];
+        // the direction differs per 4x4 block: the direction-0 / -4 shortcuts of pixel_terms are taken only when every live block of the pass has that direction
+        const int dir = live ? dir_in[fb * 64 + by * 8 + bx] : -1;
+        const int uniform_dir = __all(!live || dir == 0) ? 0 : __all(!live || dir == 4) ? 4 : -1;
         if (live) {
             const uint16_t* px = tile[pl] + (4 * by + i + kVB) * TS + 4 * bx + j + kHB;
-            const int dir = dir_in[fb * 64 + by * 8 + bx];
             int t_of[16];
 #pragma unroll
             for (int idx = 0; idx < 16; idx++) t_of[idx] = idx << cs;
             PixelTerms T;
-            pixel_terms(px, TS, dir, t_of, cs, damping, T);
+            pixel_terms<true>(px, TS, dir, uniform_dir, t_of, cs, damping, T);
 #pragma unroll
             for (int g = 0; g < 64; g += 2) {
                 const s16x2 y = combine2(T, g >> 2, (g >> 1) & 1);

@@ -17,9 +17,12 @@
 //  * A lane owns a "unit" = 8 adjacent candidates (two qsad quads) on one candidate row and walks
 //    all 64 8x8 blocks of the SB for them; 8x8 SADs live packed u16x4 in registers, 16x16 are packed
 //    adds, 32x32/64x64 are unpacked u32 sums.
-//  * Every PU keeps a running (sad<<16 | raster_candidate_index) key per lane, updated with
-//    v_min3_u32; the reference's "strict <, raster order" tie-break is exactly the minimum of that
-//    key.  32x32/64x64 SADs need 20 bits, so those 5 PUs use 64-bit keys.
+//  * Every 8x8 / 16x16 PU keeps a running (unit's minimum sad << 16 | raster index of the unit's first
+//    candidate) key per lane (packed v_pk_min_u16, one v_min_u32); the minimum of that key is the first
+//    unit in raster order that attains the minimum, and a locate step after the workgroup reduction
+//    recomputes that one unit's 8 SADs and takes the first position equal to the minimum -- together
+//    the reference's "strict <, raster order" tie-break.  32x32/64x64 SADs need 20 bits, so those 5 PUs
+//    use 64-bit per-candidate keys.
 //  * The source SB (4 KB) and the reference window ((64+63) rows) are staged in LDS once per
 //    64x64-candidate tile with the byte misalignment removed at staging time (v_alignbyte).
 #include <hip/hip_runtime.h>
@@ -48,23 +51,20 @@ constexpr int kRefStrideDw = 48;       // LDS row stride in dwords (192 B): rows
 __host__ __device__ constexpr int z16_index(int X, int Y) { return (((Y >> 1) * 2 + (X >> 1)) << 2) | ((Y & 1) << 1) | (X & 1); }
 __host__ __device__ constexpr int pu8_index(int bx, int by) { return 21 + z16_index(bx >> 1, by >> 1) * 4 + ((by & 1) << 1) + (bx & 1); }
 
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
+
 // Fold the 8 candidates of a unit (packed u16 SADs a = cands 0..3, b = cands 4..7) into a key.
-// key = sad << 16 | candidate raster index.
+// key = unit's minimum sad << 16 | raster index of the unit's FIRST candidate (idx0, a multiple of 8): the minimum is taken packed
+// (three v_pk_min_u16 and one against the swapped halves), so a PU's reduced key names (minimum SAD, first unit in raster order that attains
+// it) and the kernel's locate step (unit_sad_8x8 below) finds the first position inside that one unit -- 6 operations per (PU, unit) instead of
+// the 12 of eight per-candidate keys.
 __device__ __forceinline__ uint32_t fold_key16(uint32_t key, uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi,
                                                uint32_t idx0) {
-    uint32_t k0 = (a_lo << 16) | idx0;
-    uint32_t k1 = (a_lo & 0xFFFF0000u) | (idx0 + 1);
-    uint32_t k2 = (a_hi << 16) | (idx0 + 2);
-    uint32_t k3 = (a_hi & 0xFFFF0000u) | (idx0 + 3);
-    uint32_t k4 = (b_lo << 16) | (idx0 + 4);
-    uint32_t k5 = (b_lo & 0xFFFF0000u) | (idx0 + 5);
-    uint32_t k6 = (b_hi << 16) | (idx0 + 6);
-    uint32_t k7 = (b_hi & 0xFFFF0000u) | (idx0 + 7);
-    key = min(min(key, k0), k1);
-    key = min(min(key, k2), k3);
-    key = min(min(key, k4), k5);
-    key = min(min(key, k6), k7);
-    return key;
+    u16x2 m = __builtin_elementwise_min(__builtin_elementwise_min(as_u16x2(a_lo), as_u16x2(a_hi)),
+                                        __builtin_elementwise_min(as_u16x2(b_lo), as_u16x2(b_hi)));
+    m = __builtin_elementwise_min(m, m.yx);
+    return min(key, ((uint32_t)m.x << 16) | idx0);
 }
 
 // The folds below only feed the next unit / the final reduction, so LLVM's machine-sink pass moves
@@ -194,6 +194,39 @@ __device__ __forceinline__ void search_unit(const_u32_ptr src_dw, int src_pitch_
     }
 }
 
+// The locate step's SADs: the 8x8 source block at src_blk against the 8 candidates of one unit (ref_blk = the block's position at the unit's
+// first candidate), packed u16 x 8 in out[0..3] exactly like search_unit's p[bx][0..3] (same instruction, same operand pairing, SUB mirrored),
+// so the values are the ones the fold saw.  Rows come from global memory (L2-hot after the search) as aligned dwords with the misalignment
+// shifted out; a dword is fetched only if it holds a needed byte (source: 8, reference: 15 per row), i.e. nothing outside the aligned
+// footprint that the staging of this window read.
+template <bool SUB>
+__device__ __forceinline__ void unit_sad_8x8(const uint8_t* src_blk, const uint8_t* ref_blk, int stride, uint32_t (&out)[4]) {
+    const uint32_t ss = 8u * (uint32_t)((uintptr_t)src_blk & 3), rs = 8u * (uint32_t)((uintptr_t)ref_blk & 3);
+    const uint32_t* sp = (const uint32_t*)((uintptr_t)src_blk & ~(uintptr_t)3);
+    const uint32_t* rp = (const uint32_t*)((uintptr_t)ref_blk & ~(uintptr_t)3);
+    const int pitch_dw = stride >> 2;
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r += (SUB ? 2 : 1)) {
+        const uint32_t* s = sp + (size_t)r * pitch_dw;
+        const uint32_t* q = rp + (size_t)r * pitch_dw;
+        const uint32_t s0 = s[0], s1 = s[1], s2 = ss ? s[2] : 0u;
+        const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = rs >= 16 ? q[4] : 0u;   // bytes 0..14 end in dword 4 only at misalignment 2, 3
+        const uint32_t S0 = (uint32_t)(pack64(s0, s1) >> ss), S1 = (uint32_t)(pack64(s1, s2) >> ss);
+        const uint32_t R0 = (uint32_t)(pack64(w0, w1) >> rs), R1 = (uint32_t)(pack64(w1, w2) >> rs);
+        const uint32_t R2 = (uint32_t)(pack64(w2, w3) >> rs), R3 = (uint32_t)(pack64(w3, w4) >> rs);
+        acc0 = __builtin_amdgcn_qsad_pk_u16_u8(pack64(R0, R1), S0, acc0);
+        acc0 = __builtin_amdgcn_qsad_pk_u16_u8(pack64(R1, R2), S1, acc0);
+        acc1 = __builtin_amdgcn_qsad_pk_u16_u8(pack64(R1, R2), S0, acc1);
+        acc1 = __builtin_amdgcn_qsad_pk_u16_u8(pack64(R2, R3), S1, acc1);
+    }
+    out[0] = (uint32_t)acc0; out[1] = (uint32_t)(acc0 >> 32); out[2] = (uint32_t)acc1; out[3] = (uint32_t)(acc1 >> 32);
+    if (SUB) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) out[k] <<= 1;
+    }
+}
+
 // BIG = false: search areas of up to 65 536 candidates (the packed keys carry a 16-bit raster index); larger ones return at once and are
 // taken by the BIG = true instance of the same code, which walks the window in strips of whole candidate rows (<= 65 536 candidates each,
 // top to bottom) and merges a strip's winners into the result with the reference's strict '<', i.e. still "first minimum in raster order"
@@ -209,7 +242,7 @@ me_fullpel_85pu_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
     __shared__ uint32_t lds_part[NT], lds_fin[88];
 
     const int sb  = svt_xcd_order(blockIdx.x, gridDim.x);   // neighbouring superblocks' search windows overlap: an XCD takes a band of superblock rows
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const SvtHipSbSearch d = sbs[sb];
     const int saw = d.width, sah_all = d.height;
     if (saw & 7) return;  // widths 1..7 (window clamped at a picture edge) go to me_fullpel_narrow_kernel
@@ -262,7 +295,9 @@ me_fullpel_85pu_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
     constexpr int PPH   = 4096 / NT;   // PUs handled per pass (16 KB of the idle window buffer)
     constexpr int PARTS = NT / PPH;    // slices per PU, PPH entries each
     uint32_t* lds_keys = lds_ref;
-    const int rp = tid % PPH, rq = tid / PPH;
+    int rtid = tid;
+    if (BIG) PIN(rtid);   // keeps the reduction's per-thread LDS addresses from being computed before the strip loop and spilled across the search
+    const int rp = rtid % PPH, rq = rtid / PPH;
 #pragma unroll
     for (int ph = 0; ph * PPH < 80; ph++) {
         const int cnt = (80 - ph * PPH) < PPH ? (80 - ph * PPH) : PPH;
@@ -270,7 +305,7 @@ me_fullpel_85pu_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
 #pragma unroll
         for (int j = 0; j < cnt; j++) {
             const int i = ph * PPH + j;   // PU number - 5
-            lds_keys[j * NT + tid] = (i < 16) ? K.k16[i] : K.k8[i - 16];
+            lds_keys[j * NT + rtid] = (i < 16) ? K.k16[i] : K.k8[i - 16];
         }
         __syncthreads();
         if (rp < cnt) {
@@ -280,11 +315,11 @@ me_fullpel_85pu_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
             lds_part[rq * PPH + rp] = m;
         }
         __syncthreads();
-        if (tid < cnt) {
-            uint32_t m = lds_part[tid];
+        if (rtid < cnt) {
+            uint32_t m = lds_part[rtid];
 #pragma unroll
-            for (int q = 1; q < PARTS; q++) m = min(m, lds_part[q * PPH + tid]);
-            lds_fin[5 + ph * PPH + tid] = m;
+            for (int q = 1; q < PARTS; q++) m = min(m, lds_part[q * PPH + rtid]);
+            lds_fin[5 + ph * PPH + rtid] = m;
         }
     }
     // The five 32x32 / 64x64 PUs carry 64-bit keys: two DPP wave reductions each.
@@ -295,13 +330,55 @@ me_fullpel_85pu_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
         const uint32_t ms = wave_min_u32(s);
         const uint32_t mi = wave_min_u32(s == ms ? ix : 0xFFFFFFFFu);
         const int pu = (i < 4) ? 1 + i : 0;
-        if (lane == 0) { lds_red[wave][0][pu] = ms; lds_red[wave][1][pu] = mi; }
+        if ((rtid & 63) == 0) { lds_red[rtid >> 6][0][pu] = ms; lds_red[rtid >> 6][1][pu] = mi; }
     }
     __syncthreads();
-    for (int pu = tid; pu < SVT_HIP_SQUARE_PU_COUNT; pu += NT) {
+    // ---- locate: a reduced 32-bit key names (minimum SAD, first unit in raster order that attains it); the reference's "first minimum in raster
+    // order" is completed inside that unit.  128 equal tasks = the 8x8 block SADs at a unit's 8 candidates: tasks 0..63 are the 8x8 PUs
+    // (PU number - 21), tasks 64..127 the four 8x8 quarters of the 16x16 PUs ((PU number - 5) * 4 + quarter, summed packed below exactly as
+    // search_unit sums them).  Per strip for BIG, before the merge with earlier strips.
+    uint32_t* lds_loc = lds_ref;   // 128 x 4 dwords of the idle window buffer (the reduction's reads of it are behind the barriers above)
+    for (int t0 = tid; t0 < 128; t0 += NT) {
+        int t = t0;
+        PIN(t);   // the block addresses depend on the thread only: unpinned they are computed before the search and held (spilled) across it
+        const int n = t & 63, z = n >> 2;
+        const uint32_t key = t < 64 ? lds_fin[21 + n] : lds_fin[5 + z];
+        uint32_t o[4] = {0, 0, 0, 0};
+        if (key != 0xFFFFFFFFu) {   // (an empty search area leaves the initial keys)
+            // PU order is z-order of the 16x16 blocks, raster inside a 16x16 (inverse of pu8_index)
+            const int X = ((z >> 2) & 1) * 2 + (z & 1), Y = (z >> 3) * 2 + ((z >> 1) & 1);
+            const int bx = 2 * X + (n & 1), by = 2 * Y + ((n >> 1) & 1);
+            const int i0 = (int)(key & 0xFFFFu), cy = i0 / saw, cx = i0 - cy * saw;
+            const uint8_t* sblk = src_base + (size_t)(8 * by) * stride + 8 * bx;
+            const uint8_t* rblk = ref + (size_t)(org_y + d.sb_y + d.y_origin + sy0 + cy + 8 * by) * stride +
+                                  (org_x + d.sb_x + d.x_origin + cx + 8 * bx);
+            unit_sad_8x8<SUB>(sblk, rblk, stride, o);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) lds_loc[4 * t + k] = o[k];
+    }
+    __syncthreads();
+    for (int pu0 = tid; pu0 < SVT_HIP_SQUARE_PU_COUNT; pu0 += NT) {
+        int pu = pu0;
+        if (BIG) PIN(pu);   // (as above: the strip loop would otherwise carry this loop's per-thread addresses across the search)
         uint32_t bs, bi;
         if (pu >= 5) {
             bs = lds_fin[pu] >> 16; bi = lds_fin[pu] & 0xFFFFu;
+            uint32_t p[4];
+            if (pu >= 21) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) p[k] = lds_loc[4 * (pu - 21) + k];
+            } else {   // packed u16 adds never carry between halves (max 256 * 255)
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    p[k] = lds_loc[4 * (64 + 4 * (pu - 5)) + k] + lds_loc[4 * (65 + 4 * (pu - 5)) + k] +
+                           lds_loc[4 * (66 + 4 * (pu - 5)) + k] + lds_loc[4 * (67 + 4 * (pu - 5)) + k];
+            }
+            uint32_t pos = 0;
+#pragma unroll
+            for (int c = 7; c >= 0; c--)
+                if (((p[c >> 1] >> (16 * (c & 1))) & 0xFFFFu) == bs) pos = (uint32_t)c;
+            bi += pos;
         } else {
             bs = lds_red[0][0][pu]; bi = lds_red[0][1][pu];
 #pragma unroll
