@@ -738,6 +738,44 @@ int svt_hip_picture_format_dev(SvtHipCtx *ctx, int mode, const void *d_in0, int 
  * reference picture, and svt_extend_frame's 3-sample border of the restoration input).  d_plane points at picture sample (0, 0). */
 int svt_hip_generate_padding_dev(SvtHipCtx *ctx, void *d_plane, int pix_bytes, int stride, int w, int h, int pad_w, int pad_h);
 
+/* ------------------------------------------------------------------ super-resolution: normative upscale and the scaler ---- */
+/* A picture coded with super-resolution is encoded at width * 8 / denom (denom 9 .. 16) and brought back to full width between CDEF and the
+ * restoration by the normative, horizontal-only 8-tap upscale (svt_av1_superres_upscale_frame, Encoder/Codec/EbRestProcess.c:397-452 ->
+ * svt_av1_upscale_normative_rows, Common/Codec/EbSuperRes.c:40-294); the same upscale makes the restoration's stripe context rows from the deblocked
+ * picture (save_deblock_boundary_lines, Common/Codec/EbRestoration.c:1645-1702: rows = 1 or 2).  On the source side the input picture and every
+ * reference are scaled to the coded size by av1_resize_plane / av1_highbd_resize_plane (Encoder/Codec/EbResize.c:186-765).
+ * Samples: pix_bytes 1 (bd 8) or 2 (bd 8 .. 12, a value).  Strides in samples, >= the plane's width.  Everything is out of place: d_src is only read.
+ *
+ * svt_hip_superres_scaled_dim = calculate_scaled_size_helper (8 <= denom <= 16, 8 returns dim; 1 <= dim <= 65535); 0 for anything else.
+ * svt_hip_superres_upscale_params: the step and the first position, in 1/16384 sample, of an in_w -> out_w upscale (1 <= in_w <= out_w <= 16384):
+ * output x is the 8 taps of phase ((x0_qn + x * x_step_qn) & 0x3fff) >> 8 over the source samples ((x0_qn + x * x_step_qn) >> 14) - 4 + k, k = 0 .. 7. */
+int svt_hip_superres_scaled_dim(int dim, int denom);
+int svt_hip_superres_upscale_params(int in_w, int out_w, int32_t *x_step_qn, int32_t *x0_qn);
+/* One plane of an upscale: `rows` rows (1 .. 16384) of in_w samples -> out_w samples each. */
+typedef struct {
+    const void *d_src;
+    int         src_stride, in_w;
+    void       *d_dst;
+    int         dst_stride, out_w;
+    int         rows;
+} SvtHipUpscalePlane;
+/* 1 .. 3 planes in one launch.  Source positions outside [0, in_w) read the nearest sample of the row (the reference writes 5 replicated columns
+ * either side of its input for the time of the call; this does not touch the source), and the result does not depend on the tile columns: no tile
+ * information is taken (docs/kernels/superres.md).  Refused: out_w < in_w, in_w < 1, out_w > 16384, d_src == d_dst, a stride below the width. */
+int svt_hip_superres_upscale_planes_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const SvtHipUpscalePlane *planes, int n_planes);
+/* One plane of the general scaler: in_w x in_h -> out_w x out_h, any sizes 1 .. 16384 per axis, enlarging included; equal sizes copy. */
+typedef struct {
+    const void *d_src;
+    int         src_stride, in_w, in_h;
+    void       *d_dst;
+    int         dst_stride, out_w, out_h;
+} SvtHipResizePlane;
+/* av1_resize_plane for 1 .. 3 planes: rows first, then columns, the plane in between clipped to samples.  d_scratch holds
+ * svt_hip_resize_scratch_bytes(pix_bytes, planes, n_planes) bytes (0 when no plane changes its height; also 0 for what the call would refuse) and
+ * may be NULL when that is 0. */
+size_t svt_hip_resize_scratch_bytes(int pix_bytes, const SvtHipResizePlane *planes, int n_planes);
+int svt_hip_resize_planes_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const SvtHipResizePlane *planes, int n_planes, void *d_scratch, size_t scratch_bytes);
+
 /* ------------------------------------------------------------------ per-call forms ------------- */
 /* Operations that the frame entry points above run fused inside larger kernels, exposed on their own for a list of units, so that every
  * pointer of the reference's dispatch table on this path has a device form (include/svt_hip_rtcd.h launches these with a list of one).

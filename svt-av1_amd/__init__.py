@@ -304,6 +304,18 @@ class GmEstimate(C.Structure):
                 ("ref_frame_error", C.c_int64), ("fits", GmFit * 2), ("models", GmModelRecord * 2)]
 
 
+class UpscalePlane(C.Structure):
+    """SvtHipUpscalePlane (include/svt_hip.h)."""
+    _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32), ("out_w", C.c_int32),
+                ("rows", C.c_int32)]
+
+
+class ResizePlane(C.Structure):
+    """SvtHipResizePlane (include/svt_hip.h)."""
+    _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("in_h", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32)]
+
+
 GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
 GM_FIT_MAX_JOBS = 64   # SVT_HIP_GM_FIT_MAX_JOBS
 GM_MAX_CORNERS = 4096   # SVT_HIP_GM_MAX_CORNERS
@@ -497,6 +509,12 @@ PROTOTYPES = {
     # ---- picture formats around the high-bit-depth path
     "svt_hip_picture_format_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]),
     "svt_hip_generate_padding_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, i32]),
+    # ---- super-resolution: normative upscale and the scaler
+    "svt_hip_superres_scaled_dim": (i32, [i32, i32]),
+    "svt_hip_superres_upscale_params": (i32, [i32, i32, P(C.c_int32), P(C.c_int32)]),
+    "svt_hip_superres_upscale_planes_dev": (i32, [vp, i32, i32, P(UpscalePlane), i32]),
+    "svt_hip_resize_scratch_bytes": (sz, [i32, P(ResizePlane), i32]),
+    "svt_hip_resize_planes_dev": (i32, [vp, i32, i32, P(ResizePlane), i32, vp, sz]),
     # ---- per-call forms
     "svt_hip_quantize_batch_dev": (i32, [vp, vp, i32, i32, P(QuantParams), vp, vp, vp, vp]),
     "svt_hip_residual_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]),
@@ -912,6 +930,55 @@ class Context:
             self.check(self.L.svt_hip_sync(self.h), "sync")
             pts, cnt, kept = self.to_host(d_p, (n, max_points, 2), np.int32), self.to_host(d_c, (n,), np.int32), self.to_host(d_k, (n,), np.int32)
             return [pts[i, :max(0, min(int(cnt[i]), max_points))].copy() for i in range(n)], cnt, kept
+        finally:
+            self.free(*held)
+
+    def _scaled_planes(self, planes, shapes, dst, held):
+        """Uploads 1 .. 3 source planes and their destinations (`dst[i]` a 2-D view to write into, or None / missing for a fresh zeroed plane of shapes[i]); views as
+        in _upload_plane.  -> [(source pointer, source stride, destination pointer, destination stride, device root, host root, destination view)]"""
+        import numpy as np
+        out = []
+        for i, (src, shape) in enumerate(zip(planes, shapes)):
+            d = dst[i] if dst is not None and dst[i] is not None else np.zeros(shape, src.dtype)
+            assert d.shape == tuple(shape) and d.dtype == src.dtype == planes[0].dtype and src.dtype in (np.uint8, np.uint16)
+            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
+            d_d, p_d, s_d, root = self._upload_plane(d); held.append(d_d)
+            out.append((p_s, s_s, p_d, s_d, d_d, root, d))
+        return out
+
+    def superres_upscale_planes(self, planes, out_widths, dst=None, bd=None):
+        """svt_hip_superres_upscale_planes_dev: 1 .. 3 2-D `planes`, all uint8 (bd 8) or all uint16 (bd 10 unless `bd` says otherwise), each upscaled to its
+        entry of `out_widths`; planes and the optional destinations `dst` may be offset / strided views.  -> the upscaled planes, each a view (like the one
+        given) of a fresh copy of the whole destination array, so what lies around the plane can be checked through `.base`."""
+        pix_bytes = planes[0].dtype.itemsize
+        held = []
+        try:
+            recs = self._scaled_planes(planes, [(p.shape[0], w) for p, w in zip(planes, out_widths)], dst, held)
+            tab = (UpscalePlane * len(recs))(*[UpscalePlane(r[0], r[1], p.shape[1], r[2], r[3], w, p.shape[0]) for r, p, w in zip(recs, planes, out_widths)])
+            self.check(self.L.svt_hip_superres_upscale_planes_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), tab, len(recs)), "superres_upscale_planes")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return [self._download_plane(r[4], r[5], r[6]) for r in recs]
+        finally:
+            self.free(*held)
+
+    def resize_planes(self, planes, out_shapes, dst=None, bd=None, scratch=None):
+        """svt_hip_resize_planes_dev: 1 .. 3 2-D `planes` (dtypes, views and `dst` as in superres_upscale_planes), each scaled to its (height, width) of
+        `out_shapes`.  `scratch`, if given, is a uint8 array of at least svt_hip_resize_scratch_bytes that is used as the call's scratch and receives what
+        the device left in it.  -> the scaled planes, as superres_upscale_planes returns them."""
+        import numpy as np
+        pix_bytes = planes[0].dtype.itemsize
+        held = []
+        try:
+            recs = self._scaled_planes(planes, out_shapes, dst, held)
+            tab = (ResizePlane * len(recs))(*[ResizePlane(r[0], r[1], p.shape[1], p.shape[0], r[2], r[3], s[1], s[0]) for r, p, s in zip(recs, planes, out_shapes)])
+            need = self.L.svt_hip_resize_scratch_bytes(pix_bytes, tab, len(recs))
+            d_x = self.to_device(scratch) if scratch is not None else self.empty(need); held.append(d_x)
+            self.check(self.L.svt_hip_resize_planes_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), tab, len(recs), d_x,
+                                                        scratch.nbytes if scratch is not None else need), "resize_planes")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            if scratch is not None:
+                scratch[...] = self.to_host(d_x, scratch.shape, np.uint8)
+            return [self._download_plane(r[4], r[5], r[6]) for r in recs]
         finally:
             self.free(*held)
 

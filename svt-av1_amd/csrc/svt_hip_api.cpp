@@ -11,6 +11,7 @@
 #include "svt_hip_internal.h"
 #include "svt_hip_host.h"
 #include "tpl_synth.h"
+#include "resize_plan.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -259,7 +260,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(pyramid) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -1512,6 +1513,50 @@ int svt_hip_generate_padding_dev(SvtHipCtx* c, void* d_plane, int pix_bytes, int
     if (w == 0 || h == 0 || (pad_w == 0 && pad_h == 0)) return SVT_HIP_OK;
     if (!d_plane || stride < w + pad_w) return bad_arg(c);
     return launched(c, svt_hip_launch_generate_padding(c->stream, d_plane, pix_bytes, stride, w, h, pad_w, pad_h), "generate padding launch");
+}
+
+/* ------------------------------------------------------------------ super-resolution (resize.hip; the host arithmetic is resize_plan.h) */
+int svt_hip_superres_scaled_dim(int dim, int denom) { return dim < 1 || dim > 65535 || denom < 8 || denom > 16 ? 0 : svt_superres_scaled_dim(dim, denom); }
+
+int svt_hip_superres_upscale_params(int in_w, int out_w, int32_t* x_step_qn, int32_t* x0_qn) {
+    if (in_w < 1 || out_w < in_w || out_w > SVT_RS_MAX_DIM || !x_step_qn || !x0_qn) return SVT_HIP_ERR_BAD_ARG;
+    *x_step_qn = svt_superres_step_qn(in_w, out_w);
+    *x0_qn = svt_superres_x0_qn(in_w, out_w, *x_step_qn);
+    return SVT_HIP_OK;
+}
+
+static bool upscale_planes_ok(const SvtHipUpscalePlane* p, int n) {
+    if (!p || n < 1 || n > 3) return false;
+    for (int i = 0; i < n; i++)
+        if (!svt_upscale_plane_ok(p[i])) return false;
+    return true;
+}
+static bool resize_planes_ok(const SvtHipResizePlane* p, int n) {
+    if (!p || n < 1 || n > 3) return false;
+    for (int i = 0; i < n; i++)
+        if (!svt_resize_plane_ok(p[i])) return false;
+    return true;
+}
+
+int svt_hip_superres_upscale_planes_dev(SvtHipCtx* c, int pix_bytes, int bd, const SvtHipUpscalePlane* planes, int n_planes) {
+    SVT_HIP_ENTER(c);
+    if (!c || !fmt_8to12_ok(pix_bytes, bd) || !upscale_planes_ok(planes, n_planes))
+        return bad_arg(c, "svt_hip_superres_upscale_planes_dev: bad argument (1 <= n_planes <= 3, 1 <= in_w <= out_w <= 16384, 1 <= rows <= 16384, stride >= width, d_src != d_dst)");
+    return launched(c, svt_hip_launch_superres_upscale(c->stream, pix_bytes, bd, planes, n_planes), "super-resolution upscale launch");
+}
+
+size_t svt_hip_resize_scratch_bytes(int pix_bytes, const SvtHipResizePlane* planes, int n_planes) {
+    if (!pix_ok(pix_bytes) || !resize_planes_ok(planes, n_planes)) return 0;
+    return svt_hip_resize_scratch_layout_bytes(pix_bytes, planes, n_planes);
+}
+
+int svt_hip_resize_planes_dev(SvtHipCtx* c, int pix_bytes, int bd, const SvtHipResizePlane* planes, int n_planes, void* d_scratch, size_t scratch_bytes) {
+    SVT_HIP_ENTER(c);
+    if (!c || !fmt_8to12_ok(pix_bytes, bd) || !resize_planes_ok(planes, n_planes))
+        return bad_arg(c, "svt_hip_resize_planes_dev: bad argument (1 <= n_planes <= 3, every size 1 .. 16384, stride >= width, d_src != d_dst)");
+    const size_t need = svt_hip_resize_scratch_layout_bytes(pix_bytes, planes, n_planes);
+    if (need && (!d_scratch || scratch_bytes < need)) return bad_arg(c, "svt_hip_resize_planes_dev: d_scratch holds less than svt_hip_resize_scratch_bytes");
+    return launched(c, svt_hip_launch_resize_planes(c->stream, pix_bytes, bd, planes, n_planes, d_scratch), "resize launch");
 }
 
 

@@ -162,6 +162,10 @@ int svt_hip_launch_variance_pyramid(hipStream_t st, const uint8_t* plane, int st
                                     uint8_t* mean_out, uint16_t* var_out);
 int svt_hip_launch_sad_loop(hipStream_t st, const uint8_t* src, int src_stride, const uint8_t* ref, int ref_stride,
                             const SvtHipSadLoop* searches, int n, uint32_t* best_sad, int16_t* best_xy);
+/* resize.hip; the planes have passed svt_upscale_plane_ok / svt_resize_plane_ok of resize_plan.h */
+int svt_hip_launch_superres_upscale(hipStream_t st, int pix_bytes, int bd, const SvtHipUpscalePlane* planes, int n);
+size_t svt_hip_resize_scratch_layout_bytes(int pix_bytes, const SvtHipResizePlane* planes, int n);
+int svt_hip_launch_resize_planes(hipStream_t st, int pix_bytes, int bd, const SvtHipResizePlane* planes, int n, void* scratch);
 /* sgr.hip */
 int svt_hip_launch_sgr_proj_error(hipStream_t st, int pix_bytes, int bd, const void* dgd, int stride, const void* src, int src_stride, int pw, int ph,
                                   int unit_size, int units_x, int units_y, int ss_y, uint32_t ep_mask, int ncand, const int32_t* xqd, int64_t* err);
