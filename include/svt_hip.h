@@ -1070,6 +1070,61 @@ typedef struct {
 } SvtHipFilterIntraJob;
 int svt_hip_filter_intra_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_edges, const SvtHipFilterIntraJob *d_jobs, int njobs, void *d_dst,
                                            int dst_stride);
+/* The palette luma search for a list of blocks of one luma plane in one launch: search_palette_luma (Encoder/Codec/palette.c:320-496) -- svt_av1_count_colors[_highbd]
+ * (Encoder/Codec/EbPictureAnalysisProcess.c:3364-3399), the dominant colours, svt_av1_k_means_dim1 (Encoder/Codec/k_means_template.h:32-133, max_itr 50) from the
+ * lb / ub centroids, and for each of the up to fourteen candidates palette_rd_y (palette.c:245-312: optimize_palette_colors, av1_remove_duplicates, the clip,
+ * svt_av1_calc_indices_dim1, extend_palette_color_map) -- and svt_av1_palette_color_cost_y (palette.c:88-153) of every candidate kept.  A job's results are what the
+ * reference leaves in palette_cand[0 .. tot_palette_cands), in its order: the dominant-colour candidates n = min(colors, 8) down to 2 in steps of dominant_step, then
+ * the k-means candidates n = min(colors, 8) down to 2, each kept only when its palette_size is above 2.  The only neighbour-dependent input, the colour cache of
+ * svt_get_palette_cache (palette.c:163-205), is data of the job.
+ *   d_plane   : the luma plane (pix_bytes per sample, stride in samples); a job reads rows x cols samples at (x, y), which the caller keeps inside the plane
+ *   d_results : [njobs]; colors = the distinct sample values (0 when a 16-bit sample is not below 1 << bd, as the reference returns), n_cands = candidates kept;
+ *               nothing is kept unless 1 < colors <= 64
+ *   d_cands   : [njobs][14]; job i's kept candidates are records 14 i .. 14 i + n_cands - 1
+ *   d_maps    : candidate c of a job at map_off + c * bw * bh: the colour indices of the whole bw x bh block, row stride bw, the part outside rows x cols extended
+ *               from the last row / column inside
+ * Records and maps at candidate index >= n_cands are unspecified; every store stays inside the job's fourteen records and 14 * bw * bh map bytes.  A job whose
+ * bw x bh is not one of the 16 shapes svt_av1_allow_palette admits (Encoder/Codec/EbModeDecision.c:5052: 8x8 .. 64x64 with both sides <= 64, 4x16, 16x4), whose cols /
+ * rows is outside 1 .. bw / 1 .. bh, whose x or y is negative, whose n_cache is above 16 or whose dominant_step is not 1 or 2 gets colors = -1, n_cands = 0 and nothing
+ * else.  pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10.  Palette chroma, the colour-map rate (svt_av1_cost_color_map) and intra block copy are not covered.
+ * Stream-ordered and asynchronous: no host synchronisation, no allocation, no read-back. */
+#define SVT_HIP_PALETTE_MAX_CANDS 14
+typedef struct {
+    int32_t  x, y;                /* top-left sample of the block in the plane */
+    int32_t  bw, bh;              /* the block's full size */
+    int32_t  cols, rows;          /* the part inside the picture (av1_get_block_dimensions: mb_to_right_edge / mb_to_bottom_edge), 1 .. bw / 1 .. bh */
+    int32_t  n_cache;             /* 0 .. 16 */
+    int32_t  dominant_step;       /* 1, or 2 (palette_level == 6) */
+    uint16_t cache[16];           /* the sorted colour cache svt_get_palette_cache would return */
+    int64_t  map_off;             /* first byte of this job's maps in d_maps */
+} SvtHipPaletteJob;
+typedef struct {
+    int32_t colors;               /* svt_av1_count_colors[_highbd]; -1 for a job with a bad field */
+    int32_t n_cands;              /* tot_palette_cands, 0 .. 14 */
+} SvtHipPaletteResult;
+typedef struct {
+    int32_t  color_cost;          /* svt_av1_palette_color_cost_y of this candidate with the job's cache */
+    uint16_t colors[8];           /* pmi.palette_colors[0 .. size), ascending; 0 beyond */
+    uint16_t raw[8];              /* the n centroids before optimize_palette_colors, in the reference's order: the top colours or the k-means result; 0 beyond */
+    uint8_t  size;                /* pmi.palette_size[0], 3 .. 8 */
+    uint8_t  n;                   /* the centroids the candidate started from, 2 .. 8 */
+    uint8_t  kind;                /* 0 = dominant colours, 1 = k-means */
+    uint8_t  reserved;            /* 0 */
+} SvtHipPaletteCand;
+int svt_hip_palette_search_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_plane, int stride, const SvtHipPaletteJob *d_jobs, int njobs,
+                                     SvtHipPaletteResult *d_results, SvtHipPaletteCand *d_cands, uint8_t *d_maps);
+/* The same contract on host pointers, serially, from the arithmetic header the kernel shares (csrc/palette.h): no context and no device.  The same refusals. */
+int svt_hip_palette_search_host(int pix_bytes, int bd, const void *plane, int stride, const SvtHipPaletteJob *jobs, int njobs, SvtHipPaletteResult *results,
+                                SvtHipPaletteCand *cands, uint8_t *maps);
+/* is_screen_content (Encoder/Codec/EbPictureAnalysisProcess.c:3519-3601) of a luma plane: over every whole 16x16 block (r + 16 <= height, c + 16 <= width),
+ * counts_1 = the blocks is_valid_palette_nb_colors[_highbd] (:3459-3514) accepts with threshold 4 (more than one colour, at most four), counts_2 = those whose
+ * svt_av1_get_sby_perpixel_variance / svt_av1_high_get_sby_perpixel_variance (:3434-3454: svt_aom_variance16x16 / svt_aom_highbd_10_variance16x16 against the constant
+ * 128 / 512, ROUND_POWER_OF_TWO(var, 8)) is above 0; then color_detection = counts_1 * 2560 > width * height and sc_content_detected = color_detection &&
+ * counts_2 * 3072 > width * height (:3594-3599), which decide allow_screen_content_tools and palette_level (Encoder/Codec/EbPictureDecisionProcess.c:912-922).
+ * d_out receives four int32: counts_1, counts_2, color_detection, sc_content_detected.  pix_bytes 1 with bd 8, or pix_bytes 2 with bd 10: the 16-bit plane is the
+ * packed one (svt_hip_picture_format_dev), where the reference packs each block from its 8 + 2-bit planes first.  width * height must fit 31 bits.  Stream-ordered
+ * and asynchronous. */
+int svt_hip_screen_content_detect_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_plane, int stride, int width, int height, int32_t *d_out);
 /* open_loop_intra_search_mb (Encoder/Codec/EbMotionEstimation.c:3043-3155, called from the motion-estimation process when the look-ahead model is on) for every
  * 16x16 macroblock of an 8-bit luma picture, one launch: neighbours from the SOURCE picture (update_neighbor_samples_array_open_loop_mb,
  * Encoder/Codec/EbEncIntraPrediction.c:1201), for mode = DC_PRED .. mode_end the edges conditioned by filter_intra_edge (Common/Codec/EbIntraPrediction.c:2545), the

@@ -304,6 +304,44 @@ class GmEstimate(C.Structure):
                 ("ref_frame_error", C.c_int64), ("fits", GmFit * 2), ("models", GmModelRecord * 2)]
 
 
+class PaletteJob(C.Structure):
+    """SvtHipPaletteJob (include/svt_hip.h)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("bw", C.c_int32), ("bh", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32), ("n_cache", C.c_int32),
+                ("dominant_step", C.c_int32), ("cache", C.c_uint16 * 16), ("map_off", C.c_int64)]
+
+
+class PaletteResult(C.Structure):
+    """SvtHipPaletteResult (include/svt_hip.h)."""
+    _fields_ = [("colors", C.c_int32), ("n_cands", C.c_int32)]
+
+
+class PaletteCand(C.Structure):
+    """SvtHipPaletteCand (include/svt_hip.h)."""
+    _fields_ = [("color_cost", C.c_int32), ("colors", C.c_uint16 * 8), ("raw", C.c_uint16 * 8), ("size", C.c_uint8), ("n", C.c_uint8), ("kind", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+PALETTE_MAX_CANDS = 14   # SVT_HIP_PALETTE_MAX_CANDS
+
+
+def palette_search_host(plane, jobs, results=None, cands=None, maps=None, bd=None):
+    """svt_hip_palette_search_host: `plane` a 2-D uint8 / uint16 luma plane (may be an offset / strided view), `jobs` a ctypes array of PaletteJob.  `results`
+    (PaletteResult * njobs), `cands` (PaletteCand * (14 njobs)) and `maps` (uint8 numpy array) are written in place when given, else made here, the maps zeroed
+    and as long as the jobs' map_off need.  -> (results, cands, maps)."""
+    import numpy as np
+    n = len(jobs)
+    assert plane.ndim == 2 and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
+    results = results if results is not None else (PaletteResult * max(n, 1))()
+    cands = cands if cands is not None else (PaletteCand * (PALETTE_MAX_CANDS * max(n, 1)))()
+    if maps is None:
+        maps = np.zeros(max([j.map_off + PALETTE_MAX_CANDS * j.bw * j.bh for j in jobs if 0 <= j.bw <= 64 and 0 <= j.bh <= 64 and j.map_off >= 0] + [4]), np.uint8)
+    rc = lib().svt_hip_palette_search_host(plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), plane.ctypes.data_as(C.c_void_p), plane.strides[0] // plane.itemsize,
+                                           C.cast(jobs, C.c_void_p), n, C.cast(results, C.c_void_p), C.cast(cands, C.c_void_p), maps.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_palette_search_host refused its arguments: status {rc}")
+    return results, cands, maps
+
+
 class UpscalePlane(C.Structure):
     """SvtHipUpscalePlane (include/svt_hip.h)."""
     _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32), ("out_w", C.c_int32),
@@ -555,6 +593,10 @@ PROTOTYPES = {
     "svt_hip_cfl_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp]),
     "svt_hip_filter_intra_predict_batch_dev": (i32, [vp, i32, i32, vp, vp, i32, vp, i32]),
     "svt_hip_intra_ois_picture_dev": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    # ---- palette luma search, screen-content detection
+    "svt_hip_palette_search_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
+    "svt_hip_palette_search_host": (i32, [i32, i32, vp, i32, vp, i32, vp, vp, vp]),
+    "svt_hip_screen_content_detect_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp]),
     # ---- TPL flow dispenser
     "svt_hip_tpl_dispenser_scratch_bytes": (sz, [i32, i32]),
     "svt_hip_tpl_dispenser_picture_dev": (i32, [vp, P(TplParams), vp, i32, P(TplRef), vp, vp, vp, vp, vp, i32, vp, vp]),
@@ -738,6 +780,44 @@ class Context:
             if d_ac is not None:
                 out += (self.to_host(d_ac, ac0.shape, np.int16),)
             return out
+        finally:
+            self.free(*held)
+
+    def palette_search_batch(self, plane, jobs, results, cands, maps, bd=None):
+        """svt_hip_palette_search_batch_dev: `plane` a 2-D uint8 / uint16 luma plane (may be an offset / strided view; bd 8 for uint8, 10 for uint16 unless `bd` says
+        8), `jobs` a ctypes array of PaletteJob.  `results` (PaletteResult * njobs), `cands` (PaletteCand * (14 njobs)) and `maps` (uint8 numpy array) are the
+        initial content of the three outputs.  -> (results, cands, maps) as the device left them, fresh objects of the same types."""
+        import numpy as np
+        held = []
+        try:
+            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+            d_j = self._upload_jobs(jobs); held.append(d_j)
+            d_r, d_c = self._upload_jobs(results), self._upload_jobs(cands); held += [d_r, d_c]
+            d_m = self.to_device(maps); held.append(d_m)
+            self.check(self.L.svt_hip_palette_search_batch_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, d_j, len(jobs), d_r, d_c, d_m),
+                       "palette_search_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out_r, out_c = type(results)(), type(cands)()
+            if C.sizeof(out_r): self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_r, C.c_void_p), d_r, C.sizeof(out_r)), "d2h")
+            if C.sizeof(out_c): self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_c, C.c_void_p), d_c, C.sizeof(out_c)), "d2h")
+            return out_r, out_c, self.to_host(d_m, maps.shape, np.uint8)
+        finally:
+            self.free(*held)
+
+    def screen_content_detect(self, plane, bd=None, out=None):
+        """svt_hip_screen_content_detect_dev: `plane` a 2-D uint8 (bd 8) or uint16 (bd 10) luma plane, may be an offset / strided view.  `out`, if given, is an int32
+        array of at least four words, the initial content of the output buffer.  -> that buffer after the call: counts_1, counts_2, color_detection,
+        sc_content_detected, then whatever followed."""
+        import numpy as np
+        out = np.zeros(4, np.int32) if out is None else np.ascontiguousarray(out, np.int32)
+        held = []
+        try:
+            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+            d_o = self.to_device(out); held.append(d_o)
+            self.check(self.L.svt_hip_screen_content_detect_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, plane.shape[1], plane.shape[0], d_o),
+                       "screen_content_detect")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_o, out.shape, np.int32)
         finally:
             self.free(*held)
 

@@ -260,7 +260,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -323,6 +323,24 @@ int svt_hip_filter_intra_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, 
         return bad_arg(c, "svt_hip_filter_intra_predict_batch_dev: bad argument");
     if (!njobs) return SVT_HIP_OK;
     return launched(c, svt_hip_launch_filter_intra_predict(c->stream, pix_bytes, bd, d_edges, d_jobs, njobs, d_dst, dst_stride), "filter-intra predict launch");
+}
+
+/* ---------------------------------------------------------------------------------- palette luma search, screen-content detection (palette.hip) */
+int svt_hip_palette_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_plane, int stride, const SvtHipPaletteJob* d_jobs, int njobs,
+                                     SvtHipPaletteResult* d_results, SvtHipPaletteCand* d_cands, uint8_t* d_maps) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_plane || !d_jobs || !d_results || !d_cands || !d_maps || njobs < 0 || !fmt_ok(pix_bytes, bd) || stride <= 0)
+        return bad_arg(c, "svt_hip_palette_search_batch_dev: bad argument");
+    if (!njobs) return SVT_HIP_OK;
+    return launched(c, svt_hip_launch_palette_search(c->stream, pix_bytes, bd, d_plane, stride, d_jobs, njobs, d_results, d_cands, d_maps), "palette search launch");
+}
+
+int svt_hip_screen_content_detect_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_plane, int stride, int width, int height, int32_t* d_out) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_plane || !d_out || !((pix_bytes == 1 && bd == 8) || (pix_bytes == 2 && bd == 10)) || stride <= 0 || width < 1 || height < 1 ||
+        (int64_t)width * height > INT32_MAX)
+        return bad_arg(c, "svt_hip_screen_content_detect_dev: bad argument (pix_bytes 1 with bd 8 or pix_bytes 2 with bd 10, stride > 0, width and height >= 1)");
+    return launched(c, svt_hip_launch_screen_content_detect(c->stream, pix_bytes, d_plane, stride, width, height, d_out), "screen-content detect launch");
 }
 
 /* ---------------------------------------------------------------------------------- TPL dispenser */

@@ -7,6 +7,7 @@
 #include "svt_hip_host.h"
 #include "gm_walk.h"
 #include "tpl_synth.h"
+#include "palette.h"
 
 extern "C" {
 
@@ -295,6 +296,15 @@ int svt_hip_gm_decide_host(const SvtHipGmModelRecord models[2], int64_t ref_fram
 int svt_hip_tpl_window_host(const SvtHipTplSynthParams* p, const SvtHipTplWindowFrame* frames, int n_frames, void* out) {
     if (!tplsyn::params_ok(p) || p->rate != 0 || tplsyn::frames_check(frames, n_frames) || !out || ((uintptr_t)out & 7)) return SVT_HIP_ERR_BAD_ARG;
     tplsyn::window_host(*p, frames, n_frames, out);
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- palette luma search */
+/* svt_hip_palette_search_batch_dev's contract on host pointers: palette.h run serially, job by job, sample by sample */
+int svt_hip_palette_search_host(int pix_bytes, int bd, const void* plane, int stride, const SvtHipPaletteJob* jobs, int njobs, SvtHipPaletteResult* results,
+                                SvtHipPaletteCand* cands, uint8_t* maps) {
+    if (!pal::search_args_ok(pix_bytes, bd, plane, stride, jobs, njobs, results, cands, maps)) return SVT_HIP_ERR_BAD_ARG;
+    pal::search_host(pix_bytes, bd, plane, stride, jobs, njobs, results, cands, maps);
     return SVT_HIP_OK;
 }
 

@@ -117,6 +117,10 @@ int svt_hip_launch_intra_predict(hipStream_t st, int pix_bytes, int bd, const vo
 int svt_hip_launch_cfl_predict(hipStream_t st, int pix_bytes, int bd, const void* luma, int luma_stride, const void* edges, const SvtHipCflJob* jobs, int njobs, void* cb,
                                void* cr, int chroma_stride, int16_t* ac);
 int svt_hip_launch_filter_intra_predict(hipStream_t st, int pix_bytes, int bd, const void* edges, const SvtHipFilterIntraJob* jobs, int njobs, void* dst, int dst_stride);
+/* palette.hip; the arithmetic both sides share is palette.h */
+int svt_hip_launch_palette_search(hipStream_t st, int pix_bytes, int bd, const void* plane, int stride, const SvtHipPaletteJob* jobs, int njobs, SvtHipPaletteResult* results,
+                                  SvtHipPaletteCand* cands, uint8_t* maps);
+int svt_hip_launch_screen_content_detect(hipStream_t st, int pix_bytes, const void* plane, int stride, int width, int height, int32_t* out);
 /* md_pre.hip */
 int svt_hip_launch_md_fullpel_sad(hipStream_t st, int pix_bytes, const void* src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus, const SvtHipMdPu* pus,
                                   int n_refs, const SvtHipMdRefPlane* refs, const uint32_t* mv, uint32_t* sad);
