@@ -1125,6 +1125,80 @@ int svt_hip_palette_search_host(int pix_bytes, int bd, const void *plane, int st
  * packed one (svt_hip_picture_format_dev), where the reference packs each block from its 8 + 2-bit planes first.  width * height must fit 31 bits.  Stream-ordered
  * and asynchronous. */
 int svt_hip_screen_content_detect_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_plane, int stride, int width, int height, int32_t *d_out);
+/* Intra block copy: the hash table of a picture and the hash search of a list of blocks.  IntraBC searches the SOURCE picture (Encoder/Codec/EbModeDecision.c:4443-4448),
+ * so nothing here waits for a neighbour's reconstruction.  pix_bytes 1 with bd 8, or pix_bytes 2 with bd 8 / 10 (the reference has the 16-bit branch of the hashes
+ * although its encoder passes 8-bit samples).  The CRC is Encoder/Codec/hash.c:13-62: width 24, polynomials 0x5D6DCB (hash 1) and 0x864CFB (hash 2), the remainder
+ * reset per value; a 2x2 block hashes its 4 sample bytes or the 8 bytes of its four 16-bit samples in memory order, a larger block the 16 bytes of its four
+ * children's hashes as little-endian words.  Every device entry point is stream-ordered and asynchronous: no allocation, no host synchronisation, no read-back; what
+ * it refuses it refuses before any launch.  width, height <= 32767 (an entry's int16), width * height within 31 bits, stride >= width.  The diamond and mesh
+ * searches around the hash search, and a hook in the encoder, are not covered. */
+#define SVT_HIP_IBC_HASH_BUCKETS (1 << 19)
+#define SVT_HIP_IBC_MV_VALS 32767
+typedef struct {
+    int16_t  x, y;                /* top-left sample of the block */
+    uint32_t hash_value2;
+} SvtHipIbcHashEntry;             /* BlockHash (Encoder/Codec/hash_motion.h) */
+/* bytes of d_scratch for a picture (0 for a size that is refused), and the most entries its table can have (every position of every block size) */
+size_t svt_hip_ibc_hash_scratch_bytes(int width, int height);
+size_t svt_hip_ibc_hash_max_entries(int width, int height);
+/* svt_av1_generate_block_2x2_hash_value (Encoder/Codec/hash_motion.c:138-186) followed by svt_av1_generate_block_hash_value (:188-251) applied 2 -> 4 -> ... ->
+ * block_size (2, 4, ... 128): what those calls leave in the valid region x < width - block_size + 1, y < height - block_size + 1 of
+ *   d_hash1, d_hash2 : uint32[width * height], indexed y * width + x as the reference indexes them
+ *   d_same           : int8[3][width * height]: same_info[0] (rows alike), [1] (columns alike), [2] the "add this position" flag of :238-250 (block_size >= 4 only)
+ * Everything outside the valid region is unspecified; a picture smaller than block_size has an empty region and nothing is written.  d_scratch: at least
+ * svt_hip_ibc_hash_scratch_bytes(width, height), 256-byte aligned. */
+int svt_hip_ibc_block_hashes_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_luma, int stride, int width, int height, int block_size, uint32_t *d_hash1,
+                                 uint32_t *d_hash2, int8_t *d_same, void *d_scratch, size_t scratch_bytes);
+/* The table the hash generation of an intra picture builds (Encoder/Codec/EbModeDecisionConfigurationProcess.c:939-1051: the two generators and six
+ * svt_av1_add_to_hash_map_by_row_with_precal_data calls, hash_motion.c:253-283), as compressed rows:
+ *   d_bucket_start : int32[SVT_HIP_IBC_HASH_BUCKETS + 1]; bucket k = (hash1 & 0xFFFF) + (size_index << 16), size_index 0 .. 5 for 4 .. 128, holds entries
+ *                    d_bucket_start[k] .. d_bucket_start[k + 1] - 1
+ *   d_entries      : [capacity]; inside a bucket in the reference's insertion order, ascending x, then ascending y (the inserter scans column by column and a
+ *                    bucket belongs to one block size).  The search keeps the first smallest cost, so the order is part of the result; it never depends on the
+ *                    order in which atomics arrive
+ *   d_info         : int32[2] = {n_entries, stored}.  d_bucket_start is always complete; when n_entries > capacity no entry is stored, stored = 0, and nothing
+ *                    is written outside the buffers
+ * d_scratch: at least svt_hip_ibc_hash_scratch_bytes(width, height), 256-byte aligned. */
+int svt_hip_ibc_hash_table_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_luma, int stride, int width, int height, int32_t *d_bucket_start,
+                               SvtHipIbcHashEntry *d_entries, int64_t capacity, int32_t *d_info, void *d_scratch, size_t scratch_bytes);
+/* The hash search of svt_av1_full_pixel_search (Encoder/Codec/av1me.c:1346-1403, the do { } while (0)) for every job in one launch; the comparison with the diamond
+ * search's var (:1404-1408) stays with the caller.  Per job: the block's two hash values as svt_av1_get_block_hash_value computes them from the samples
+ * (hash_motion.c:285-369); count = the bucket's size, and the job stops when count <= (intra ? 1 : 0); for every entry of equal hash_value2, in bucket order,
+ * av1_is_dv_valid (Encoder/Codec/EbAdaptiveMotionVectorPrediction.c:2003-2083, when intra) and is_mv_in (av1me.c:320-323), then the cost svt_av1_get_mvpred_var
+ * (av1me.c:328-342): svt_aom_variance{N}x{N} of the block against the entry's block of the same plane (bd 10: the form of svt_aom_highbd_10_variance) plus
+ * mv_err_cost (av1me.c:273-282); the strict < keeps the first smallest cost.
+ *   d_mv_joint_cost : int32[4]; d_mv_comp_cost : int32[2][SVT_HIP_IBC_MV_VALS], row then column, entry [16383 + d] for a difference d in 1/8 sample
+ * An entry whose difference from ref_mv is outside -16383 .. 16383 (the reference would read outside the tables) or whose block is not inside the picture (the
+ * table's builder makes none) is passed over like one outside the limits.  A job whose block_size is not 4 .. 128, whose position is negative, whose block is not
+ * inside the picture, whose mib_size_log2 is outside 0 .. 16 or whose tile bounds are outside 0 .. 2^20 gets count = -1.  Whenever found = 0: best_cost = INT32_MAX,
+ * best_row = best_col = 0. */
+typedef struct {
+    int32_t x_pos, y_pos;         /* top-left sample of the block */
+    int32_t block_size;           /* 4, 8, 16, 32, 64 or 128 */
+    int32_t intra;                /* 1: the entries are filtered by av1_is_dv_valid and the block itself is expected in its bucket */
+    int32_t col_min, col_max, row_min, row_max;   /* x->mv_limits, whole samples */
+    int32_t ref_mv_row, ref_mv_col;               /* 1/8 sample */
+    int32_t error_per_bit;
+    int32_t mi_row_start, mi_row_end, mi_col_start, mi_col_end;   /* xd->tile */
+    int32_t mib_size_log2;        /* av1_is_dv_valid's last argument */
+} SvtHipIbcSearchJob;
+typedef struct {
+    int32_t count;                /* the bucket's size; -1 for a job with a bad field */
+    int32_t n_matched;            /* entries of equal hash_value2 */
+    int32_t n_valid;              /* ... that passed av1_is_dv_valid and is_mv_in and were costed */
+    int32_t found;                /* n_valid > 0 */
+    int32_t best_cost, best_row, best_col;   /* best_hash_cost, best_hash_mv (whole samples) */
+} SvtHipIbcSearchResult;
+int svt_hip_ibc_hash_search_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_luma, int stride, int width, int height, const int32_t *d_bucket_start,
+                                      const SvtHipIbcHashEntry *d_entries, const int32_t *d_mv_joint_cost, const int32_t *d_mv_comp_cost, const SvtHipIbcSearchJob *d_jobs,
+                                      int njobs, SvtHipIbcSearchResult *d_results);
+/* The same contracts on host pointers, serially, from the arithmetic header the kernels share (csrc/ibc_hash.h): no context and no device.  The same refusals; the
+ * scratch is host memory of svt_hip_ibc_hash_scratch_bytes(width, height). */
+int svt_hip_ibc_hash_table_host(int pix_bytes, int bd, const void *luma, int stride, int width, int height, int32_t *bucket_start, SvtHipIbcHashEntry *entries,
+                                int64_t capacity, int32_t *info, void *scratch, size_t scratch_bytes);
+int svt_hip_ibc_hash_search_host(int pix_bytes, int bd, const void *luma, int stride, int width, int height, const int32_t *bucket_start,
+                                 const SvtHipIbcHashEntry *entries, const int32_t *mv_joint_cost, const int32_t *mv_comp_cost, const SvtHipIbcSearchJob *jobs, int njobs,
+                                 SvtHipIbcSearchResult *results);
 /* open_loop_intra_search_mb (Encoder/Codec/EbMotionEstimation.c:3043-3155, called from the motion-estimation process when the look-ahead model is on) for every
  * 16x16 macroblock of an 8-bit luma picture, one launch: neighbours from the SOURCE picture (update_neighbor_samples_array_open_loop_mb,
  * Encoder/Codec/EbEncIntraPrediction.c:1201), for mode = DC_PRED .. mode_end the edges conditioned by filter_intra_edge (Common/Codec/EbIntraPrediction.c:2545), the

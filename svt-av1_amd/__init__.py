@@ -342,6 +342,68 @@ def palette_search_host(plane, jobs, results=None, cands=None, maps=None, bd=Non
     return results, cands, maps
 
 
+class IbcHashEntry(C.Structure):
+    """SvtHipIbcHashEntry (include/svt_hip.h)."""
+    _fields_ = [("x", C.c_int16), ("y", C.c_int16), ("hash_value2", C.c_uint32)]
+
+
+class IbcSearchJob(C.Structure):
+    """SvtHipIbcSearchJob (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("x_pos", "y_pos", "block_size", "intra", "col_min", "col_max", "row_min", "row_max", "ref_mv_row", "ref_mv_col", "error_per_bit",
+                                         "mi_row_start", "mi_row_end", "mi_col_start", "mi_col_end", "mib_size_log2")]
+
+
+class IbcSearchResult(C.Structure):
+    """SvtHipIbcSearchResult (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("count", "n_matched", "n_valid", "found", "best_cost", "best_row", "best_col")]
+
+
+IBC_HASH_BUCKETS = 1 << 19   # SVT_HIP_IBC_HASH_BUCKETS
+IBC_MV_VALS = 32767          # SVT_HIP_IBC_MV_VALS
+IBC_ENTRY_DTYPE = [("x", "<i2"), ("y", "<i2"), ("hash_value2", "<u4")]   # SvtHipIbcHashEntry as a numpy record
+
+
+def _plane_args(plane):
+    assert plane.ndim == 2 and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
+    return plane.itemsize, plane.ctypes.data_as(C.c_void_p), plane.strides[0] // plane.itemsize, plane.shape[1], plane.shape[0]
+
+
+def ibc_hash_table_host(plane, capacity=None, bd=None):
+    """svt_hip_ibc_hash_table_host: `plane` a 2-D uint8 / uint16 luma plane (may be a strided view).  capacity None: svt_hip_ibc_hash_max_entries.
+    -> (bucket_start int32[2^19 + 1], entries record array [capacity], info int32[2])."""
+    import numpy as np
+    L = lib()
+    pb, p, stride, w, h = _plane_args(plane)
+    capacity = int(L.svt_hip_ibc_hash_max_entries(w, h)) if capacity is None else capacity
+    start, entries, info = np.zeros(IBC_HASH_BUCKETS + 1, np.int32), np.zeros(max(capacity, 1), IBC_ENTRY_DTYPE), np.zeros(2, np.int32)
+    nbytes = L.svt_hip_ibc_hash_scratch_bytes(w, h)
+    scratch = np.zeros(max(nbytes, 1), np.uint8)
+    rc = L.svt_hip_ibc_hash_table_host(pb, bd or (8 if pb == 1 else 10), p, stride, w, h, start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p), capacity,
+                                       info.ctypes.data_as(C.c_void_p), scratch.ctypes.data_as(C.c_void_p), nbytes)
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_ibc_hash_table_host refused its arguments: status {rc}")
+    return start, entries[:capacity], info
+
+
+def ibc_cost_tables(joint_cost, comp_cost):
+    import numpy as np
+    j, c = np.ascontiguousarray(joint_cost, np.int32), np.ascontiguousarray(comp_cost, np.int32)
+    assert j.shape == (4,) and c.shape == (2, IBC_MV_VALS)
+    return j, c
+
+
+def ibc_hash_search_host(plane, bucket_start, entries, joint_cost, comp_cost, jobs, bd=None):
+    """svt_hip_ibc_hash_search_host: `jobs` a ctypes array of IbcSearchJob; the table as ibc_hash_table_host returns it.  -> IbcSearchResult * njobs."""
+    pb, p, stride, w, h = _plane_args(plane)
+    j, c = ibc_cost_tables(joint_cost, comp_cost)
+    res = (IbcSearchResult * max(len(jobs), 1))()
+    rc = lib().svt_hip_ibc_hash_search_host(pb, bd or (8 if pb == 1 else 10), p, stride, w, h, bucket_start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p),
+                                            j.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.cast(jobs, C.c_void_p), len(jobs), C.cast(res, C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_ibc_hash_search_host refused its arguments: status {rc}")
+    return res
+
+
 class UpscalePlane(C.Structure):
     """SvtHipUpscalePlane (include/svt_hip.h)."""
     _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32), ("out_w", C.c_int32),
@@ -597,6 +659,14 @@ PROTOTYPES = {
     "svt_hip_palette_search_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
     "svt_hip_palette_search_host": (i32, [i32, i32, vp, i32, vp, i32, vp, vp, vp]),
     "svt_hip_screen_content_detect_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp]),
+    # ---- intra block copy: hash planes, hash table, hash search
+    "svt_hip_ibc_hash_scratch_bytes": (sz, [i32, i32]),
+    "svt_hip_ibc_hash_max_entries": (sz, [i32, i32]),
+    "svt_hip_ibc_block_hashes_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz]),
+    "svt_hip_ibc_hash_table_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, C.c_int64, vp, vp, sz]),
+    "svt_hip_ibc_hash_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "svt_hip_ibc_hash_table_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, C.c_int64, vp, vp, sz]),
+    "svt_hip_ibc_hash_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
     # ---- TPL flow dispenser
     "svt_hip_tpl_dispenser_scratch_bytes": (sz, [i32, i32]),
     "svt_hip_tpl_dispenser_picture_dev": (i32, [vp, P(TplParams), vp, i32, P(TplRef), vp, vp, vp, vp, vp, i32, vp, vp]),
@@ -818,6 +888,75 @@ class Context:
                        "screen_content_detect")
             self.check(self.L.svt_hip_sync(self.h), "sync")
             return self.to_host(d_o, out.shape, np.int32)
+        finally:
+            self.free(*held)
+
+    def ibc_block_hashes(self, plane, block_size, bd=None, fill=0):
+        """svt_hip_ibc_block_hashes_dev: `plane` a 2-D uint8 / uint16 luma plane (may be a strided view).  The outputs start filled with the byte `fill`.
+        -> (hash1, hash2 uint32[h, w], same int8[3, h, w]); only x < w - block_size + 1, y < h - block_size + 1 is specified."""
+        import numpy as np
+        h, w = plane.shape
+        held = []
+        try:
+            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+            nbytes = self.L.svt_hip_ibc_hash_scratch_bytes(w, h)
+            d_s = self.empty(max(nbytes, 256)); held.append(d_s)
+            d_1, d_2 = self.to_device(np.full(w * h * 4, fill, np.uint8)), self.to_device(np.full(w * h * 4, fill, np.uint8)); held += [d_1, d_2]
+            d_m = self.to_device(np.full(3 * w * h, fill, np.uint8)); held.append(d_m)
+            self.check(self.L.svt_hip_ibc_block_hashes_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, block_size, d_1, d_2, d_m, d_s, nbytes),
+                       "ibc_block_hashes")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            return self.to_host(d_1, (h, w), np.uint32), self.to_host(d_2, (h, w), np.uint32), self.to_host(d_m, (3, h, w), np.int8)
+        finally:
+            self.free(*held)
+
+    def ibc_hash_table(self, plane, capacity=None, bd=None, guard=0, fill=0xC3):
+        """svt_hip_ibc_hash_table_dev: `plane` a 2-D uint8 / uint16 luma plane.  capacity None: svt_hip_ibc_hash_max_entries.  `guard` bytes of `fill` lie before
+        and behind d_bucket_start and d_entries, which start filled with it too.  -> (bucket_start int32[2^19 + 1], entries record array [capacity], info
+        int32[2], the four guard areas as uint8 arrays)."""
+        import numpy as np
+        h, w = plane.shape
+        capacity = int(self.L.svt_hip_ibc_hash_max_entries(w, h)) if capacity is None else capacity
+        assert guard % 8 == 0
+        nb_s, nb_e = (IBC_HASH_BUCKETS + 1) * 4, capacity * 8
+        held = []
+        try:
+            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+            nbytes = self.L.svt_hip_ibc_hash_scratch_bytes(w, h)
+            d_s = self.empty(max(nbytes, 256)); held.append(d_s)
+            d_b = self.to_device(np.full(nb_s + 2 * guard, fill, np.uint8)); held.append(d_b)
+            d_e = self.to_device(np.full(nb_e + 2 * guard + 8, fill, np.uint8)); held.append(d_e)
+            d_i = self.to_device(np.full(2, -1, np.int32)); held.append(d_i)
+            self.check(self.L.svt_hip_ibc_hash_table_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, d_b.value + guard, d_e.value + guard,
+                                                         capacity, d_i, d_s, nbytes), "ibc_hash_table")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            b, e = self.to_host(d_b, (nb_s + 2 * guard,), np.uint8), self.to_host(d_e, (nb_e + 2 * guard + 8,), np.uint8)
+            guards = (b[:guard], b[guard + nb_s:], e[:guard], e[guard + nb_e:])
+            return b[guard:guard + nb_s].view(np.int32).copy(), e[guard:guard + nb_e].view(IBC_ENTRY_DTYPE).copy(), self.to_host(d_i, (2,), np.int32), guards
+        finally:
+            self.free(*held)
+
+    def ibc_hash_search_batch(self, plane, bucket_start, entries, joint_cost, comp_cost, jobs, bd=None, fill=0xC3):
+        """svt_hip_ibc_hash_search_batch_dev: the table as ibc_hash_table returns it, `jobs` a ctypes array of IbcSearchJob.  -> IbcSearchResult * njobs as the
+        device left them (started as the byte `fill`)."""
+        import numpy as np
+        h, w = plane.shape
+        j, c = ibc_cost_tables(joint_cost, comp_cost)
+        res = (IbcSearchResult * max(len(jobs), 1))()
+        C.memset(res, fill, C.sizeof(res))
+        held = []
+        try:
+            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+            d_b = self.to_device(np.ascontiguousarray(bucket_start, np.int32)); held.append(d_b)
+            d_e = self.to_device(np.frombuffer(entries.tobytes() + bytes(8), np.uint8)); held.append(d_e)
+            d_jc, d_cc = self.to_device(j), self.to_device(c); held += [d_jc, d_cc]
+            d_j, d_r = self._upload_jobs(jobs if len(jobs) else (IbcSearchJob * 1)()), self._upload_jobs(res); held += [d_j, d_r]
+            self.check(self.L.svt_hip_ibc_hash_search_batch_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, d_b, d_e, d_jc, d_cc, d_j,
+                                                                len(jobs), d_r), "ibc_hash_search_batch")
+            self.check(self.L.svt_hip_sync(self.h), "sync")
+            out = type(res)()
+            self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_r, C.sizeof(out)), "d2h")
+            return out
         finally:
             self.free(*held)
 

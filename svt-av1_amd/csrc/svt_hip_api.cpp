@@ -12,6 +12,7 @@
 #include "svt_hip_host.h"
 #include "tpl_synth.h"
 #include "resize_plan.h"
+#include "ibc_hash.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -260,7 +261,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -341,6 +342,45 @@ int svt_hip_screen_content_detect_dev(SvtHipCtx* c, int pix_bytes, int bd, const
         (int64_t)width * height > INT32_MAX)
         return bad_arg(c, "svt_hip_screen_content_detect_dev: bad argument (pix_bytes 1 with bd 8 or pix_bytes 2 with bd 10, stride > 0, width and height >= 1)");
     return launched(c, svt_hip_launch_screen_content_detect(c->stream, pix_bytes, d_plane, stride, width, height, d_out), "screen-content detect launch");
+}
+
+/* ---------------------------------------------------------------------------------- intra block copy: hash planes, hash table, hash search (ibc_hash.hip) */
+size_t svt_hip_ibc_hash_scratch_bytes(int width, int height) { return ibc::picture_ok(width, width, height) ? ibc::scratch_layout(width, height).total : 0; }
+size_t svt_hip_ibc_hash_max_entries(int width, int height) { return ibc::picture_ok(width, width, height) ? (size_t)ibc::max_entries(width, height) : 0; }
+static bool ibc_scratch_ok(const void* d_scratch, size_t scratch_bytes, int width, int height) {
+    return d_scratch && !((uintptr_t)d_scratch & 255) && scratch_bytes >= ibc::scratch_layout(width, height).total;
+}
+
+int svt_hip_ibc_block_hashes_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_luma, int stride, int width, int height, int block_size, uint32_t* d_hash1,
+                                 uint32_t* d_hash2, int8_t* d_same, void* d_scratch, size_t scratch_bytes) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_luma || !d_hash1 || !d_hash2 || !d_same || !ibc::fmt_ok(pix_bytes, bd) || !ibc::picture_ok(stride, width, height) ||
+        (block_size != 2 && ibc::size_index(block_size) < 0) || !ibc_scratch_ok(d_scratch, scratch_bytes, width, height))
+        return bad_arg(c, "svt_hip_ibc_block_hashes_dev: bad argument");
+    return launched(c, svt_hip_launch_ibc_block_hashes(c->stream, pix_bytes, d_luma, stride, width, height, block_size, d_hash1, d_hash2, d_same, d_scratch),
+                    "intra-block-copy block hashes launch");
+}
+
+int svt_hip_ibc_hash_table_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_luma, int stride, int width, int height, int32_t* d_bucket_start,
+                               SvtHipIbcHashEntry* d_entries, int64_t capacity, int32_t* d_info, void* d_scratch, size_t scratch_bytes) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_luma || !d_bucket_start || !d_info || (!d_entries && capacity) || capacity < 0 || !ibc::fmt_ok(pix_bytes, bd) || !ibc::picture_ok(stride, width, height) ||
+        !ibc_scratch_ok(d_scratch, scratch_bytes, width, height))
+        return bad_arg(c, "svt_hip_ibc_hash_table_dev: bad argument");
+    return launched(c, svt_hip_launch_ibc_hash_table(c->stream, pix_bytes, d_luma, stride, width, height, d_bucket_start, d_entries, capacity, d_info, d_scratch),
+                    "intra-block-copy hash table launch");
+}
+
+int svt_hip_ibc_hash_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_luma, int stride, int width, int height, const int32_t* d_bucket_start,
+                                      const SvtHipIbcHashEntry* d_entries, const int32_t* d_mv_joint_cost, const int32_t* d_mv_comp_cost, const SvtHipIbcSearchJob* d_jobs,
+                                      int njobs, SvtHipIbcSearchResult* d_results) {
+    SVT_HIP_ENTER(c);
+    if (!c || !ibc::search_args_ok(pix_bytes, bd, d_luma, stride, width, height, d_bucket_start, d_entries, d_mv_joint_cost, d_mv_comp_cost, d_jobs, njobs, d_results))
+        return bad_arg(c, "svt_hip_ibc_hash_search_batch_dev: bad argument");
+    if (!njobs) return SVT_HIP_OK;
+    return launched(c, svt_hip_launch_ibc_hash_search(c->stream, pix_bytes, bd, d_luma, stride, width, height, d_bucket_start, d_entries, d_mv_joint_cost, d_mv_comp_cost,
+                                                      d_jobs, njobs, d_results),
+                    "intra-block-copy hash search launch");
 }
 
 /* ---------------------------------------------------------------------------------- TPL dispenser */

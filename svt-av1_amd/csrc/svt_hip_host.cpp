@@ -8,6 +8,7 @@
 #include "gm_walk.h"
 #include "tpl_synth.h"
 #include "palette.h"
+#include "ibc_hash.h"
 
 extern "C" {
 
@@ -305,6 +306,22 @@ int svt_hip_palette_search_host(int pix_bytes, int bd, const void* plane, int st
                                 SvtHipPaletteCand* cands, uint8_t* maps) {
     if (!pal::search_args_ok(pix_bytes, bd, plane, stride, jobs, njobs, results, cands, maps)) return SVT_HIP_ERR_BAD_ARG;
     pal::search_host(pix_bytes, bd, plane, stride, jobs, njobs, results, cands, maps);
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- intra block copy: hash table, hash search */
+/* the contracts of svt_hip_ibc_hash_table_dev / svt_hip_ibc_hash_search_batch_dev on host pointers: ibc_hash.h run serially */
+int svt_hip_ibc_hash_table_host(int pix_bytes, int bd, const void* luma, int stride, int width, int height, int32_t* bucket_start, SvtHipIbcHashEntry* entries,
+                                int64_t capacity, int32_t* info, void* scratch, size_t scratch_bytes) {
+    if (!ibc::table_args_ok(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, capacity, info, scratch, scratch_bytes)) return SVT_HIP_ERR_BAD_ARG;
+    ibc::table_host(pix_bytes, luma, stride, width, height, bucket_start, entries, capacity, info, scratch);
+    return SVT_HIP_OK;
+}
+
+int svt_hip_ibc_hash_search_host(int pix_bytes, int bd, const void* luma, int stride, int width, int height, const int32_t* bucket_start, const SvtHipIbcHashEntry* entries,
+                                 const int32_t* mv_joint_cost, const int32_t* mv_comp_cost, const SvtHipIbcSearchJob* jobs, int njobs, SvtHipIbcSearchResult* results) {
+    if (!ibc::search_args_ok(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, jobs, njobs, results)) return SVT_HIP_ERR_BAD_ARG;
+    ibc::search_host(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, jobs, njobs, results);
     return SVT_HIP_OK;
 }
 

@@ -121,6 +121,14 @@ int svt_hip_launch_filter_intra_predict(hipStream_t st, int pix_bytes, int bd, c
 int svt_hip_launch_palette_search(hipStream_t st, int pix_bytes, int bd, const void* plane, int stride, const SvtHipPaletteJob* jobs, int njobs, SvtHipPaletteResult* results,
                                   SvtHipPaletteCand* cands, uint8_t* maps);
 int svt_hip_launch_screen_content_detect(hipStream_t st, int pix_bytes, const void* plane, int stride, int width, int height, int32_t* out);
+/* ibc_hash.hip; the arithmetic both sides share is ibc_hash.h */
+int svt_hip_launch_ibc_block_hashes(hipStream_t st, int pix_bytes, const void* luma, int stride, int width, int height, int block_size, uint32_t* hash1, uint32_t* hash2,
+                                    int8_t* same, void* scratch);
+int svt_hip_launch_ibc_hash_table(hipStream_t st, int pix_bytes, const void* luma, int stride, int width, int height, int32_t* bucket_start, SvtHipIbcHashEntry* entries,
+                                  int64_t capacity, int32_t* info, void* scratch);
+int svt_hip_launch_ibc_hash_search(hipStream_t st, int pix_bytes, int bd, const void* luma, int stride, int width, int height, const int32_t* bucket_start,
+                                   const SvtHipIbcHashEntry* entries, const int32_t* joint_cost, const int32_t* comp_cost, const SvtHipIbcSearchJob* jobs, int njobs,
+                                   SvtHipIbcSearchResult* results);
 /* md_pre.hip */
 int svt_hip_launch_md_fullpel_sad(hipStream_t st, int pix_bytes, const void* src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus, const SvtHipMdPu* pus,
                                   int n_refs, const SvtHipMdRefPlane* refs, const uint32_t* mv, uint32_t* sad);
