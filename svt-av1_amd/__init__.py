@@ -8,8 +8,11 @@ device is present, loading / svt_hip_init fails loudly.
 The directory name contains a '-', so import it through `load_package()` in tests/conftest.py
 (importlib, module name `svt_av1_amd`).
 """
+import collections
 import ctypes as C
 import os
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvtav1_hip.so")
@@ -324,19 +327,28 @@ class PaletteCand(C.Structure):
 PALETTE_MAX_CANDS = 14   # SVT_HIP_PALETTE_MAX_CANDS
 
 
+def default_bd(pix_bytes, bd=None):
+    """The bit depth of a call: `bd` when given, else 8 for one-byte samples and 10 for two-byte samples."""
+    return bd if bd else (8 if pix_bytes == 1 else 10)
+
+
+def _plane_args(plane):
+    assert plane.ndim == 2 and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
+    return plane.itemsize, plane.ctypes.data_as(C.c_void_p), plane.strides[0] // plane.itemsize, plane.shape[1], plane.shape[0]
+
+
 def palette_search_host(plane, jobs, results=None, cands=None, maps=None, bd=None):
     """svt_hip_palette_search_host: `plane` a 2-D uint8 / uint16 luma plane (may be an offset / strided view), `jobs` a ctypes array of PaletteJob.  `results`
     (PaletteResult * njobs), `cands` (PaletteCand * (14 njobs)) and `maps` (uint8 numpy array) are written in place when given, else made here, the maps zeroed
     and as long as the jobs' map_off need.  -> (results, cands, maps)."""
-    import numpy as np
     n = len(jobs)
-    assert plane.ndim == 2 and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
+    pb, p, stride, _, _ = _plane_args(plane)
     results = results if results is not None else (PaletteResult * max(n, 1))()
     cands = cands if cands is not None else (PaletteCand * (PALETTE_MAX_CANDS * max(n, 1)))()
     if maps is None:
         maps = np.zeros(max([j.map_off + PALETTE_MAX_CANDS * j.bw * j.bh for j in jobs if 0 <= j.bw <= 64 and 0 <= j.bh <= 64 and j.map_off >= 0] + [4]), np.uint8)
-    rc = lib().svt_hip_palette_search_host(plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), plane.ctypes.data_as(C.c_void_p), plane.strides[0] // plane.itemsize,
-                                           C.cast(jobs, C.c_void_p), n, C.cast(results, C.c_void_p), C.cast(cands, C.c_void_p), maps.ctypes.data_as(C.c_void_p))
+    rc = lib().svt_hip_palette_search_host(pb, default_bd(pb, bd), p, stride, C.cast(jobs, C.c_void_p), n, C.cast(results, C.c_void_p), C.cast(cands, C.c_void_p),
+                                           maps.ctypes.data_as(C.c_void_p))
     if rc != 0:
         raise RuntimeError(f"svt_hip_palette_search_host refused its arguments: status {rc}")
     return results, cands, maps
@@ -363,22 +375,16 @@ IBC_MV_VALS = 32767          # SVT_HIP_IBC_MV_VALS
 IBC_ENTRY_DTYPE = [("x", "<i2"), ("y", "<i2"), ("hash_value2", "<u4")]   # SvtHipIbcHashEntry as a numpy record
 
 
-def _plane_args(plane):
-    assert plane.ndim == 2 and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
-    return plane.itemsize, plane.ctypes.data_as(C.c_void_p), plane.strides[0] // plane.itemsize, plane.shape[1], plane.shape[0]
-
-
 def ibc_hash_table_host(plane, capacity=None, bd=None):
     """svt_hip_ibc_hash_table_host: `plane` a 2-D uint8 / uint16 luma plane (may be a strided view).  capacity None: svt_hip_ibc_hash_max_entries.
     -> (bucket_start int32[2^19 + 1], entries record array [capacity], info int32[2])."""
-    import numpy as np
     L = lib()
     pb, p, stride, w, h = _plane_args(plane)
     capacity = int(L.svt_hip_ibc_hash_max_entries(w, h)) if capacity is None else capacity
     start, entries, info = np.zeros(IBC_HASH_BUCKETS + 1, np.int32), np.zeros(max(capacity, 1), IBC_ENTRY_DTYPE), np.zeros(2, np.int32)
     nbytes = L.svt_hip_ibc_hash_scratch_bytes(w, h)
     scratch = np.zeros(max(nbytes, 1), np.uint8)
-    rc = L.svt_hip_ibc_hash_table_host(pb, bd or (8 if pb == 1 else 10), p, stride, w, h, start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p), capacity,
+    rc = L.svt_hip_ibc_hash_table_host(pb, default_bd(pb, bd), p, stride, w, h, start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p), capacity,
                                        info.ctypes.data_as(C.c_void_p), scratch.ctypes.data_as(C.c_void_p), nbytes)
     if rc != 0:
         raise RuntimeError(f"svt_hip_ibc_hash_table_host refused its arguments: status {rc}")
@@ -386,7 +392,6 @@ def ibc_hash_table_host(plane, capacity=None, bd=None):
 
 
 def ibc_cost_tables(joint_cost, comp_cost):
-    import numpy as np
     j, c = np.ascontiguousarray(joint_cost, np.int32), np.ascontiguousarray(comp_cost, np.int32)
     assert j.shape == (4,) and c.shape == (2, IBC_MV_VALS)
     return j, c
@@ -397,7 +402,7 @@ def ibc_hash_search_host(plane, bucket_start, entries, joint_cost, comp_cost, jo
     pb, p, stride, w, h = _plane_args(plane)
     j, c = ibc_cost_tables(joint_cost, comp_cost)
     res = (IbcSearchResult * max(len(jobs), 1))()
-    rc = lib().svt_hip_ibc_hash_search_host(pb, bd or (8 if pb == 1 else 10), p, stride, w, h, bucket_start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p),
+    rc = lib().svt_hip_ibc_hash_search_host(pb, default_bd(pb, bd), p, stride, w, h, bucket_start.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p),
                                             j.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.cast(jobs, C.c_void_p), len(jobs), C.cast(res, C.c_void_p))
     if rc != 0:
         raise RuntimeError(f"svt_hip_ibc_hash_search_host refused its arguments: status {rc}")
@@ -427,7 +432,6 @@ def tpl_stats_grid(stats, is_720p_or_larger):
     """result_model_store's replication (EbRateControlProcess.c:148-161): the per-macroblock records `stats` ([mb_rows][mb_cols] structured array) spread over
     the picture's tpl_stats grid: one cell per 16x16 samples at 720p and above (the array as it is), one per 8x8 below (every record in a 2x2 square), i.e.
     [rows][aligned16_width >> shift] with shift = 3 + is_720p_or_larger."""
-    import numpy as np
     rep = 1 if is_720p_or_larger else 2
     return np.repeat(np.repeat(stats, rep, axis=0), rep, axis=1)
 
@@ -466,7 +470,6 @@ def tpl_window_frames(frames):
 
 def tpl_split_out(raw, params):
     """The bytes of d_out -> dict(r0, intra_cost_base, mc_dep_cost_base, factors [mb_rows][mb_cols], beta [sb_rows][sb_cols])."""
-    import numpy as np
     mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
     sbw, sbh = (params.w + params.sb_size - 1) // params.sb_size, (params.h + params.sb_size - 1) // params.sb_size
     raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
@@ -479,7 +482,6 @@ def tpl_split_out(raw, params):
 def tpl_window_host(params, stats, on, ref_windows):
     """svt_hip_tpl_window_host: `stats` one [mb_rows][mb_cols] structured array (TplMbStats fields) per window picture (None allowed for a picture that is
     off, except picture 0), `on` and `ref_windows` per picture.  Returns (the tpl_split_out dict, the grids as [n][rows][cols][2] int64)."""
-    import numpy as np
     L = lib()
     s = 4 - params.cell_log2
     mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
@@ -723,6 +725,65 @@ def lib():
     return _lib
 
 
+Plane = collections.namedtuple("Plane", "d_root ptr stride root view")
+Plane.__doc__ = """An uploaded 2-D plane: device pointer of the whole array, device pointer of the view's sample (0, 0), row stride in samples, the array, the view."""
+
+
+class Scope:
+    """The device memory of one call, `with ctx.scope() as s:`.  Whatever is allocated through `s` is freed when the block ends, normally or by an exception.
+    Memory the caller owns is passed around as a pointer and never registered here; neither is a pointer derived by offset from a registered one."""
+
+    def __init__(self, ctx):
+        self.ctx, self.owned = ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        owned, self.owned = self.owned, []
+        self.ctx.free(*owned)
+
+    def empty(self, nbytes):
+        self.owned.append(self.ctx.empty(nbytes))
+        return self.owned[-1]
+
+    def upload(self, arr):
+        """A numpy array (made contiguous) -> device pointer; max(nbytes, 4) are allocated and nothing is copied when nbytes == 0."""
+        arr = np.ascontiguousarray(arr)
+        return self.ctx._h2d(self.empty(arr.nbytes), arr.ctypes.data_as(C.c_void_p), arr.nbytes)
+
+    def filled(self, shape, value, dtype):
+        return self.upload(np.full(shape, value, dtype))
+
+    def structs(self, arr):
+        """A ctypes array -> device pointer, sized and copied as in upload."""
+        return self.ctx._h2d(self.empty(C.sizeof(arr)), C.cast(arr, C.c_void_p), C.sizeof(arr))
+
+    def plane(self, view):
+        """A 2-D plane that may be an offset / strided view (unit stride along a row) of a C-contiguous array: that array is uploaded whole.  -> Plane"""
+        root = view
+        while isinstance(root.base, np.ndarray):
+            root = root.base
+        assert view.ndim == 2 and root.flags.c_contiguous and view.strides[1] == view.itemsize and view.strides[0] % view.itemsize == 0
+        d = self.upload(root)
+        return Plane(d, C.c_void_p(d.value + view.ctypes.data - root.ctypes.data), view.strides[0] // view.itemsize, root, view)
+
+    def download(self, dptr, shape, dtype):
+        return self.ctx.to_host(dptr, shape, dtype)
+
+    def structs_back(self, dptr, kind):
+        """A fresh ctypes array of type `kind` as the device holds it at dptr (a zero-size one is not copied)."""
+        out = kind()
+        if C.sizeof(out):
+            self.ctx.call("memcpy_d2h", C.cast(out, C.c_void_p), dptr, C.sizeof(out), what="d2h")
+        return out
+
+    def plane_back(self, rec):
+        """The view of `rec` as the device now holds it (a view of a fresh copy of the whole array: what lies around the view comes along)."""
+        host = self.download(rec.d_root, rec.root.shape, rec.root.dtype)
+        return np.ndarray(rec.view.shape, rec.view.dtype, host, rec.view.ctypes.data - rec.root.ctypes.data, rec.view.strides)
+
+
 class Context:
     """RAII wrapper of SvtHipCtx."""
 
@@ -737,26 +798,51 @@ class Context:
         if rc != 0:
             raise RuntimeError(f"{what} failed: status {rc}: {self.L.svt_hip_last_error(self.h).decode()}")
 
+    def call(self, name, *args, what=None):
+        """svt_hip_<name>(ctx, *args), checked; a failure is reported as `what`, by default the name without its _dev suffix."""
+        self.check(getattr(self.L, "svt_hip_" + name)(self.h, *args), what or name.removesuffix("_dev"))
+
+    def sync(self):
+        self.call("sync")
+
+    def scope(self):
+        return Scope(self)
+
+    def timed(self, fn, window_ms, warm=2, reps=2, growth=1.2):
+        """HIP-event time of back-to-back fn() calls: `warm` calls and a synchronisation, then windows of `reps` calls, `reps` growing until a window lasts
+        window_ms; only that last window counts.  -> (ms per call, ms of the window, its reps)"""
+        for _ in range(warm):
+            fn()
+        self.sync()
+        ms = C.c_float()
+        while True:
+            self.L.svt_hip_timer_start(self.h)
+            for _ in range(reps):
+                fn()
+            self.call("timer_stop_ms", C.byref(ms), what="timer")
+            if ms.value >= window_ms:
+                return ms.value / reps, ms.value, reps
+            reps = int(reps * max(2.0, growth * window_ms / max(ms.value, 1e-3)))
+
     # ---- device memory through the C ABI (tests / tools; bench.py uses torch tensors instead)
+    def _h2d(self, dptr, src, nbytes):
+        if nbytes:
+            self.call("memcpy_h2d", dptr, src, nbytes, what="h2d")
+        return dptr
+
     def to_device(self, arr):
-        import numpy as np
         arr = np.ascontiguousarray(arr)
-        p = C.c_void_p()
-        self.check(self.L.svt_hip_malloc(self.h, C.byref(p), max(arr.nbytes, 4)), "malloc")
-        if arr.nbytes:
-            self.check(self.L.svt_hip_memcpy_h2d(self.h, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "h2d")
-        return p
+        return self._h2d(self.empty(arr.nbytes), arr.ctypes.data_as(C.c_void_p), arr.nbytes)
 
     def empty(self, nbytes):
         p = C.c_void_p()
-        self.check(self.L.svt_hip_malloc(self.h, C.byref(p), max(nbytes, 4)), "malloc")
+        self.call("malloc", C.byref(p), max(nbytes, 4))
         return p
 
     def to_host(self, dptr, shape, dtype):
-        import numpy as np
         out = np.empty(shape, dtype)
         if out.nbytes:
-            self.check(self.L.svt_hip_memcpy_d2h(self.h, out.ctypes.data_as(C.c_void_p), dptr, out.nbytes), "d2h")
+            self.call("memcpy_d2h", out.ctypes.data_as(C.c_void_p), dptr, out.nbytes, what="d2h")
         return out
 
     def free(self, *ptrs):
@@ -766,403 +852,261 @@ class Context:
     # ---- intra prediction
     def intra_ois_picture(self, d_src, stride, w, h, mode_end=12):
         """svt_hip_intra_ois_picture_dev on a resident 8-bit luma plane -> (mode [mb_rows][mb_cols] uint8, cost [mb_rows][mb_cols] int32) on the host."""
-        import numpy as np
         mbw, mbh = (w + 15) // 16, (h + 15) // 16
-        d_mode, d_cost = self.empty(mbw * mbh), self.empty(mbw * mbh * 4)
-        try:
-            self.check(self.L.svt_hip_intra_ois_picture_dev(self.h, d_src, stride, w, h, mode_end, d_mode, d_cost), "intra_ois_picture")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_mode, (mbh, mbw), np.uint8), self.to_host(d_cost, (mbh, mbw), np.int32)
-        finally:
-            self.free(d_mode, d_cost)
+        with self.scope() as s:
+            d_mode, d_cost = s.empty(mbw * mbh), s.empty(mbw * mbh * 4)
+            self.call("intra_ois_picture_dev", d_src, stride, w, h, mode_end, d_mode, d_cost)
+            self.sync()
+            return s.download(d_mode, (mbh, mbw), np.uint8), s.download(d_cost, (mbh, mbw), np.int32)
 
     def intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_intra_predict_batch_dev: `edges` a uint8 / uint16 array of edge records, `jobs` a ctypes array of IntraJob, `dst` the 2-D destination plane
         (same dtype) the blocks are written into; `bd` defaults to the dtype's usual depth (8 for uint8, 10 for uint16; uint16 planes may also hold 8-bit samples: bd=8).
         Returns the plane after the launch."""
-        import numpy as np
         pix_bytes = edges.dtype.itemsize
         assert dst.dtype == edges.dtype and dst.ndim == 2
-        d_e, d_j, d_d = self.to_device(edges), self.empty(max(C.sizeof(jobs), 4)), self.to_device(dst)
-        try:
-            if len(jobs):
-                self.check(self.L.svt_hip_memcpy_h2d(self.h, d_j, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
-            self.check(self.L.svt_hip_intra_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), d_e, d_j, len(jobs), d_d, dst.shape[1]),
-                       "intra_predict_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_d, dst.shape, dst.dtype)
-        finally:
-            self.free(d_e, d_j, d_d)
-
-    def _upload_plane(self, plane):
-        """A 2-D plane that may be an offset / strided view (unit stride along a row) of a C-contiguous array: that array is uploaded whole.
-        -> (device pointer of the array, device pointer of the view's sample (0, 0), row stride in samples, the array)."""
-        import numpy as np
-        root = plane
-        while isinstance(root.base, np.ndarray):
-            root = root.base
-        assert plane.ndim == 2 and root.flags.c_contiguous and plane.strides[1] == plane.itemsize and plane.strides[0] % plane.itemsize == 0
-        d = self.to_device(root)
-        return d, C.c_void_p(d.value + plane.ctypes.data - root.ctypes.data), plane.strides[0] // plane.itemsize, root
-
-    def _download_plane(self, d_root, root, plane):
-        """The view `plane` of `root` as the device now holds it (a view of a fresh copy of the whole array: what lies around the view comes along)."""
-        import numpy as np
-        host = self.to_host(d_root, root.shape, root.dtype)
-        off = plane.ctypes.data - root.ctypes.data
-        return np.ndarray(plane.shape, plane.dtype, host, off, plane.strides)
-
-    def _upload_jobs(self, jobs):
-        d = self.empty(max(C.sizeof(jobs), 4))
-        if len(jobs):
-            self.check(self.L.svt_hip_memcpy_h2d(self.h, d, C.cast(jobs, C.c_void_p), C.sizeof(jobs)), "h2d")
-        return d
+        with self.scope() as s:
+            d_e, d_j, d_d = s.upload(edges), s.structs(jobs), s.upload(dst)
+            self.call("intra_predict_batch_dev", pix_bytes, default_bd(pix_bytes, bd), d_e, d_j, len(jobs), d_d, dst.shape[1])
+            self.sync()
+            return s.download(d_d, dst.shape, dst.dtype)
 
     def cfl_predict_batch(self, luma, edges, jobs, cb, cr, want_ac=False, bd=None):
         """svt_hip_cfl_predict_batch_dev: `luma` the 2-D luma plane, `edges` a flat array of edge records, `jobs` a ctypes array of CflJob, `cb` / `cr` the 2-D chroma
         planes (one of them may be None), all uint8 (bd 8) or all uint16 (bd 10 unless `bd` says 8); planes may be offset / strided views, the two chroma planes with one row stride.
         Returns (cb, cr) after the launch -- views like the ones given, None for a plane not given -- and with `want_ac` also the [njobs][32][32] int16 AC
         buffer; `want_ac` may be that buffer's initial content instead of True."""
-        import numpy as np
         pix_bytes = luma.dtype.itemsize
         planes = [p for p in (cb, cr) if p is not None]
         assert planes and all(p.dtype == luma.dtype for p in planes) and edges.dtype == luma.dtype
-        held = []
-        try:
-            d_l, p_l, s_l, _ = self._upload_plane(luma); held.append(d_l)
-            d_e = self.to_device(edges); held.append(d_e)
-            d_j = self._upload_jobs(jobs); held.append(d_j)
-            up = []
-            for p in (cb, cr):
-                up.append(self._upload_plane(p) if p is not None else (None, None, 0, None))
-                if p is not None: held.append(up[-1][0])
-            strides = {u[2] for u in up if u[0] is not None}
+        with self.scope() as s:
+            y, d_e, d_j = s.plane(luma), s.upload(edges), s.structs(jobs)
+            up = [s.plane(p) if p is not None else None for p in (cb, cr)]
+            strides = {u.stride for u in up if u}
             assert len(strides) == 1, "the two chroma planes share one stride"
             d_ac = None
             if want_ac is not False:
                 ac0 = np.zeros((len(jobs), 32, 32), np.int16) if want_ac is True else np.ascontiguousarray(want_ac, np.int16)
                 assert ac0.shape == (len(jobs), 32, 32)
-                d_ac = self.to_device(ac0); held.append(d_ac)
-            self.check(self.L.svt_hip_cfl_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), p_l, s_l, d_e, d_j, len(jobs), up[0][1], up[1][1],
-                                                             strides.pop(), d_ac), "cfl_predict_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out = tuple(self._download_plane(u[0], u[3], p) if p is not None else None for u, p in zip(up, (cb, cr)))
+                d_ac = s.upload(ac0)
+            self.call("cfl_predict_batch_dev", pix_bytes, default_bd(pix_bytes, bd), y.ptr, y.stride, d_e, d_j, len(jobs), up[0] and up[0].ptr, up[1] and up[1].ptr,
+                      strides.pop(), d_ac)
+            self.sync()
+            out = tuple(s.plane_back(u) if u else None for u in up)
             if d_ac is not None:
-                out += (self.to_host(d_ac, ac0.shape, np.int16),)
+                out += (s.download(d_ac, ac0.shape, np.int16),)
             return out
-        finally:
-            self.free(*held)
 
     def palette_search_batch(self, plane, jobs, results, cands, maps, bd=None):
         """svt_hip_palette_search_batch_dev: `plane` a 2-D uint8 / uint16 luma plane (may be an offset / strided view; bd 8 for uint8, 10 for uint16 unless `bd` says
         8), `jobs` a ctypes array of PaletteJob.  `results` (PaletteResult * njobs), `cands` (PaletteCand * (14 njobs)) and `maps` (uint8 numpy array) are the
         initial content of the three outputs.  -> (results, cands, maps) as the device left them, fresh objects of the same types."""
-        import numpy as np
-        held = []
-        try:
-            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
-            d_j = self._upload_jobs(jobs); held.append(d_j)
-            d_r, d_c = self._upload_jobs(results), self._upload_jobs(cands); held += [d_r, d_c]
-            d_m = self.to_device(maps); held.append(d_m)
-            self.check(self.L.svt_hip_palette_search_batch_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, d_j, len(jobs), d_r, d_c, d_m),
-                       "palette_search_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out_r, out_c = type(results)(), type(cands)()
-            if C.sizeof(out_r): self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_r, C.c_void_p), d_r, C.sizeof(out_r)), "d2h")
-            if C.sizeof(out_c): self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_c, C.c_void_p), d_c, C.sizeof(out_c)), "d2h")
-            return out_r, out_c, self.to_host(d_m, maps.shape, np.uint8)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            p, d_j, d_r, d_c, d_m = s.plane(plane), s.structs(jobs), s.structs(results), s.structs(cands), s.upload(maps)
+            self.call("palette_search_batch_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, d_j, len(jobs), d_r, d_c, d_m)
+            self.sync()
+            return s.structs_back(d_r, type(results)), s.structs_back(d_c, type(cands)), s.download(d_m, maps.shape, np.uint8)
 
     def screen_content_detect(self, plane, bd=None, out=None):
         """svt_hip_screen_content_detect_dev: `plane` a 2-D uint8 (bd 8) or uint16 (bd 10) luma plane, may be an offset / strided view.  `out`, if given, is an int32
         array of at least four words, the initial content of the output buffer.  -> that buffer after the call: counts_1, counts_2, color_detection,
         sc_content_detected, then whatever followed."""
-        import numpy as np
         out = np.zeros(4, np.int32) if out is None else np.ascontiguousarray(out, np.int32)
-        held = []
-        try:
-            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
-            d_o = self.to_device(out); held.append(d_o)
-            self.check(self.L.svt_hip_screen_content_detect_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, plane.shape[1], plane.shape[0], d_o),
-                       "screen_content_detect")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_o, out.shape, np.int32)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            p, d_o = s.plane(plane), s.upload(out)
+            self.call("screen_content_detect_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, plane.shape[1], plane.shape[0], d_o)
+            self.sync()
+            return s.download(d_o, out.shape, np.int32)
 
     def ibc_block_hashes(self, plane, block_size, bd=None, fill=0):
         """svt_hip_ibc_block_hashes_dev: `plane` a 2-D uint8 / uint16 luma plane (may be a strided view).  The outputs start filled with the byte `fill`.
         -> (hash1, hash2 uint32[h, w], same int8[3, h, w]); only x < w - block_size + 1, y < h - block_size + 1 is specified."""
-        import numpy as np
         h, w = plane.shape
-        held = []
-        try:
-            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+        with self.scope() as s:
+            p = s.plane(plane)
             nbytes = self.L.svt_hip_ibc_hash_scratch_bytes(w, h)
-            d_s = self.empty(max(nbytes, 256)); held.append(d_s)
-            d_1, d_2 = self.to_device(np.full(w * h * 4, fill, np.uint8)), self.to_device(np.full(w * h * 4, fill, np.uint8)); held += [d_1, d_2]
-            d_m = self.to_device(np.full(3 * w * h, fill, np.uint8)); held.append(d_m)
-            self.check(self.L.svt_hip_ibc_block_hashes_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, block_size, d_1, d_2, d_m, d_s, nbytes),
-                       "ibc_block_hashes")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_1, (h, w), np.uint32), self.to_host(d_2, (h, w), np.uint32), self.to_host(d_m, (3, h, w), np.int8)
-        finally:
-            self.free(*held)
+            d_s = s.empty(max(nbytes, 256))
+            d_1, d_2, d_m = s.filled(w * h * 4, fill, np.uint8), s.filled(w * h * 4, fill, np.uint8), s.filled(3 * w * h, fill, np.uint8)
+            self.call("ibc_block_hashes_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, block_size, d_1, d_2, d_m, d_s, nbytes)
+            self.sync()
+            return s.download(d_1, (h, w), np.uint32), s.download(d_2, (h, w), np.uint32), s.download(d_m, (3, h, w), np.int8)
 
     def ibc_hash_table(self, plane, capacity=None, bd=None, guard=0, fill=0xC3):
         """svt_hip_ibc_hash_table_dev: `plane` a 2-D uint8 / uint16 luma plane.  capacity None: svt_hip_ibc_hash_max_entries.  `guard` bytes of `fill` lie before
         and behind d_bucket_start and d_entries, which start filled with it too.  -> (bucket_start int32[2^19 + 1], entries record array [capacity], info
         int32[2], the four guard areas as uint8 arrays)."""
-        import numpy as np
         h, w = plane.shape
         capacity = int(self.L.svt_hip_ibc_hash_max_entries(w, h)) if capacity is None else capacity
         assert guard % 8 == 0
         nb_s, nb_e = (IBC_HASH_BUCKETS + 1) * 4, capacity * 8
-        held = []
-        try:
-            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
+        with self.scope() as s:
+            p = s.plane(plane)
             nbytes = self.L.svt_hip_ibc_hash_scratch_bytes(w, h)
-            d_s = self.empty(max(nbytes, 256)); held.append(d_s)
-            d_b = self.to_device(np.full(nb_s + 2 * guard, fill, np.uint8)); held.append(d_b)
-            d_e = self.to_device(np.full(nb_e + 2 * guard + 8, fill, np.uint8)); held.append(d_e)
-            d_i = self.to_device(np.full(2, -1, np.int32)); held.append(d_i)
-            self.check(self.L.svt_hip_ibc_hash_table_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, d_b.value + guard, d_e.value + guard,
-                                                         capacity, d_i, d_s, nbytes), "ibc_hash_table")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            b, e = self.to_host(d_b, (nb_s + 2 * guard,), np.uint8), self.to_host(d_e, (nb_e + 2 * guard + 8,), np.uint8)
+            d_s = s.empty(max(nbytes, 256))
+            d_b, d_e = s.filled(nb_s + 2 * guard, fill, np.uint8), s.filled(nb_e + 2 * guard + 8, fill, np.uint8)
+            d_i = s.filled(2, -1, np.int32)
+            self.call("ibc_hash_table_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, d_b.value + guard, d_e.value + guard, capacity, d_i,
+                      d_s, nbytes)
+            self.sync()
+            b, e = s.download(d_b, (nb_s + 2 * guard,), np.uint8), s.download(d_e, (nb_e + 2 * guard + 8,), np.uint8)
             guards = (b[:guard], b[guard + nb_s:], e[:guard], e[guard + nb_e:])
-            return b[guard:guard + nb_s].view(np.int32).copy(), e[guard:guard + nb_e].view(IBC_ENTRY_DTYPE).copy(), self.to_host(d_i, (2,), np.int32), guards
-        finally:
-            self.free(*held)
+            return b[guard:guard + nb_s].view(np.int32).copy(), e[guard:guard + nb_e].view(IBC_ENTRY_DTYPE).copy(), s.download(d_i, (2,), np.int32), guards
 
     def ibc_hash_search_batch(self, plane, bucket_start, entries, joint_cost, comp_cost, jobs, bd=None, fill=0xC3):
         """svt_hip_ibc_hash_search_batch_dev: the table as ibc_hash_table returns it, `jobs` a ctypes array of IbcSearchJob.  -> IbcSearchResult * njobs as the
         device left them (started as the byte `fill`)."""
-        import numpy as np
         h, w = plane.shape
         j, c = ibc_cost_tables(joint_cost, comp_cost)
         res = (IbcSearchResult * max(len(jobs), 1))()
         C.memset(res, fill, C.sizeof(res))
-        held = []
-        try:
-            d_p, p_p, s_p, _ = self._upload_plane(plane); held.append(d_p)
-            d_b = self.to_device(np.ascontiguousarray(bucket_start, np.int32)); held.append(d_b)
-            d_e = self.to_device(np.frombuffer(entries.tobytes() + bytes(8), np.uint8)); held.append(d_e)
-            d_jc, d_cc = self.to_device(j), self.to_device(c); held += [d_jc, d_cc]
-            d_j, d_r = self._upload_jobs(jobs if len(jobs) else (IbcSearchJob * 1)()), self._upload_jobs(res); held += [d_j, d_r]
-            self.check(self.L.svt_hip_ibc_hash_search_batch_dev(self.h, plane.itemsize, bd or (8 if plane.itemsize == 1 else 10), p_p, s_p, w, h, d_b, d_e, d_jc, d_cc, d_j,
-                                                                len(jobs), d_r), "ibc_hash_search_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out = type(res)()
-            self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_r, C.sizeof(out)), "d2h")
-            return out
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            p = s.plane(plane)
+            d_b, d_e = s.upload(np.ascontiguousarray(bucket_start, np.int32)), s.upload(np.frombuffer(entries.tobytes() + bytes(8), np.uint8))
+            d_jc, d_cc = s.upload(j), s.upload(c)
+            d_j, d_r = s.structs(jobs if len(jobs) else (IbcSearchJob * 1)()), s.structs(res)
+            self.call("ibc_hash_search_batch_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, d_b, d_e, d_jc, d_cc, d_j, len(jobs), d_r)
+            self.sync()
+            return s.structs_back(d_r, type(res))
 
     def filter_intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D
         destination plane of the same dtype (may be an offset / strided view); bd 8 for uint8, 10 for uint16 unless `bd` says 8.  Returns the plane after the launch."""
         pix_bytes = edges.dtype.itemsize
         assert dst.dtype == edges.dtype
-        held = []
-        try:
-            d_e = self.to_device(edges); held.append(d_e)
-            d_j = self._upload_jobs(jobs); held.append(d_j)
-            d_d, p_d, s_d, root = self._upload_plane(dst); held.append(d_d)
-            self.check(self.L.svt_hip_filter_intra_predict_batch_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), d_e, d_j, len(jobs), p_d, s_d),
-                       "filter_intra_predict_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self._download_plane(d_d, root, dst)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            d_e, d_j, d = s.upload(edges), s.structs(jobs), s.plane(dst)
+            self.call("filter_intra_predict_batch_dev", pix_bytes, default_bd(pix_bytes, bd), d_e, d_j, len(jobs), d.ptr, d.stride)
+            self.sync()
+            return s.plane_back(d)
 
     # ---- TPL flow dispenser
     def tpl_dispenser_picture(self, params, d_cur, cur_stride, refs, d_mv, d_ref_mask, d_ois_mode, d_ois_cost, d_recon, recon_stride):
         """svt_hip_tpl_dispenser_picture_dev on resident planes and tables: `params` a TplParams, `refs` a sequence of up to 7 TplRef (missing slots unused).
         The reconstruction (border included) stays on the device at d_recon; returns the statistics as a structured numpy array [mb_rows][mb_cols] whose
         fields are TplMbStats'."""
-        import numpy as np
         mbw, mbh = (params.w + 15) // 16, (params.h + 15) // 16
         arr = (TplRef * TPL_MAX_REFS)()
         for i, r in enumerate(refs):
             arr[i] = r
-        d_stats = self.empty(mbw * mbh * C.sizeof(TplMbStats))
-        d_scratch = self.empty(self.L.svt_hip_tpl_dispenser_scratch_bytes(params.w, params.h))
-        try:
-            self.check(self.L.svt_hip_tpl_dispenser_picture_dev(self.h, C.byref(params), d_cur, cur_stride, arr, d_mv, d_ref_mask, d_ois_mode, d_ois_cost,
-                                                                 d_recon, recon_stride, d_stats, d_scratch), "tpl_dispenser_picture")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_stats, (mbh, mbw), np.dtype(TplMbStats))
-        finally:
-            self.free(d_stats, d_scratch)
+        with self.scope() as s:
+            d_stats = s.empty(mbw * mbh * C.sizeof(TplMbStats))
+            d_scratch = s.empty(self.L.svt_hip_tpl_dispenser_scratch_bytes(params.w, params.h))
+            self.call("tpl_dispenser_picture_dev", C.byref(params), d_cur, cur_stride, arr, d_mv, d_ref_mask, d_ois_mode, d_ois_cost, d_recon, recon_stride, d_stats,
+                      d_scratch)
+            self.sync()
+            return s.download(d_stats, (mbh, mbw), np.dtype(TplMbStats))
 
     def tpl_recon_to_host(self, d_recon, recon_stride, w, h, pad):
         """The padded reconstruction tpl_dispenser_picture left at d_recon (sample (0, 0)): [h + 2 pad][w + 2 pad] uint8."""
-        import numpy as np
         out = np.empty((h + 2 * pad, w + 2 * pad), np.uint8)
         top_left = C.c_void_p(d_recon.value - pad * recon_stride - pad)
-        self.check(self.L.svt_hip_memcpy2d_d2h(self.h, out.ctypes.data_as(C.c_void_p), out.shape[1], top_left, recon_stride, out.shape[1], out.shape[0]), "d2h 2d")
+        self.call("memcpy2d_d2h", out.ctypes.data_as(C.c_void_p), out.shape[1], top_left, recon_stride, out.shape[1], out.shape[0], what="d2h 2d")
         return out
 
     # ---- TPL flow synthesizer, r0 / beta / lambda factors
     def tpl_window(self, params, frames, d_out=None, d_scratch=None):
         """svt_hip_tpl_window_dev on resident records and grids: `frames` a TplWindowFrame array (tpl_window_frames) of device pointers.  Every grid stays on
         the device.  Returns the tpl_split_out dict; with the caller's d_out / d_scratch nothing is allocated here."""
-        import numpy as np
         nbytes = self.L.svt_hip_tpl_r0beta_out_bytes(params.w, params.h, params.sb_size)
-        own = [] if d_out is not None else [self.empty(nbytes)]
-        own += [] if d_scratch is not None else [self.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())]
-        o = d_out if d_out is not None else own[0]
-        sc = d_scratch if d_scratch is not None else own[-1]
-        try:
-            self.check(self.L.svt_hip_tpl_window_dev(self.h, C.byref(params), frames, len(frames), o, sc), "tpl_window")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return tpl_split_out(self.to_host(o, (nbytes,), np.uint8), params)
-        finally:
-            self.free(*own)
+        with self.scope() as s:
+            d_out = d_out if d_out is not None else s.empty(nbytes)
+            d_scratch = d_scratch if d_scratch is not None else s.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())
+            self.call("tpl_window_dev", C.byref(params), frames, len(frames), d_out, d_scratch)
+            self.sync()
+            return tpl_split_out(s.download(d_out, (nbytes,), np.uint8), params)
 
     def tpl_synth_picture(self, params, frames, frame_idx):
         """svt_hip_tpl_synth_picture_dev: the scatter of window picture frame_idx into the grids the descriptors name (nothing is zeroed)."""
-        self.check(self.L.svt_hip_tpl_synth_picture_dev(self.h, C.byref(params), frames, len(frames), frame_idx), "tpl_synth_picture")
+        self.call("tpl_synth_picture_dev", C.byref(params), frames, len(frames), frame_idx)
 
     def tpl_r0beta(self, params, d_stats, d_dep):
         """svt_hip_tpl_r0beta_dev on one picture's resident records and grid -> the tpl_split_out dict."""
-        import numpy as np
         nbytes = self.L.svt_hip_tpl_r0beta_out_bytes(params.w, params.h, params.sb_size)
-        d_out, d_scratch = self.empty(nbytes), self.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())
-        try:
-            self.check(self.L.svt_hip_tpl_r0beta_dev(self.h, C.byref(params), d_stats, d_dep, d_out, d_scratch), "tpl_r0beta")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return tpl_split_out(self.to_host(d_out, (nbytes,), np.uint8), params)
-        finally:
-            self.free(d_out, d_scratch)
+        with self.scope() as s:
+            d_out, d_scratch = s.empty(nbytes), s.empty(self.L.svt_hip_tpl_r0beta_scratch_bytes())
+            self.call("tpl_r0beta_dev", C.byref(params), d_stats, d_dep, d_out, d_scratch)
+            self.sync()
+            return tpl_split_out(s.download(d_out, (nbytes,), np.uint8), params)
 
     def tpl_dep_to_host(self, params, d_dep):
         """One picture's grid: [rows][cols][2] int64 = {mc_dep_rate, mc_dep_dist} per cell."""
-        import numpy as np
         s = 4 - params.cell_log2
         return self.to_host(d_dep, (((params.h + 15) // 16) << s, ((params.w + 15) // 16) << s, 2), np.int64)
 
     # ---- global motion
     def gm_shear_params_batch(self, wmmat):
         """svt_hip_gm_shear_params_batch_dev: `wmmat` [n][6] int32 -> a ctypes array of n GmModel."""
-        import numpy as np
         wmmat = np.ascontiguousarray(wmmat, np.int32).reshape(-1, 6)
         n = len(wmmat)
-        d_in, d_out = self.to_device(wmmat), self.empty(n * C.sizeof(GmModel))
-        try:
-            self.check(self.L.svt_hip_gm_shear_params_batch_dev(self.h, d_in, n, d_out), "gm_shear_params_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out = (GmModel * n)()
-            if n:
-                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_out, C.sizeof(out)), "d2h")
-            return out
-        finally:
-            self.free(d_in, d_out)
+        with self.scope() as s:
+            d_in, d_out = s.upload(wmmat), s.empty(n * C.sizeof(GmModel))
+            self.call("gm_shear_params_batch_dev", d_in, n, d_out)
+            self.sync()
+            return s.structs_back(d_out, GmModel * n)
 
     def gm_warp_error_batch(self, src, ref, models):
         """svt_hip_gm_warp_error_batch_dev: `src` / `ref` 2-D uint8 planes (offset / strided views allowed), `models` a ctypes array of GmModel -> int64 [n]."""
-        import numpy as np
-        held = []
-        try:
-            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-            d_r, p_r, s_r, _ = self._upload_plane(ref); held.append(d_r)
-            d_m = self._upload_jobs(models); held.append(d_m)
-            d_e = self.to_device(np.full(max(len(models), 1), -7, np.int64)); held.append(d_e)
-            self.check(self.L.svt_hip_gm_warp_error_batch_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], p_r, ref.shape[1], ref.shape[0], s_r, d_m, len(models), d_e),
-                       "gm_warp_error_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_e, (len(models),), np.int64)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            a, b, d_m = s.plane(src), s.plane(ref), s.structs(models)
+            d_e = s.filled(max(len(models), 1), -7, np.int64)
+            self.call("gm_warp_error_batch_dev", a.ptr, a.stride, src.shape[1], src.shape[0], b.ptr, ref.shape[1], ref.shape[0], b.stride, d_m, len(models), d_e)
+            self.sync()
+            return s.download(d_e, (len(models),), np.int64)
+
+    def _gm_plane_table(self, s, planes, n_tab):
+        tab = (GmRef * n_tab)()
+        for i, r in enumerate(planes):
+            p = s.plane(r)
+            tab[i] = GmRef(p.ptr, r.shape[1], r.shape[0], p.stride, 0)
+        return tab
 
     def gm_frame_error_batch(self, src, refs):
         """svt_hip_gm_frame_error_batch_dev: `src` and each of up to 8 `refs` a 2-D uint8 plane of one size -> int64 [len(refs)]."""
-        import numpy as np
-        held = []
-        try:
-            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-            tab = (GmRef * GM_MAX_REFS)()
-            for i, r in enumerate(refs):
-                d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
-                tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
-            d_e = self.to_device(np.full(max(len(refs), 1), -7, np.int64)); held.append(d_e)
-            self.check(self.L.svt_hip_gm_frame_error_batch_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], tab, len(refs), d_e), "gm_frame_error_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_e, (len(refs),), np.int64)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            a, tab = s.plane(src), self._gm_plane_table(s, refs, GM_MAX_REFS)
+            d_e = s.filled(max(len(refs), 1), -7, np.int64)
+            self.call("gm_frame_error_batch_dev", a.ptr, a.stride, src.shape[1], src.shape[0], tab, len(refs), d_e)
+            self.sync()
+            return s.download(d_e, (len(refs),), np.int64)
 
     def gm_refine_picture(self, src, refs, jobs, repeat=1):
         """svt_hip_gm_refine_picture_dev: `src` a 2-D uint8 plane, `refs` up to 8 such planes (own sizes), `jobs` a ctypes array of GmJob.  `repeat` calls are issued
         back to back on the same scratch and results without a synchronisation of the caller's in between.  -> (ctypes array of GmResult, host polls of the last call)."""
-        held = []
-        try:
-            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-            tab = (GmRef * GM_MAX_REFS)()
-            for i, r in enumerate(refs):
-                d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
-                tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
-            n = len(jobs)
-            d_j = self._upload_jobs(jobs); held.append(d_j)
-            d_o = self.empty(n * C.sizeof(GmResult)); held.append(d_o)
-            d_x = self.empty(self.L.svt_hip_gm_refine_scratch_bytes(n)); held.append(d_x)
+        n = len(jobs)
+        with self.scope() as s:
+            a, tab = s.plane(src), self._gm_plane_table(s, refs, GM_MAX_REFS)
+            d_j, d_o, d_x = s.structs(jobs), s.empty(n * C.sizeof(GmResult)), s.empty(self.L.svt_hip_gm_refine_scratch_bytes(n))
             polls = C.c_int(0)
             for _ in range(repeat):
-                self.check(self.L.svt_hip_gm_refine_picture_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], tab, len(refs), d_j, n, d_o, d_x, C.byref(polls)),
-                           "gm_refine_picture")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out = (GmResult * n)()
-            if n:
-                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out, C.c_void_p), d_o, C.sizeof(out)), "d2h")
-            return out, polls.value
-        finally:
-            self.free(*held)
+                self.call("gm_refine_picture_dev", a.ptr, a.stride, src.shape[1], src.shape[0], tab, len(refs), d_j, n, d_o, d_x, C.byref(polls))
+            self.sync()
+            return s.structs_back(d_o, GmResult * n), polls.value
 
-    def _gm_plane_table(self, planes, held, n_tab):
-        tab = (GmRef * n_tab)()
-        for i, r in enumerate(planes):
-            d_r, p_r, s_r, _ = self._upload_plane(r); held.append(d_r)
-            tab[i] = GmRef(p_r, r.shape[1], r.shape[0], s_r, 0)
-        return tab
-
-    def _gm_corners_dev(self, tab, n, max_points, held):
+    def _gm_corners_dev(self, s, tab, n, max_points):
         """-> device pointers (points [n][max_points][2], counts [n], kept [n]) of svt_hip_gm_corners_batch_dev; nothing is synchronised."""
-        import numpy as np
-        d_p = self.to_device(np.full((n, max_points, 2), -7, np.int32)); held.append(d_p)
-        d_c = self.to_device(np.full(n, -7, np.int32)); held.append(d_c)
-        d_k = self.to_device(np.full(n, -7, np.int32)); held.append(d_k)
-        d_x = self.empty(self.L.svt_hip_gm_corners_scratch_bytes(tab, n)); held.append(d_x)
-        self.check(self.L.svt_hip_gm_corners_batch_dev(self.h, tab, n, max_points, d_p, d_c, d_k, d_x), "gm_corners_batch")
+        d_p, d_c, d_k = s.filled((n, max_points, 2), -7, np.int32), s.filled(n, -7, np.int32), s.filled(n, -7, np.int32)
+        d_x = s.empty(self.L.svt_hip_gm_corners_scratch_bytes(tab, n))
+        self.call("gm_corners_batch_dev", tab, n, max_points, d_p, d_c, d_k, d_x)
         return d_p, d_c, d_k
 
     def gm_corners_batch(self, planes, max_points=GM_MAX_CORNERS):
         """svt_hip_gm_corners_batch_dev: up to 9 2-D uint8 `planes` (own sizes; offset / strided views allowed) -> (list of int32 [count][2] x, y per plane,
         counts int32 [n], kept-before-truncation int32 [n])."""
-        import numpy as np
-        held = []
-        try:
-            n = len(planes)
-            tab = self._gm_plane_table(planes, held, 1 + GM_MAX_REFS)
-            d_p, d_c, d_k = self._gm_corners_dev(tab, n, max_points, held)
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            pts, cnt, kept = self.to_host(d_p, (n, max_points, 2), np.int32), self.to_host(d_c, (n,), np.int32), self.to_host(d_k, (n,), np.int32)
+        n = len(planes)
+        with self.scope() as s:
+            d_p, d_c, d_k = self._gm_corners_dev(s, self._gm_plane_table(s, planes, 1 + GM_MAX_REFS), n, max_points)
+            self.sync()
+            pts, cnt, kept = s.download(d_p, (n, max_points, 2), np.int32), s.download(d_c, (n,), np.int32), s.download(d_k, (n,), np.int32)
             return [pts[i, :max(0, min(int(cnt[i]), max_points))].copy() for i in range(n)], cnt, kept
-        finally:
-            self.free(*held)
 
-    def _scaled_planes(self, planes, shapes, dst, held):
+    def _scaled_planes(self, s, planes, shapes, dst):
         """Uploads 1 .. 3 source planes and their destinations (`dst[i]` a 2-D view to write into, or None / missing for a fresh zeroed plane of shapes[i]); views as
-        in _upload_plane.  -> [(source pointer, source stride, destination pointer, destination stride, device root, host root, destination view)]"""
-        import numpy as np
+        in Scope.plane.  -> [(source Plane, destination Plane)]"""
         out = []
         for i, (src, shape) in enumerate(zip(planes, shapes)):
             d = dst[i] if dst is not None and dst[i] is not None else np.zeros(shape, src.dtype)
             assert d.shape == tuple(shape) and d.dtype == src.dtype == planes[0].dtype and src.dtype in (np.uint8, np.uint16)
-            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-            d_d, p_d, s_d, root = self._upload_plane(d); held.append(d_d)
-            out.append((p_s, s_s, p_d, s_d, d_d, root, d))
+            out.append((s.plane(src), s.plane(d)))
         return out
 
     def superres_upscale_planes(self, planes, out_widths, dst=None, bd=None):
@@ -1170,74 +1114,57 @@ class Context:
         entry of `out_widths`; planes and the optional destinations `dst` may be offset / strided views.  -> the upscaled planes, each a view (like the one
         given) of a fresh copy of the whole destination array, so what lies around the plane can be checked through `.base`."""
         pix_bytes = planes[0].dtype.itemsize
-        held = []
-        try:
-            recs = self._scaled_planes(planes, [(p.shape[0], w) for p, w in zip(planes, out_widths)], dst, held)
-            tab = (UpscalePlane * len(recs))(*[UpscalePlane(r[0], r[1], p.shape[1], r[2], r[3], w, p.shape[0]) for r, p, w in zip(recs, planes, out_widths)])
-            self.check(self.L.svt_hip_superres_upscale_planes_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), tab, len(recs)), "superres_upscale_planes")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return [self._download_plane(r[4], r[5], r[6]) for r in recs]
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            recs = self._scaled_planes(s, planes, [(p.shape[0], w) for p, w in zip(planes, out_widths)], dst)
+            tab = (UpscalePlane * len(recs))(*[UpscalePlane(a.ptr, a.stride, p.shape[1], b.ptr, b.stride, w, p.shape[0]) for (a, b), p, w in zip(recs, planes, out_widths)])
+            self.call("superres_upscale_planes_dev", pix_bytes, default_bd(pix_bytes, bd), tab, len(recs))
+            self.sync()
+            return [s.plane_back(b) for _, b in recs]
 
     def resize_planes(self, planes, out_shapes, dst=None, bd=None, scratch=None):
         """svt_hip_resize_planes_dev: 1 .. 3 2-D `planes` (dtypes, views and `dst` as in superres_upscale_planes), each scaled to its (height, width) of
         `out_shapes`.  `scratch`, if given, is a uint8 array of at least svt_hip_resize_scratch_bytes that is used as the call's scratch and receives what
         the device left in it.  -> the scaled planes, as superres_upscale_planes returns them."""
-        import numpy as np
         pix_bytes = planes[0].dtype.itemsize
-        held = []
-        try:
-            recs = self._scaled_planes(planes, out_shapes, dst, held)
-            tab = (ResizePlane * len(recs))(*[ResizePlane(r[0], r[1], p.shape[1], p.shape[0], r[2], r[3], s[1], s[0]) for r, p, s in zip(recs, planes, out_shapes)])
+        with self.scope() as s:
+            recs = self._scaled_planes(s, planes, out_shapes, dst)
+            tab = (ResizePlane * len(recs))(*[ResizePlane(a.ptr, a.stride, p.shape[1], p.shape[0], b.ptr, b.stride, o[1], o[0])
+                                              for (a, b), p, o in zip(recs, planes, out_shapes)])
             need = self.L.svt_hip_resize_scratch_bytes(pix_bytes, tab, len(recs))
-            d_x = self.to_device(scratch) if scratch is not None else self.empty(need); held.append(d_x)
-            self.check(self.L.svt_hip_resize_planes_dev(self.h, pix_bytes, bd or (8 if pix_bytes == 1 else 10), tab, len(recs), d_x,
-                                                        scratch.nbytes if scratch is not None else need), "resize_planes")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
+            d_x = s.upload(scratch) if scratch is not None else s.empty(need)
+            self.call("resize_planes_dev", pix_bytes, default_bd(pix_bytes, bd), tab, len(recs), d_x, scratch.nbytes if scratch is not None else need)
+            self.sync()
             if scratch is not None:
-                scratch[...] = self.to_host(d_x, scratch.shape, np.uint8)
-            return [self._download_plane(r[4], r[5], r[6]) for r in recs]
-        finally:
-            self.free(*held)
+                scratch[...] = s.download(d_x, scratch.shape, np.uint8)
+            return [s.plane_back(b) for _, b in recs]
 
     def gm_cross_correlation_batch(self, im1, im2, pairs):
         """svt_hip_gm_cross_correlation_batch_dev: `im1` / `im2` 2-D uint8 planes of one size, `pairs` [n][4] int32 x1, y1, x2, y2 -> float64 [n]."""
-        import numpy as np
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 4)
         assert im1.shape == im2.shape
-        held = []
-        try:
-            d_a, p_a, s_a, _ = self._upload_plane(im1); held.append(d_a)
-            d_b, p_b, s_b, _ = self._upload_plane(im2); held.append(d_b)
-            d_q = self.to_device(pairs); held.append(d_q)
-            d_o = self.to_device(np.full(max(len(pairs), 1), -7.0, np.float64)); held.append(d_o)
-            self.check(self.L.svt_hip_gm_cross_correlation_batch_dev(self.h, p_a, s_a, p_b, s_b, im1.shape[1], im1.shape[0], d_q, len(pairs), d_o),
-                       "gm_cross_correlation_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            return self.to_host(d_o, (len(pairs),), np.float64)
-        finally:
-            self.free(*held)
+        with self.scope() as s:
+            a, b, d_q = s.plane(im1), s.plane(im2), s.upload(pairs)
+            d_o = s.filled(max(len(pairs), 1), -7.0, np.float64)
+            self.call("gm_cross_correlation_batch_dev", a.ptr, a.stride, b.ptr, b.stride, im1.shape[1], im1.shape[0], d_q, len(pairs), d_o)
+            self.sync()
+            return s.download(d_o, (len(pairs),), np.float64)
 
     def gm_correspondences_batch(self, src, refs, src_points=None, ref_points=None, max_points=GM_MAX_CORNERS):
         """svt_hip_gm_correspondences_batch_dev: `src` and up to 8 `refs` 2-D uint8 planes (the references are read at the source's size), `src_points` an int32
         [n][2] list and `ref_points` one such list per reference -> list of int32 [ncorr][4] x, y, rx, ry per reference.  With both lists None the corners come
         from svt_hip_gm_corners_batch_dev on the same stream and stay on the device in between."""
-        import numpy as np
-        held = []
-        try:
-            h, w = src.shape
-            n = len(refs)
+        h, w = src.shape
+        n = len(refs)
+        with self.scope() as s:
             if src_points is None and ref_points is None:
-                tab = self._gm_plane_table([src] + list(refs), held, 1 + GM_MAX_REFS)
-                d_p, d_c, _ = self._gm_corners_dev(tab, n + 1, max_points, held)
+                tab = self._gm_plane_table(s, [src] + list(refs), 1 + GM_MAX_REFS)
+                d_sp, d_sc, _ = self._gm_corners_dev(s, tab, n + 1, max_points)
                 p_s, s_s = tab[0].d_plane, tab[0].stride
                 rtab = (GmRef * GM_MAX_REFS)(*[tab[i + 1] for i in range(n)])
-                d_sp, d_sc = d_p, d_c
-                d_rp, d_rc = C.c_void_p(d_p.value + max_points * 8), C.c_void_p(d_c.value + 4)
+                d_rp, d_rc = C.c_void_p(d_sp.value + max_points * 8), C.c_void_p(d_sc.value + 4)   # the references' lists follow the source's
             else:
-                d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-                rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
+                a, rtab = s.plane(src), self._gm_plane_table(s, refs, GM_MAX_REFS)
+                p_s, s_s = a.ptr, a.stride
                 sp = np.ascontiguousarray(src_points, np.int32).reshape(-1, 2)
                 assert len(sp) <= max_points and len(ref_points) == n
                 rp = np.full((max(n, 1), max_points, 2), -7, np.int32)
@@ -1245,83 +1172,57 @@ class Context:
                 for i, q in enumerate(ref_points):
                     q = np.ascontiguousarray(q, np.int32).reshape(-1, 2)
                     rp[i, :len(q)] = q; rc[i] = len(q)
-                d_sp = self.to_device(sp); held.append(d_sp)
-                d_sc = self.to_device(np.array([len(sp)], np.int32)); held.append(d_sc)
-                d_rp = self.to_device(rp); held.append(d_rp)
-                d_rc = self.to_device(rc); held.append(d_rc)
-            d_o = self.to_device(np.full((max(n, 1), max_points, 4), -7, np.int32)); held.append(d_o)
-            d_n = self.to_device(np.full(max(n, 1), -7, np.int32)); held.append(d_n)
-            self.check(self.L.svt_hip_gm_correspondences_batch_dev(self.h, p_s, s_s, w, h, d_sp, d_sc, rtab, n, d_rp, d_rc, max_points, d_o, d_n),
-                       "gm_correspondences_batch")
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            out, cnt = self.to_host(d_o, (max(n, 1), max_points, 4), np.int32), self.to_host(d_n, (max(n, 1),), np.int32)
+                d_sp, d_sc, d_rp, d_rc = s.upload(sp), s.upload(np.array([len(sp)], np.int32)), s.upload(rp), s.upload(rc)
+            d_o, d_n = s.filled((max(n, 1), max_points, 4), -7, np.int32), s.filled(max(n, 1), -7, np.int32)
+            self.call("gm_correspondences_batch_dev", p_s, s_s, w, h, d_sp, d_sc, rtab, n, d_rp, d_rc, max_points, d_o, d_n)
+            self.sync()
+            out, cnt = s.download(d_o, (max(n, 1), max_points, 4), np.int32), s.download(d_n, (max(n, 1),), np.int32)
             assert all(0 <= int(c) <= max_points for c in cnt[:n])
             return [out[i, :int(cnt[i])].copy() for i in range(n)]
-        finally:
-            self.free(*held)
 
     def gm_fit_batch(self, corr, counts, jobs, n_refinements=5, want_inliers=True, want_jobs=True, repeat=1, refine=None, num_motions=1):
         """svt_hip_gm_fit_batch_dev: `corr` int32 [n_lists][max_points][4] and `counts` int32 [n_lists] as the correspondence call leaves them, `jobs` a list of
         (list index, model type).  `repeat` calls are issued back to back on the same scratch.  refine = (src, refs): svt_hip_gm_refine_picture_dev then runs on
         the jobs the fit wrote, without leaving the device.  -> (ctypes array of GmFit, int32 [njobs][max_points] inlier indices or None, ctypes array of GmJob or
         None, ctypes array of GmResult or None)."""
-        import numpy as np
         corr = np.ascontiguousarray(corr, np.int32)
         counts = np.ascontiguousarray(counts, np.int32)
         n_lists, max_points = corr.shape[0], corr.shape[1]
         n = len(jobs)
         tab = (GmFitJob * max(n, 1))(*[GmFitJob(r, t) for r, t in jobs])
-        held = []
-        try:
-            d_c = self.to_device(corr); held.append(d_c)
-            d_n = self.to_device(counts); held.append(d_n)
-            d_f = self.to_device(np.full(max(n, 1) * C.sizeof(GmFit), 0xA5, np.uint8)); held.append(d_f)
-            d_i = d_j = None
-            if want_inliers:
-                d_i = self.to_device(np.full((max(n, 1), max_points), -7, np.int32)); held.append(d_i)
-            if want_jobs or refine:
-                d_j = self.to_device(np.full(max(n, 1) * C.sizeof(GmJob), 0xA5, np.uint8)); held.append(d_j)
-            d_x = self.empty(max(self.L.svt_hip_gm_fit_scratch_bytes(n, max_points), 8)); held.append(d_x)
+        with self.scope() as s:
+            d_c, d_n = s.upload(corr), s.upload(counts)
+            d_f = s.filled(max(n, 1) * C.sizeof(GmFit), 0xA5, np.uint8)
+            d_i = s.filled((max(n, 1), max_points), -7, np.int32) if want_inliers else None
+            d_j = s.filled(max(n, 1) * C.sizeof(GmJob), 0xA5, np.uint8) if want_jobs or refine else None
+            d_x = s.empty(max(self.L.svt_hip_gm_fit_scratch_bytes(n, max_points), 8))
             for _ in range(repeat):
-                self.check(self.L.svt_hip_gm_fit_batch_dev(self.h, d_c, d_n, n_lists, max_points, tab, n, num_motions, n_refinements, d_f, d_i, d_j, d_x), "gm_fit_batch")
-            res = None
+                self.call("gm_fit_batch_dev", d_c, d_n, n_lists, max_points, tab, n, num_motions, n_refinements, d_f, d_i, d_j, d_x)
+            d_o = None
             if refine and n:
                 src, refs = refine
-                d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-                rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
-                d_o = self.empty(n * C.sizeof(GmResult)); held.append(d_o)
-                d_y = self.empty(self.L.svt_hip_gm_refine_scratch_bytes(n)); held.append(d_y)
-                self.check(self.L.svt_hip_gm_refine_picture_dev(self.h, p_s, s_s, src.shape[1], src.shape[0], rtab, len(refs), d_j, n, d_o, d_y, None), "gm_refine_picture")
-                res = (GmResult * n)()
-            self.check(self.L.svt_hip_sync(self.h), "sync")
-            fits, out_jobs = (GmFit * n)(), (GmJob * n)() if d_j else None
-            if n:
-                self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(fits, C.c_void_p), d_f, C.sizeof(fits)), "d2h")
-                if d_j:
-                    self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(out_jobs, C.c_void_p), d_j, C.sizeof(out_jobs)), "d2h")
-                if res is not None:
-                    self.check(self.L.svt_hip_memcpy_d2h(self.h, C.cast(res, C.c_void_p), d_o, C.sizeof(res)), "d2h")
-            inl = self.to_host(d_i, (max(n, 1), max_points), np.int32)[:n] if d_i else None
+                a, rtab = s.plane(src), self._gm_plane_table(s, refs, GM_MAX_REFS)
+                d_o, d_y = s.empty(n * C.sizeof(GmResult)), s.empty(self.L.svt_hip_gm_refine_scratch_bytes(n))
+                self.call("gm_refine_picture_dev", a.ptr, a.stride, src.shape[1], src.shape[0], rtab, len(refs), d_j, n, d_o, d_y, None)
+            self.sync()
+            fits = s.structs_back(d_f, GmFit * n)
+            out_jobs = s.structs_back(d_j, GmJob * n) if d_j else None
+            res = s.structs_back(d_o, GmResult * n) if d_o else None
+            inl = s.download(d_i, (max(n, 1), max_points), np.int32)[:n] if d_i else None
             return fits, inl, out_jobs, res
-        finally:
-            self.free(*held)
 
     def gm_estimate_picture(self, src, refs, rotzoom_model_only=0, allow_high_precision_mv=0, n_refinements=5, max_points=GM_MAX_CORNERS, repeat=1):
         """svt_hip_gm_estimate_picture_dev: `src` a 2-D uint8 plane, `refs` up to 8 such planes at least as large (offset / strided views allowed); `repeat` calls
         on the same scratch -> ctypes array of GmEstimate, one per reference (of the last call)."""
-        held = []
-        try:
-            h, w = src.shape
-            d_s, p_s, s_s, _ = self._upload_plane(src); held.append(d_s)
-            rtab = self._gm_plane_table(refs, held, GM_MAX_REFS)
+        h, w = src.shape
+        with self.scope() as s:
+            a, rtab = s.plane(src), self._gm_plane_table(s, refs, GM_MAX_REFS)
             opt = GmEstimateOptions(rotzoom_model_only, allow_high_precision_mv, n_refinements, max_points)
-            d_x = self.empty(max(self.L.svt_hip_gm_estimate_scratch_bytes(w, h, len(refs), C.byref(opt)), 256)); held.append(d_x)
+            d_x = s.empty(max(self.L.svt_hip_gm_estimate_scratch_bytes(w, h, len(refs), C.byref(opt)), 256))
             out = (GmEstimate * max(len(refs), 1))()
             for _ in range(repeat):
-                self.check(self.L.svt_hip_gm_estimate_picture_dev(self.h, p_s, s_s, w, h, rtab, len(refs), C.byref(opt), out, d_x), "gm_estimate_picture")
+                self.call("gm_estimate_picture_dev", a.ptr, a.stride, w, h, rtab, len(refs), C.byref(opt), out, d_x)
             return out
-        finally:
-            self.free(*held)
 
     def close(self):
         if self.h:
@@ -1333,3 +1234,4 @@ class Context:
             self.close()
         except Exception:
             pass
+

@@ -121,15 +121,10 @@ def mixed_frame(w, h):
 
 def device_ois(hip, plane, w, h, mode_end=12):
     """The product on the same samples: `plane` may be a strided / offset view; its base array is uploaded whole and the view's address handed over."""
-    root = plane
-    while isinstance(root.base, np.ndarray): root = root.base
-    assert root.flags.c_contiguous and plane.strides[1] == 1
-    off = plane.ctypes.data - root.ctypes.data
-    d = hip.to_device(root)
-    try:
-        return hip.intra_ois_picture(C.c_void_p(d.value + off), plane.strides[0], w, h, mode_end)
-    finally:
-        hip.free(d)
+    assert plane.dtype == np.uint8
+    with hip.scope() as s:
+        p = s.plane(plane)
+        return hip.intra_ois_picture(p.ptr, p.stride, w, h, mode_end)
 
 
 # ---------------------------------------------------------------------------------------------------- predictor batch: the reference side

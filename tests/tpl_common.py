@@ -337,14 +337,12 @@ def device_dispenser(hip, pkg, case, ois_mode, ois_cost, qp, use_ois=1, add_resi
     extra_stride / offset put every plane into a wider buffer at a byte offset (odd strides, unaligned bases).  d_ois = (d_mode, d_cost) uses tables already
     on the device.  calls > 1 repeats the call on a fresh destination and asserts identical bytes."""
     w, h = case["w"], case["h"]
-    held = []
 
     def up(arr, es, off):
         buf, stride, o = _place(arr, es, off)
-        d = hip.to_device(buf); held.append(d)
-        return d, stride, o
+        return s.upload(buf), stride, o
 
-    try:
+    with hip.scope() as s:
         d_cur, cs, co = up(case["cur"], extra_stride, offset)
         origin = lambda d, stride, o: C.c_void_p(d.value + o + PAD * stride + PAD)
         refs = [pkg.TplRef() for _ in range(N_SLOTS)]
@@ -359,13 +357,12 @@ def device_dispenser(hip, pkg, case, ois_mode, ois_cost, qp, use_ois=1, add_resi
                 dr, rs, ro = up(rp, extra_stride, offset + (1 if offset else 0))
                 refs[r].d_rec, refs[r].rec_stride = origin(dr, rs, ro).value, rs
         any_ref = any(x is not None for x in case["refs"])
-        d_mv = hip.to_device(case["mv"]) if any_ref else None
-        d_mask = hip.to_device(case["mask"]) if any_ref else None
-        held.extend(x for x in (d_mv, d_mask) if x is not None)
+        d_mv = s.upload(case["mv"]) if any_ref else None
+        d_mask = s.upload(case["mask"]) if any_ref else None
         if d_ois is not None:
             d_mode, d_cost = d_ois
         elif use_ois or ois_mode is not None:
-            d_mode, d_cost = hip.to_device(ois_mode.astype(np.uint8)), hip.to_device(ois_cost.astype(np.int32)); held.extend((d_mode, d_cost))
+            d_mode, d_cost = s.upload(ois_mode.astype(np.uint8)), s.upload(ois_cost.astype(np.int32))
         else:
             d_mode = d_cost = None
         P = pkg.TplParams()
@@ -375,7 +372,7 @@ def device_dispenser(hip, pkg, case, ois_mode, ois_cost, qp, use_ois=1, add_resi
         result = None
         for _ in range(calls):
             host, rs, ro = _place(np.full((rh, rw), MARK, np.uint8), extra_stride + (5 if extra_stride else 0), offset)
-            d_rec = hip.to_device(host); held.append(d_rec)
+            d_rec = s.upload(host)
             d_recon = C.c_void_p(d_rec.value + ro + (pad + GUARD) * rs + pad + GUARD)
             stats = hip.tpl_dispenser_picture(P, origin(d_cur, cs, co), cs, refs, d_mv, d_mask, d_mode, d_cost, d_recon, rs)
             whole = hip.to_host(d_rec, (host.size,), np.uint8)
@@ -389,8 +386,6 @@ def device_dispenser(hip, pkg, case, ois_mode, ois_cost, qp, use_ois=1, add_resi
                 assert stats_equal(got[0], result[0]) and (got[1] == result[1]).all(), "two calls on the same inputs differ"
             result = got
         return result
-    finally:
-        hip.free(*held)
 
 
 def compare(dev_stats, dev_recon, ref_stats, ref_recon, pad=PAD):

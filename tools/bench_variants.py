@@ -27,18 +27,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 
 
-def timed(torch, stream, fn, reps):
-    fn(); fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(reps):
-        fn()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
 def setup():
     import torch
     from conftest import load_package
@@ -55,6 +43,7 @@ def setup():
     E.ctx.check(E.L.svt_hip_set_stream(E.ctx.h, C.c_void_p(stream.cuda_stream)))
     E.dev = torch.device("cuda", 0)
     E.ctx.check(E.L.svt_hip_me_set_big_windows(E.ctx.h, 0))
+    E.ms_per_call = lambda fn, reps: E.ctx.timed(fn, 0, reps=reps)[0]   # two warm calls, then ONE window of exactly `reps` calls on the stream set above
     return torch, bench, E, stream
 
 
@@ -72,7 +61,7 @@ def config1(reps):
             for name, sub in (("FULL_SAD_SEARCH", 0), ("SUB_SAD_SEARCH", 1)):
                 fn = lambda sub=sub: E.ctx.check(E.L.svt_hip_me_fullpel_frame_dev(E.ctx.h, P.d_cur_p.data_ptr(), P.d_ref_p.data_ptr(), F.cur_y_p.shape[1], F.pad, F.pad,
                                                                                    P.d_sbs.data_ptr(), P.n_sb, sub, P.d_sad.data_ptr(), P.d_mv.data_ptr()), "me")
-                ms = timed(torch, stream, fn, reps)
+                ms = E.ms_per_call(fn, reps)
                 out["me"][name] = {"ms": ms, "sb_per_s": n_sb / (ms * 1e-3)}
             P.run_me(); P.run_subpel()   # the prediction the transform chain codes against
         else:
@@ -88,7 +77,7 @@ def config1(reps):
                     for c in range(2):
                         EJ[i].fwd.qp.round[c] = int(qp[5][c]); EJ[i].fwd.qp.quant[c] = int(qp[6][c])
             fn = lambda EJ=EJ: E.ctx.check(E.L.svt_hip_enc_txfm_multi_dev(E.ctx.h, 1, 8, EJ, len(keep)), "enc txfm")
-            ms = timed(torch, stream, fn, reps)
+            ms = E.ms_per_call(fn, reps)
             nblk = sum(P.tx_jobs[k]["n"] for k in keep)
             out["txfm_chain"].setdefault(vname, {})[f"qindex_{q}"] = {"ms": ms, "blocks": nblk, "sb_per_s": n_sb / (ms * 1e-3)}
         del P
@@ -141,7 +130,7 @@ def config2(reps):
     def probes_two_launches():   # round 4's form: every prediction written to HBM by one launch and read back by the next
         ctx.check(L.svt_hip_upsampled_pred_batch_dev(ctx.h, d_ref.data_ptr(), st, d_pred.data_ptr(), d_jobs.data_ptr(), 8 * nblk), "upsampled pred")
         ctx.check(L.svt_hip_block_variance_batch_dev(ctx.h, 1, 8, d_pred.data_ptr(), 16, d_cur.data_ptr(), W, d_pairs.data_ptr(), 8 * nblk, d_var.data_ptr(), d_sse.data_ptr()), "variance")
-    ms_two = timed(torch, stream, probes_two_launches, reps)
+    ms_two = E.ms_per_call(probes_two_launches, reps)
     v2, s2 = d_var.cpu().numpy().view(np.uint32).copy(), d_sse.cpu().numpy().view(np.uint32).copy()
     # the fused form: one workgroup per block stages the window once, the nine half-pel positions' predictions never leave the chip (svt_hip_md_halfpel_grid_picture_dev)
     sb_cols, sb_rows = (W + 63) // 64, (H + 63) // 64
@@ -159,7 +148,7 @@ def config2(reps):
 
     def probes():
         ctx.check(L.svt_hip_md_halfpel_grid_picture_dev(ctx.h, d_cur.data_ptr(), W, W, H, sb_cols, sb_rows * sb_cols, 16, pus16, 1, planes, d_mvtab.data_ptr(), 0, d_grid.data_ptr()), "half-pel grid")
-    ms = timed(torch, stream, probes, reps)
+    ms = E.ms_per_call(probes, reps)
     alg = nblk * (25 * 25 + 256 + 8 * 8)   # per block: the (16 + 8 + 1)^2 window its eight probes share + the source block, read once; 8 x (variance, sse) out
     out["upsampled_pred_variance_8_neighbours"] = {"ms": ms, "candidates": 8 * nblk, "algorithmic_bytes": alg, "algorithmic_GBps": alg / (ms * 1e-3) / 1e9, "hbm_frac": alg / (ms * 1e-3) / HBM,
                                                    "sb_per_s": n_sb / (ms * 1e-3), "traffic_bytes": None, "launches": 1, "two_launch_form_ms": ms_two,
@@ -182,7 +171,7 @@ def config2(reps):
         d_cb = T(np.frombuffer(bytes(CB), np.uint8).copy())
         off = PAD * st + PAD
         fn = lambda d_cb=d_cb: ctx.check(L.svt_hip_subpel_predict_batch_dev(ctx.h, 1, 8, d_ref.data_ptr() + off, st, d_dst.data_ptr(), W, d_cb.data_ptr(), nblk), "convolve")
-        ms = timed(torch, stream, fn, reps)
+        ms = E.ms_per_call(fn, reps)
         alg = nblk * alg_blk
         conv[name] = {"ms": ms, "algorithmic_bytes": alg, "algorithmic_GBps": alg / (ms * 1e-3) / 1e9, "hbm_frac": alg / (ms * 1e-3) / HBM, "sb_per_s": n_sb / (ms * 1e-3), "traffic_bytes": None}
         conv_out[name] = (d_dst.cpu().numpy().copy(), np.frombuffer(bytes(CB), np.uint8).copy())
@@ -245,7 +234,7 @@ def hbd(reps):
             S[k] = pkg.SadLoop(bx + PAD, by + PAD, bx + PAD - 32, by + PAD - 32, 64, bh, 64, 64, 1, 0); k += 1
     d_S = T(np.frombuffer(bytes(S), np.uint8).copy())
     d_bs = torch.zeros(n_sb, dtype=torch.int32, device=E.dev); d_bxy = torch.zeros((n_sb, 2), dtype=torch.int16, device=E.dev)
-    out["stages_ms"]["hbd_sad_window_64x64"] = timed(torch, stream, lambda: ctx.check(L.svt_hip_sad_loop16_batch_dev(ctx.h, d_curp.data_ptr(), st, d_refp.data_ptr(), st, d_S.data_ptr(), n_sb,
+    out["stages_ms"]["hbd_sad_window_64x64"] = E.ms_per_call(lambda: ctx.check(L.svt_hip_sad_loop16_batch_dev(ctx.h, d_curp.data_ptr(), st, d_refp.data_ptr(), st, d_S.data_ptr(), n_sb,
                                                                                                                       d_bs.data_ptr(), d_bxy.data_ptr()), "sad16 loop"), max(2, reps // 2))
     # (2) HBD SAD + highbd_10 variance of every whole 64x64 and its four 32x32
     pairs = []
@@ -262,7 +251,7 @@ def hbd(reps):
     def sadvar():
         ctx.check(L.svt_hip_block_sad_batch_dev(ctx.h, 2, d_cur.data_ptr(), W, d_ref.data_ptr(), W + 8, d_p.data_ptr(), len(pairs), d_o[0].data_ptr()), "sad16")
         ctx.check(L.svt_hip_block_variance_batch_dev(ctx.h, 2, BD, d_cur.data_ptr(), W, d_ref.data_ptr(), W + 8, d_p.data_ptr(), len(pairs), d_o[1].data_ptr(), d_o[2].data_ptr()), "var10")
-    out["stages_ms"]["hbd_sad_variance_64x64_32x32"] = timed(torch, stream, sadvar, reps)
+    out["stages_ms"]["hbd_sad_variance_64x64_32x32"] = E.ms_per_call(sadvar, reps)
     # (3) the 64-point transform chain of the whole luma plane, five sizes, both high-bit-depth quantizers
     g = np.load(os.path.join(ROOT, "tests", "golden", "txfm_tables.npz"))
     qp = g["qp/10/60/0"]
@@ -283,7 +272,7 @@ def hbd(reps):
             EJ = (pkg.EncTxJob * 1)()
             EJ[0].fwd = pkg.FwdTxJob(ts, len(descs), d_cur.data_ptr(), W, d_prd.data_ptr(), W, d_desc.data_ptr(), qs, stt, None, d_q.data_ptr(), None, d_eob.data_ptr(), None, None)
             EJ[0].d_recon = d_rec.data_ptr(); EJ[0].recon_stride = W
-            ms = timed(torch, stream, lambda EJ=EJ: ctx.check(L.svt_hip_enc_txfm_multi_dev(ctx.h, 2, BD, EJ, 1), "enc txfm 10"), reps)
+            ms = E.ms_per_call(lambda EJ=EJ: ctx.check(L.svt_hip_enc_txfm_multi_dev(ctx.h, 2, BD, EJ, 1), "enc txfm 10"), reps)
             out["stages_ms"][f"txfm_chain_{tw}x{th}_{vname}"] = ms
     # (4) the complete self-guided unit search of the three planes (16 sets) + apply with the sets it chose
     EXT, US = 3, [256, 256, 256]
@@ -316,8 +305,8 @@ def hbd(reps):
             ph_, pw_ = planes_rec[p].shape
             ctx.check(L.svt_hip_sgr_apply_plane_dev(ctx.h, 2, BD, org(b_cdef, p), xs[p], org(b_rest, p), xs[p], pw_, ph_, US[p], int(p > 0), d_dbl[p].data_ptr(), pw_, d_ubest[p].data_ptr(),
                                                     d_ubx[p].data_ptr()), "sgr apply 10")
-    out["stages_ms"]["sgr_units_search"] = timed(torch, stream, sgr_units, reps)
-    out["stages_ms"]["sgr_apply"] = timed(torch, stream, sgr_apply, reps)
+    out["stages_ms"]["sgr_units_search"] = E.ms_per_call(sgr_units, reps)
+    out["stages_ms"]["sgr_apply"] = E.ms_per_call(sgr_apply, reps)
     unfinished = int(sum(int(d_scr[p][:128].cpu().numpy().view(np.uint32)[2]) for p in range(3)))
     chain = ["hbd_sad_window_64x64", "hbd_sad_variance_64x64_32x32", "txfm_chain_64x64_highbd_quantize_b", "sgr_units_search", "sgr_apply"]
     total = sum(out["stages_ms"][k] for k in chain)

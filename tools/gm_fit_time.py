@@ -31,24 +31,11 @@ hip = pkg.Context(0)
 L = hip.L
 cref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsvtav1_ref.so"))
 cref.setup_common_rtcd_internal(0); cref.setup_rtcd_internal(0)
-ms = C.c_float()
+per_call = lambda fn: hip.timed(fn, args.window)[0]
 ONE = g.ONE
 TRUTH = (3 * ONE + 8192, -2 * ONE - 4096, ONE + 160, 96, -96, ONE + 160)
 MAXP = pkg.GM_MAX_CORNERS
 N_REF = 5
-
-
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps
 
 
 for size in args.sizes.split(","):
@@ -109,9 +96,9 @@ for size in args.sizes.split(","):
                 three_out[r] = (list(wm), wt.value)
 
         front()
-        t_fit = timed(fit)
-        t_picture = timed(picture)
-        t_three = timed(three_calls)
+        t_fit = per_call(fit)
+        t_picture = per_call(picture)
+        t_three = per_call(three_calls)
         t0 = time.perf_counter()
         want = fc.ref_estimate(cref, src, ref, 0, 0, N_REF)
         t_cpu = (time.perf_counter() - t0) * 1e3 * n_refs

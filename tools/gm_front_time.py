@@ -30,23 +30,10 @@ cref.setup_common_rtcd_internal(0); cref.setup_rtcd_internal(0)
 simd = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsvtav1_ref_simd.so"))
 simd.refb_setup.restype = C.c_uint64; simd.refb_setup.argtypes = [C.c_uint64]
 simd.refb_setup(0xFFFFFFFFFFFFFFFF)
-ms = C.c_float()
+per_call = lambda fn: hip.timed(fn, args.window)[0]
 ONE = g.ONE
 TRUTH = (3 * ONE + 8192, -2 * ONE - 4096, ONE + 160, 96, -96, ONE + 160)
 MAXP = pkg.GM_MAX_CORNERS
-
-
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps
 
 
 def host(lib, src, ref, n_refs):
@@ -82,9 +69,9 @@ for size in args.sizes.split(","):
         def chain():
             corners(); match()
 
-        t_corners = timed(corners)
-        t_match = timed(match)
-        t_chain = timed(chain)
+        t_corners = per_call(corners)
+        t_match = per_call(match)
+        t_chain = per_call(chain)
         cnt, kept, ncorr = hip.to_host(d_c, (n,), np.int32), hip.to_host(d_k, (n,), np.int32), hip.to_host(d_n, (n_refs,), np.int32)
         pts, corr = hip.to_host(d_p, (n, MAXP, 2), np.int32), hip.to_host(d_o, (n_refs, MAXP, 4), np.int32)
         c_corners, c_match, sp, rp, want = host(cref, src, ref, n_refs)

@@ -28,24 +28,10 @@ simd = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsvtav1_ref_simd.so"))
 simd.refb_setup.restype = C.c_uint64; simd.refb_setup.argtypes = [C.c_uint64]
 simd.refb_setup(0xFFFFFFFFFFFFFFFF)
 g.prepare(simd)
-ms = C.c_float()
 ONE = g.ONE
 TRUTH = (3 * ONE + 8192, -2 * ONE - 4096, ONE + 160, 96, -96, ONE + 160)
 WALKS = [("ROTZOOM", g.ROTZOOM, (3 * ONE + 2048, -2 * ONE, ONE + 128, 64, 0, 0)), ("AFFINE", g.AFFINE, (3 * ONE + 2048, -2 * ONE, ONE + 128, 64, -64, ONE + 140))]
 N_REF = 5
-
-
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps, ms.value, reps
 
 
 for size in args.sizes.split(","):
@@ -64,16 +50,14 @@ for size in args.sizes.split(","):
             for i, j in enumerate(jobs):
                 j.ref, j.wmtype, j.n_refinements, j.best_frame_error = i, wmtype, N_REF, g.INT64_MAX
                 for k, v in enumerate(start): j.wmmat[k] = v
-            d_jobs = hip._upload_jobs(jobs)
-            d_out, d_x = hip.empty(njobs * C.sizeof(pkg.GmResult)), hip.empty(L.svt_hip_gm_refine_scratch_bytes(njobs))
-            polls = C.c_int()
-            call = lambda: hip.check(L.svt_hip_gm_refine_picture_dev(hip.h, d_src, w, w, h, tab, 7, d_jobs, njobs, d_out, d_x, C.byref(polls)), "gm_refine_picture")
-            t, window, reps = timed(call)
-            out = (pkg.GmResult * njobs)()
-            hip.check(L.svt_hip_memcpy_d2h(hip.h, C.cast(out, C.c_void_p), d_out, C.sizeof(out)), "d2h")
+            with hip.scope() as s:
+                d_jobs, d_out, d_x = s.structs(jobs), s.empty(njobs * C.sizeof(pkg.GmResult)), s.empty(L.svt_hip_gm_refine_scratch_bytes(njobs))
+                polls = C.c_int()
+                call = lambda: hip.call("gm_refine_picture_dev", d_src, w, w, h, tab, 7, d_jobs, njobs, d_out, d_x, C.byref(polls))
+                t, window, reps = hip.timed(call, args.window)
+                out = s.structs_back(d_out, pkg.GmResult * njobs)
             same = all((list(o.wmmat), o.wmtype, o.best_error) == want for o in out)
             print(f"{w}x{h} {name:8s} {njobs} job(s): {t:9.3f} ms per call  probes {out[0].probes:4d}  rounds {out[0].rounds:3d}  polls {polls.value}  "
                   f"(window {window:.0f} ms, {reps} calls)   CPU (x86 kernels, 1 thread) {cpu_ms:9.1f} ms per walk  results {'equal' if same else 'DIFFER'}", flush=True)
-            hip.free(d_jobs, d_out, d_x)
     hip.free(d_src, d_ref)
 hip.close()

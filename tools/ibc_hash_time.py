@@ -29,7 +29,7 @@ args = ap.parse_args()
 pkg = load_package()
 hip = pkg.Context(0)
 L = hip.L
-ms = C.c_float()
+per_call = lambda fn: hip.timed(fn, args.window)[0]
 
 
 def screen_picture(w, h, seed):
@@ -46,19 +46,6 @@ def screen_picture(w, h, seed):
     return pic.astype(np.uint8)
 
 
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps
-
-
 jc, cc = I.cost_tables()
 d_jc, d_cc = hip.to_device(jc), hip.to_device(cc)
 for size in args.sizes.split(","):
@@ -66,7 +53,7 @@ for size in args.sizes.split(","):
     for kind, pic in (("screen", screen_picture(W, H, 1)), ("noise", I.noise(W, H))):
         cap, nbytes = int(L.svt_hip_ibc_hash_max_entries(W, H)), L.svt_hip_ibc_hash_scratch_bytes(W, H)
         d_pic, d_start, d_ent, d_info, d_scr = hip.to_device(pic), hip.empty((I.N_BUCKETS + 1) * 4), hip.empty(cap * 8), hip.empty(8), hip.empty(nbytes)
-        t = timed(lambda: hip.check(L.svt_hip_ibc_hash_table_dev(hip.h, 1, 8, d_pic, W, W, H, d_start, d_ent, cap, d_info, d_scr, nbytes), "ibc_hash_table"))
+        t = per_call(lambda: hip.check(L.svt_hip_ibc_hash_table_dev(hip.h, 1, 8, d_pic, W, W, H, d_start, d_ent, cap, d_info, d_scr, nbytes), "ibc_hash_table"))
         n_entries, stored = hip.to_host(d_info, (2,), np.int32).tolist()
         start = hip.to_host(d_start, (I.N_BUCKETS + 1,), np.int32)
         positions = sum((W - s + 1) * (H - s + 1) for s in (2,) + I.SIZES)
@@ -80,9 +67,11 @@ for size in args.sizes.split(","):
             grid = grid[::max(1, len(grid) // args.jobs)][:args.jobs]
             jobs = [I.job(x, y, n, 1, limits=(-1023, 1023, -1023, 1023), w=W, h=H, log2=4) for x, y in grid]
             tab = I.c_jobs(pkg, jobs)
-            d_jobs, d_res = hip._upload_jobs(tab), hip.empty(len(jobs) * C.sizeof(pkg.IbcSearchResult))
-            t = timed(lambda: hip.check(L.svt_hip_ibc_hash_search_batch_dev(hip.h, 1, 8, d_pic, W, W, H, d_start, d_ent, d_jc, d_cc, d_jobs, len(jobs), d_res), "ibc_hash_search"))
-            res = hip.to_host(d_res, (len(jobs), 7), np.int32)
+            with hip.scope() as s:
+                d_jobs, d_res = s.structs(tab), s.empty(len(jobs) * C.sizeof(pkg.IbcSearchResult))
+                t = per_call(lambda: hip.check(L.svt_hip_ibc_hash_search_batch_dev(hip.h, 1, 8, d_pic, W, W, H, d_start, d_ent, d_jc, d_cc, d_jobs, len(jobs), d_res),
+                                               "ibc_hash_search"))
+                res = s.download(d_res, (len(jobs), 7), np.int32)
             few = jobs[::max(1, len(jobs) // args.host_jobs)]
             t0 = time.perf_counter(); h_res = pkg.ibc_hash_search_host(pic, h_start, h_ent, jc, cc, I.c_jobs(pkg, few)); host = (time.perf_counter() - t0) * len(jobs) / len(few)
             step = max(1, len(jobs) // args.host_jobs)
@@ -90,7 +79,6 @@ for size in args.sizes.split(","):
             print(f"  hash search {n:3d}x{n:<3d}: {t * 1e3:9.1f} us per launch  {len(jobs):5d} jobs, {int(np.maximum(res[:, 0], 0).sum()):9d} entries compared, "
                   f"{int(res[:, 2].sum()):9d} candidates costed, {int(res[:, 3].sum()):5d} found  | host form, one thread ({len(few)} jobs timed, scaled): {host * 1e3:9.1f} ms "
                   f"({host / (t * 1e-3):6.0f} x), results {'equal' if same else 'DIFFER'}", flush=True)
-            hip.free(d_jobs, d_res)
         hip.free(d_pic, d_start, d_ent, d_info, d_scr)
 hip.free(d_jc, d_cc)
 hip.close()

@@ -32,21 +32,11 @@ d_cb, d_cr = hip.to_device(rng.integers(0, 256, (CH, CW)).astype(np.uint8)), hip
 d_dst = hip.empty(W * H)
 NREC = 4096   # a pool of edge records shared by the jobs
 d_edges = hip.to_device(rng.integers(0, 256, (NREC, 2, 160)).astype(np.uint8))
-ms = C.c_float()
 
 
-def timed(name, fn, nbytes, njobs):
-    for _ in range(5): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps, t = 20, 0.0
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    t = ms.value / reps
-    print(f"{name:44s} {t * 1e3:9.1f} us per call  {njobs:7d} jobs  {nbytes / 1e6:7.2f} MB algorithmic -> {nbytes / t / 1e6:8.1f} GB/s  (window {ms.value:.0f} ms, {reps} launches)",
+def report(name, fn, nbytes, njobs):
+    t, window, reps = hip.timed(fn, args.window, warm=5, reps=20)   # this tool has always warmed five times and started at 20 launches
+    print(f"{name:44s} {t * 1e3:9.1f} us per call  {njobs:7d} jobs  {nbytes / 1e6:7.2f} MB algorithmic -> {nbytes / t / 1e6:8.1f} GB/s  (window {window:.0f} ms, {reps} launches)",
           flush=True)
 
 
@@ -68,8 +58,8 @@ for tw, tx in ((8, 1), (16, 2)):
         n = len(tiles)
         # luma area + per plane (block read unless the DC comes from 2 tw edge samples) + block written, + the descriptor
         nbytes = n * (4 * tw * tw + 2 * ((0 if dc else tw * tw) + (2 * tw if dc else 0) + tw * tw) + C.sizeof(pkg.CflJob))
-        timed(f"cfl {tw}x{tw} chroma blocks, {'dc_from_edges' if dc else 'in place'}",
-              lambda d_jobs=d_jobs, n=n: hip.check(L.svt_hip_cfl_predict_batch_dev(hip.h, 1, 8, d_luma, W, d_edges, d_jobs, n, d_cb, d_cr, CW, None), "cfl"), nbytes, n)
+        report(f"cfl {tw}x{tw} chroma blocks, {'dc_from_edges' if dc else 'in place'}",
+               lambda d_jobs=d_jobs, n=n: hip.check(L.svt_hip_cfl_predict_batch_dev(hip.h, 1, 8, d_luma, W, d_edges, d_jobs, n, d_cb, d_cr, CW, None), "cfl"), nbytes, n)
         hip.free(d_jobs)
 
 for tw, tx in ((16, 2), (4, 0)):
@@ -80,8 +70,8 @@ for tw, tx in ((16, 2), (4, 0)):
     d_jobs = device_jobs(arr)
     n = len(tiles)
     nbytes = n * ((2 * tw + 1) + tw * tw + C.sizeof(pkg.FilterIntraJob))
-    timed(f"filter-intra {tw}x{tw} luma blocks",
-          lambda d_jobs=d_jobs, n=n: hip.check(L.svt_hip_filter_intra_predict_batch_dev(hip.h, 1, 8, d_edges, d_jobs, n, d_dst, W), "filter-intra"), nbytes, n)
+    report(f"filter-intra {tw}x{tw} luma blocks",
+           lambda d_jobs=d_jobs, n=n: hip.check(L.svt_hip_filter_intra_predict_batch_dev(hip.h, 1, 8, d_edges, d_jobs, n, d_dst, W), "filter-intra"), nbytes, n)
     hip.free(d_jobs)
 
 # the comparison: 16x16 sub-pel blocks over the same luma plane (padded by 32), random fractional positions within +-8 samples
@@ -96,8 +86,8 @@ for by in range(0, H, 16):
         CB[k] = pkg.ConvBlk(bx + int(rng.integers(-8, 9)), by + int(rng.integers(-8, 9)), bx, by, 16, 16, 0, 0, int(rng.integers(0, 16)), int(rng.integers(0, 16)), 0, 0)
         k += 1
 d_cbk = device_jobs(CB)
-timed("subpel_predict 16x16 luma blocks (8-tap window)",
-      lambda: hip.check(L.svt_hip_subpel_predict_batch_dev(hip.h, 1, 8, d_refp.value + PAD * refp.shape[1] + PAD, refp.shape[1], d_dst, W, d_cbk, n16), "subpel"),
-      n16 * (23 * 23 + 256 + C.sizeof(pkg.ConvBlk)), n16)
+report("subpel_predict 16x16 luma blocks (8-tap window)",
+       lambda: hip.check(L.svt_hip_subpel_predict_batch_dev(hip.h, 1, 8, d_refp.value + PAD * refp.shape[1] + PAD, refp.shape[1], d_dst, W, d_cbk, n16), "subpel"),
+       n16 * (23 * 23 + 256 + C.sizeof(pkg.ConvBlk)), n16)
 hip.free(d_luma, d_cb, d_cr, d_dst, d_edges, d_refp, d_cbk)
 hip.close()

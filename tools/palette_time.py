@@ -27,7 +27,7 @@ args = ap.parse_args()
 pkg = load_package()
 hip = pkg.Context(0)
 L = hip.L
-ms = C.c_float()
+per_call = lambda fn: hip.timed(fn, args.window)[0]
 
 
 def screen_picture(w, h, bd, seed):
@@ -43,19 +43,6 @@ def screen_picture(w, h, bd, seed):
     pic[h // 2:h // 2 + h // 8, :] = (np.arange(w) * 255 // w * sc)[None, :]                                                      # a gradient
     pic[h - h // 6:, :] = np.clip(rng.normal(128, 30, (h // 6, w)), 0, 255).astype(np.int64) * sc + rng.integers(0, sc, (h // 6, w))   # camera-like
     return pic.astype(np.uint8 if bd == 8 else np.uint16)
-
-
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps
 
 
 class TimedRef(P.RefBackend):
@@ -102,9 +89,10 @@ for size in (8, 16, 32, 64):
     jobs = [dict(x=x, y=y, bw=size, bh=size, cols=size, rows=size, cache=[], step=1) for y in range(0, H - size + 1, size) for x in range(0, W - size + 1, size)]
     tab, nbytes = P.c_jobs(pkg, jobs)
     n = len(jobs)
-    d_jobs, d_res, d_cands, d_maps = hip._upload_jobs(tab), hip.empty(n * C.sizeof(pkg.PaletteResult)), hip.empty(n * 14 * C.sizeof(pkg.PaletteCand)), hip.empty(nbytes)
-    t = timed(lambda: hip.check(L.svt_hip_palette_search_batch_dev(hip.h, 1, 8, d_pic, W, d_jobs, n, d_res, d_cands, d_maps), "palette_search_batch"))
-    res = hip.to_host(d_res, (n, 2), np.int32)
+    with hip.scope() as s:
+        d_jobs, d_res, d_cands, d_maps = s.structs(tab), s.empty(n * C.sizeof(pkg.PaletteResult)), s.empty(n * 14 * C.sizeof(pkg.PaletteCand)), s.empty(nbytes)
+        t = per_call(lambda: hip.check(L.svt_hip_palette_search_batch_dev(hip.h, 1, 8, d_pic, W, d_jobs, n, d_res, d_cands, d_maps), "palette_search_batch"))
+        res = s.download(d_res, (n, 2), np.int32)
     searched = int(((res[:, 0] > 1) & (res[:, 0] <= 64)).sum())
     line = (f"palette search {W}x{H} 8-bit, {size:2d}x{size:<2d}: {t * 1e3:8.1f} us per launch  {n:6d} jobs, {searched:6d} with 1 < colors <= 64, "
             f"{int(res[:, 1].sum()):7d} candidates kept, {t * 1e6 / n:6.1f} ns per job")
@@ -115,14 +103,13 @@ for size in (8, 16, 32, 64):
         host = be.seconds * n / len(sample)
         line += f"  | host, one thread, reference dispatch: {host * 1e3:9.1f} ms ({len(sample)} blocks timed, {kept} candidates; {host / (t * 1e-3):7.0f} x)"
     print(line, flush=True)
-    hip.free(d_jobs, d_res, d_cands, d_maps)
 hip.free(d_pic)
 
 W, H = 3840, 2160
 for bd in (8, 10):
     pic = screen_picture(W, H, bd, 2)
     d_pic, d_out = hip.to_device(pic), hip.empty(16)
-    t = timed(lambda: hip.check(L.svt_hip_screen_content_detect_dev(hip.h, pic.itemsize, bd, d_pic, W, W, H, d_out), "screen_content_detect"))
+    t = per_call(lambda: hip.check(L.svt_hip_screen_content_detect_dev(hip.h, pic.itemsize, bd, d_pic, W, W, H, d_out), "screen_content_detect"))
     out = hip.to_host(d_out, (4,), np.int32).tolist()
     line = (f"screen-content detection {W}x{H} {bd:2d}-bit: {t * 1e3:8.1f} us per call  {(W // 16) * (H // 16)} blocks, {W * H * pic.itemsize / 1e6:.1f} MB read "
             f"-> {W * H * pic.itemsize / t / 1e6:7.1f} GB/s  counts {out[0]}, {out[1]}  detected {out[2]}, {out[3]}")

@@ -5,7 +5,6 @@ full-width picture to that coded width (svt_hip_resize_planes_dev, width alone, 
 it reads and writes that many), measured in the same run, and the ratio.  The kernels are memory-bound; that copy is the yardstick.
     python tools/superres_time.py [--window 100] [--size 3840x2160] [--denoms 9,12,16]"""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -23,22 +22,8 @@ args = ap.parse_args()
 pkg = load_package()
 hip = pkg.Context(0)
 L = hip.L
-ms = C.c_float()
 W, H = (int(v) for v in args.size.split("x"))
-
-
-def timed(fn):
-    for _ in range(2): fn()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # lengthen the window until it is long enough; only the last one counts
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): fn()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window: break
-        reps = int(reps * max(2.0, 1.2 * args.window / max(ms.value, 1e-3)))
-    return ms.value / reps
-
+per_call = lambda fn: hip.timed(fn, args.window)[0]
 
 for dtype, bd in ((np.uint8, 8), (np.uint16, 10)):
     pix = np.dtype(dtype).itemsize
@@ -53,9 +38,9 @@ for dtype, bd in ((np.uint8, 8), (np.uint16, 10)):
         assert L.svt_hip_resize_scratch_bytes(pix, down, 3) == 0
         nbytes = sum((sw + w) * h * pix for sw, (w, h) in zip(small, full))   # bytes in + bytes out, the same for both directions
         d_a, d_b = hip.empty(nbytes // 2), hip.empty(nbytes // 2)
-        t_down = timed(lambda: hip.check(L.svt_hip_resize_planes_dev(hip.h, pix, bd, down, 3, None, 0), "resize_planes"))
-        t_up = timed(lambda: hip.check(L.svt_hip_superres_upscale_planes_dev(hip.h, pix, bd, up, 3), "superres_upscale_planes"))
-        t_copy = timed(lambda: hip.check(L.svt_hip_memcpy_d2d(hip.h, d_a, d_b, nbytes // 2), "d2d"))
+        t_down = per_call(lambda: hip.check(L.svt_hip_resize_planes_dev(hip.h, pix, bd, down, 3, None, 0), "resize_planes"))
+        t_up = per_call(lambda: hip.check(L.svt_hip_superres_upscale_planes_dev(hip.h, pix, bd, up, 3), "superres_upscale_planes"))
+        t_copy = per_call(lambda: hip.check(L.svt_hip_memcpy_d2d(hip.h, d_a, d_b, nbytes // 2), "d2d"))
         print(f"{W}x{H} 4:2:0 {8 * pix:2d}-bit samples bd {bd:2d} denom {denom:2d} (coded width {small[0]}): upscale {t_up * 1e3:7.1f} us ({t_up / t_copy:4.2f} x copy)  "
               f"downscale {t_down * 1e3:7.1f} us ({t_down / t_copy:4.2f} x copy)  copy of {nbytes / 1e6:.1f} MB in + out {t_copy * 1e3:7.1f} us "
               f"({nbytes / t_copy / 1e6:.0f} GB/s)", flush=True)

@@ -35,7 +35,6 @@ d_stats = [hip.to_device(S.random_stats(rng, w, h, 3)) for _ in range(n_max)]
 d_dep = [hip.empty(dep_bytes) for _ in range(n_max)]
 d_out = hip.empty(L.svt_hip_tpl_r0beta_out_bytes(w, h, P.sb_size))
 d_scratch = hip.empty(L.svt_hip_tpl_r0beta_scratch_bytes())
-ms = C.c_float()
 print(f"tpl_window {w}x{h}, {1 << P.cell_log2}x{1 << P.cell_log2} cells, {dep_bytes // 16} source blocks per picture, grid {dep_bytes / 1e6:.2f} MB")
 for n in counts:
     slots = [[pocs[k - 1] if k >= 1 else 999, pocs[k - 2] if k >= 2 else 999, pocs[0] if k >= 2 else 999] for k in range(n)]
@@ -44,18 +43,9 @@ for n in counts:
     def once():
         hip.check(L.svt_hip_tpl_window_dev(hip.h, C.byref(P), F, n, d_out, d_scratch), "tpl_window")
 
-    for _ in range(2): once()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps = 2
-    while True:   # grow the window until it is long enough
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): once()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window_ms: break
-        reps = max(reps * 2, int(reps * 1.3 * args.window_ms / max(ms.value, 1e-3)))
-    t = ms.value / reps
+    t, win, reps = hip.timed(once, args.window_ms, growth=1.3)   # this tool has always grown its windows by 1.3, not 1.2
     launches = 2 * n + 3
-    print(f"  {n:2d} pictures: {t:.4f} ms per window  (window {ms.value:.0f} ms, {reps} calls); {launches} launches ({n} memsets + {n} scatters + 1 memset + 2 kernels) "
+    print(f"  {n:2d} pictures: {t:.4f} ms per window  (window {win:.0f} ms, {reps} calls); {launches} launches ({n} memsets + {n} scatters + 1 memset + 2 kernels) "
           f"x {BOUNDARY_US} us = {launches * BOUNDARY_US / 1e3:.4f} ms; {1e3 * t / launches:.2f} us per launch")
 hip.free(*d_stats, *d_dep, d_out, d_scratch)
 hip.close()

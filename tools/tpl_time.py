@@ -56,34 +56,18 @@ d_scratch = hip.empty(L.svt_hip_tpl_dispenser_scratch_bytes(w, h)); held.append(
 P = pkg.TplParams()
 P.w, P.h, P.pad, P.q = w, h, T.PAD, T.device_qparams(pkg, qp)
 P.use_ois, P.add_residual, P.rate, P.best_ref_only = 1, 1, 1, 0
-ms = C.c_float()
-
-
-def timed(table, mask):
-    def once():
-        hip.check(L.svt_hip_tpl_dispenser_picture_dev(hip.h, C.byref(P), org(d_cur), S, table, d_mv, d_mask, d_mode, d_cost, org(d_rec), S, d_stats, d_scratch), "tpl")
-    hip.check(L.svt_hip_tpl_set_phases(hip.h, mask), "phases")
-    for _ in range(2): once()
-    hip.check(L.svt_hip_sync(hip.h), "sync")
-    reps, t = 2, 0.0
-    while True:   # grow the window until it is long enough
-        L.svt_hip_timer_start(hip.h)
-        for _ in range(reps): once()
-        hip.check(L.svt_hip_timer_stop_ms(hip.h, C.byref(ms)), "timer")
-        if ms.value >= args.window_ms: break
-        reps = max(reps * 2, int(reps * 1.3 * args.window_ms / max(ms.value, 1e-3)))
-    return ms.value / reps, ms.value, reps
-
 
 for name, table in (("generator picture", refs), ("all-intra picture", none)):
+    once = lambda: hip.check(L.svt_hip_tpl_dispenser_picture_dev(hip.h, C.byref(P), org(d_cur), S, table, d_mv, d_mask, d_mode, d_cost, org(d_rec), S, d_stats, d_scratch), "tpl")
     hip.check(L.svt_hip_tpl_set_phases(hip.h, 7), "phases")
-    hip.check(L.svt_hip_tpl_dispenser_picture_dev(hip.h, C.byref(P), org(d_cur), S, table, d_mv, d_mask, d_mode, d_cost, org(d_rec), S, d_stats, d_scratch), "tpl")
-    hip.check(L.svt_hip_sync(hip.h), "sync")
+    once()
+    hip.sync()
     st = hip.to_host(d_stats, (mbh, mbw), np.dtype(pkg.TplMbStats))
     print(f"tpl_dispenser {w}x{h} qindex 140, {name}: {mbw * mbh} macroblocks, inter share {float((st['is_inter'] != 0).mean()):.3f}, "
           f"launches per call: 1 (phase A) + {steps} (phase B) + 1 (padding)")
     for label, mask in (("whole call", 7), ("phase A", 1), ("phase B", 2), ("padding", 4)):
-        t, win, reps = timed(table, mask)
+        hip.check(L.svt_hip_tpl_set_phases(hip.h, mask), "phases")
+        t, win, reps = hip.timed(once, args.window_ms, growth=1.3)   # this tool has always grown its windows by 1.3, not 1.2
         extra = f"  = {1e3 * t / steps:.2f} us per step; {steps} boundaries x {BOUNDARY_US} us = {steps * BOUNDARY_US / 1e3:.3f} ms" if mask == 2 else ""
         print(f"  {label:10s}: {t:.4f} ms per picture  (window {win:.0f} ms, {reps} calls){extra}")
 hip.check(L.svt_hip_tpl_set_phases(hip.h, 7), "phases")
