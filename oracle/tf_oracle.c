@@ -176,8 +176,22 @@ void orc_tf_filter_frame(int pix_bytes, int bd, const void *const src[3], const 
                                     else (p == 0 ? yp16 : p == 1 ? up16 : vp16)[i * pstride[p] + j] = (uint16_t)v;
                                 }
                         }
-                        orc_tf_planewise(blk, r, c, tf_chroma, min_frame_size, pix_bytes, bd, s[0], src_stride[0],
-                                         pix_bytes == 1 ? (void *)yp8 : (void *)yp16, pstride[0], s[1], s[2], src_stride[1],
+                        /* ... and on copies of the central block as well: the block function has ONE stride for both chroma planes of the central picture
+                         * (uv_src_stride, as the reference's), the frame call a stride per plane */
+                        uint16_t sp16[3][32 * 64];
+                        uint8_t  sp8[3][32 * 64];
+                        for (int p = 0; p < 3; p++) {
+                            const int pw = (p ? cw : 64) >> 1, ph = (p ? ch : 64) >> 1;
+                            if (p && !tf_chroma) break;
+                            for (int i = 0; i < ph; i++)
+                                for (int j = 0; j < pw; j++) {
+                                    const unsigned v = px(s[p], pix_bytes, (size_t)i * src_stride[p] + j);
+                                    if (pix_bytes == 1) sp8[p][i * pstride[p] + j] = (uint8_t)v; else sp16[p][i * pstride[p] + j] = (uint16_t)v;
+                                }
+                        }
+                        for (int p = 0; p < 3; p++) s[p] = pix_bytes == 1 ? (const void *)sp8[p] : (const void *)sp16[p];
+                        orc_tf_planewise(blk, r, c, tf_chroma, min_frame_size, pix_bytes, bd, s[0], pstride[0],
+                                         pix_bytes == 1 ? (void *)yp8 : (void *)yp16, pstride[0], s[1], s[2], pstride[1],
                                          pix_bytes == 1 ? (void *)up8 : (void *)up16, pix_bytes == 1 ? (void *)vp8 : (void *)vp16, pstride[1], 32, 32,
                                          ss_x, ss_y, noise_levels, decay_control, ya, yc, ua, uc, va, vc);
                         for (int p = 0; p < (tf_chroma ? 3 : 1); p++) {

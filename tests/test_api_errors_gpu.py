@@ -1,7 +1,7 @@
 """GPU: what the C-ABI layer (csrc/svt_hip_api.cpp) answers to calls it refuses, with a live context: the return code and the exact text svt_hip_last_error()
 gives afterwards.  Some refusals carry a text and some leave the context's text as it was; the per-call table (csrc/rtcd_hip.cpp) tells a device failure from a
 domain delegation by exactly that, so both are pinned.  The families here are the ones the other live-context tests do not refuse anything in: transforms,
-deblocking, the CDEF frame calls, the md_* pictures, pyramids / SAD loops, the 2-D copies and the self-guided unit search, plus the zero-size successes that
+deblocking, the CDEF frame calls, the md_* pictures, pyramids / SAD loops, the temporal filter's three entry points, the 2-D copies and the self-guided unit search, plus the zero-size successes that
 return before anything is enqueued.
 
 No kernel is meant to run.  Every case is built so that a lost check shows as a failed assertion and not as a launch on bad memory: every pointer lies in one
@@ -205,6 +205,27 @@ def copy2d(e, fn, wbytes=64, rows=4, dpitch=64, hpitch=64):
     return getattr(e.L, fn)(e.h, e.hp, hpitch, e.d, dpitch, wbytes, rows)
 
 
+# ---- the temporal filter: a one-frame window (the central picture alone), no jobs
+def tf_filter(e, pix_bytes=1, bd=8, ss=(1, 1), decay=4, n_refs=1, src0=True, pred0=True):
+    refs = (e.pkg.TfRef * 1)()
+    if not pred0:            # a frame with block records and no predictor plane
+        refs[0].blocks = e.d.value
+    nl = (C.c_double * 3)(1.0, 1.0, 1.0)
+    src = e.p3() if src0 else (C.c_void_p * 3)(None, e.at(65536).value, e.at(131072).value)
+    return e.L.svt_hip_tf_filter_frame_dev(e.h, pix_bytes, bd, src, i3(64, 32, 32), e.p3(), i3(64, 32, 32), 64, 64, ss[0], ss[1], 1, refs, n_refs, nl, decay, 64, e.at(65536 * 8))
+
+
+def tf_noise(e, pix_bytes=1, bd=8, width=64, stride=64):
+    return e.L.svt_hip_tf_estimate_noise_dev(e.h, e.d, pix_bytes, bd, width, 8, stride, e.at(65536))
+
+
+def tf_subpel(e, pix_bytes=1, bd=8, ref0=True):
+    ref = e.p3() if ref0 else (C.c_void_p * 3)(None, e.at(65536).value, e.at(131072).value)
+    return e.L.svt_hip_tf_subpel_frame_dev(e.h, pix_bytes, bd, e.p3(), i3(64, 32, 32), ref, i3(64, 32, 32), e.p3(), i3(64, 32, 32), 16, 16, 0, 1, 1, e.d, 0, e.at(65536 * 8))
+
+
+TF_FILTER_TEXT, TF_SUBPEL_TEXT = b"svt_hip_tf_filter_frame_dev: bad argument", b"svt_hip_tf_subpel_frame_dev: bad argument"
+
 COPIES_2D = ("svt_hip_memcpy2d_h2d", "svt_hip_memcpy2d_d2h", "svt_hip_memcpy2d_h2d_async", "svt_hip_memcpy2d_d2h_async")
 
 # (id, call, return code, text afterwards)
@@ -284,6 +305,21 @@ CASES = [
     ("block_variance-bd12", lambda e: e.L.svt_hip_block_variance_batch_dev(e.h, 2, 12, e.d, 64, e.d, 64, e.d, 0, e.d, e.d), BAD_ARG, SAME),
     ("block_variance-8bit-bytes-bd16", lambda e: e.L.svt_hip_block_variance_batch_dev(e.h, 1, 16, e.d, 64, e.d, 64, e.d, 0, e.d, e.d), BAD_ARG, SAME),
     ("subpel_predict-bd", lambda e: e.L.svt_hip_subpel_predict_batch_dev(e.h, 2, 12, e.d, 64, e.d, 64, e.d, 0), BAD_ARG, b"svt_hip_subpel_predict_batch_dev: bad argument"),
+    # temporal filter
+    ("tf_filter-bd7", lambda e: tf_filter(e, pix_bytes=2, bd=7), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-bd13", lambda e: tf_filter(e, pix_bytes=2, bd=13), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-ss_y-without-ss_x", lambda e: tf_filter(e, ss=(0, 1)), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-decay_control", lambda e: tf_filter(e, decay=0), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-n_refs0", lambda e: tf_filter(e, n_refs=0), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-n_refs17", lambda e: tf_filter(e, n_refs=17), BAD_ARG, TF_FILTER_TEXT),
+    ("tf_filter-src-plane", lambda e: tf_filter(e, src0=False), BAD_ARG, SAME),
+    ("tf_filter-pred-plane", lambda e: tf_filter(e, pred0=False), BAD_ARG, SAME),
+    ("tf_noise-bd7", lambda e: tf_noise(e, pix_bytes=2, bd=7), BAD_ARG, SAME),
+    ("tf_noise-bd13", lambda e: tf_noise(e, pix_bytes=2, bd=13), BAD_ARG, SAME),
+    ("tf_noise-stride", lambda e: tf_noise(e, width=64, stride=63), BAD_ARG, SAME),
+    ("tf_subpel-bd12", lambda e: tf_subpel(e, pix_bytes=2, bd=12), BAD_ARG, TF_SUBPEL_TEXT),
+    ("tf_subpel-bd7", lambda e: tf_subpel(e, pix_bytes=2, bd=7), BAD_ARG, TF_SUBPEL_TEXT),
+    ("tf_subpel-ref-plane", lambda e: tf_subpel(e, ref0=False), BAD_ARG, SAME),
     # copies and the zero-size successes: nothing is enqueued
     *[("%s-dpitch" % fn[8:], lambda e, fn=fn: copy2d(e, fn, dpitch=32), BAD_ARG, SAME) for fn in COPIES_2D],
     *[("%s-hpitch" % fn[8:], lambda e, fn=fn: copy2d(e, fn, hpitch=32), BAD_ARG, SAME) for fn in COPIES_2D],

@@ -962,7 +962,7 @@ def test_temporal_filter_planewise_noise_and_divu(orc, ref):
     def _cnt0(it):
         r2 = np.random.default_rng(it); [r2.integers(0, 1 << 20, 32 * 64) for _ in range(3)]
         return r2.integers(0, 3000, 32 * 64).astype(np.int64)
-    for bd, dt in FMT3:
+    for bd, dt in FMT3 + ((9, np.uint16), (11, np.uint16), (12, np.uint16)):      # the shifts (bd - 8) * 2 and bd - 8 are run-time values: every depth the entry points accept
         hbd = int(dt == np.uint16)
         seen = set()
         for it in range(24):

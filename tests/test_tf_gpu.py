@@ -273,3 +273,113 @@ def test_subpel_finds_the_motion(hip, orc, pkg):
     # the reference texture is offset by (-2.3, +1.6): block at x in the central picture sits at x - 2.3 in the reference -> vector ~ (-2.3, +1.6) * 8
     mvx = blk["mv32_x"][inner].astype(np.int32); mvy = blk["mv32_y"][inner].astype(np.int32)
     assert np.all(np.abs(mvx - round(-2.3 * 8)) <= 12) and np.all(np.abs(mvy - round(1.6 * 8)) <= 12), (mvx, mvy)
+
+
+# ------------------------------------------------------------------------------------------------ wraps, ties and edges
+# The cases are tf_common's; tests/test_tf_ref_cpu.py proves on the CPU what each contains and that the oracle equals a plain restatement on every one of them.
+def filter_on_device(hip, pkg, c, in_place=False):
+    """svt_hip_tf_filter_frame_dev on a FilterCase -> (destination allocations whole, padding included, sse)"""
+    d_src = [hip.to_device(b) for b in c.src]; d_dst = d_src if in_place else [hip.to_device(b) for b in c.dst]
+    d_pred = [[hip.to_device(b) for b in pr] for pr in c.preds]; d_blk = [hip.to_device(b) for b in c.blocks]
+    refs = c.refs(pkg.TfRef, lambda k, p: d_pred[k][p].value, lambda k: d_blk[k].value)
+    shapes = c.src if in_place else c.dst
+    d_sse = hip.to_device(np.full(2, 0xDEAD, np.uint64))         # the entry point clears it
+    hip.check(hip.L.svt_hip_tf_filter_frame_dev(hip.h, c.src[0].itemsize, c.bd, P3(*[p.value for p in d_src]), I3(*[b.shape[1] for b in c.src]), P3(*[p.value for p in d_dst]),
+                                               I3(*[b.shape[1] for b in shapes]), c.w, c.h, c.ss_x, c.ss_y, c.tf_chroma, refs, c.n_refs,
+                                               c.noise.ctypes.data_as(C.POINTER(C.c_double)), c.decay, c.mfs, d_sse), "tf filter " + c.name)
+    got = [hip.to_host(d, b.shape, b.dtype) for d, b in zip(d_dst, shapes)]
+    sse = hip.to_host(d_sse, (2,), np.uint64)
+    hip.free(*d_src, *([] if in_place else d_dst), *[x for pr in d_pred for x in pr], *d_blk, d_sse)
+    return got, sse
+
+
+def check_filter_case(hip, orc, pkg, c):
+    for in_place in (False, True):
+        exp, e_sse = c.oracle(orc, in_place)
+        got, g_sse = filter_on_device(hip, pkg, c, in_place)
+        for p in range(3):      # whole allocations: the planes, the sentinels of the padding, and -- luma only -- the chroma planes untouched
+            assert np.array_equal(got[p], exp[p]), (c.name, in_place, p, np.argwhere(got[p] != exp[p])[:5])
+            assert (got[p][:, c.dims[p][1]:] == tfc.sentinel(c.dt)).all()
+        assert np.array_equal(g_sse, e_sse), (c.name, in_place, g_sse, e_sse)
+    return got
+
+
+@pytest.mark.parametrize("fmt", tfc.FILTER_FMTS, ids=[tfc.fmt_id(f) for f in tfc.FILTER_FMTS])
+def test_filter_edge_cases(hip, orc, pkg, fmt):
+    """saturated, checkerboard, binary, border-only and luma-only contents; every plane of every role with a stride of its own; extreme block records; 4:2:0 / 4:2:2 /
+    4:4:4, with and without chroma, decay 1 / 4, min_frame_size 1 / 64 / 2160; bit depths 8 .. 12 -- bit-exact against the oracle, out of place and in place"""
+    for c in tfc.filter_edge_cases(fmt):
+        check_filter_case(hip, orc, pkg, c)
+
+
+@pytest.mark.parametrize("fmt", tfc.FILTER_FMTS, ids=[tfc.fmt_id(f) for f in tfc.FILTER_FMTS])
+def test_filter_slow_division_instance(hip, orc, pkg, fmt):
+    """V noise level -1 makes 2 n_decay^2 of V +inf, which recip_ok refuses: the launcher takes the IEEE-division instance for the whole launch.  Y and U go through real
+    divisions and must equal both the oracle and the three-operation instance's result on the same pictures; V is the rounded mean of the window."""
+    c, twin = tfc.slow_division_case(fmt), tfc.slow_division_case(fmt, v_noise=2.4)
+    slow = check_filter_case(hip, orc, pkg, c)
+    fast = check_filter_case(hip, orc, pkg, twin)
+    assert np.array_equal(c.view(slow, 2), tfc.rounded_mean_of_window(c, 2))
+    assert all(np.array_equal(c.view(slow, p), c.view(fast, p)) for p in (0, 1)) and not np.array_equal(c.view(slow, 2), c.view(fast, 2))
+
+
+@pytest.mark.parametrize("fmt", tfc.NOISE_FMTS, ids=[tfc.fmt_id(f) for f in tfc.NOISE_FMTS])
+def test_estimate_noise_edges(hip, orc, fmt):
+    """rows past the grid's 2048, planes with nothing to visit, 15 / 16 smooth samples, the column loop's second trip, the edge threshold from both sides, the checkerboard's
+    closed form -- sums, counts and sigma against the oracle and the closed forms; the output is pre-filled"""
+    orc.orc_tf_estimate_noise.restype = C.c_double
+    dt, bd = fmt
+    for name, buf, w, h, closed in tfc.noise_edge_cases(fmt):
+        e_out = np.zeros(2, np.int64)
+        e = orc.orc_tf_estimate_noise(ptr(buf), buf.itemsize, bd, w, h, buf.shape[1], ptr(e_out))
+        d_img, d_out = hip.to_device(buf), hip.to_device(np.full(2, -1, np.int64))
+        hip.check(hip.L.svt_hip_tf_estimate_noise_dev(hip.h, d_img, buf.itemsize, bd, w, h, buf.shape[1], d_out), "noise " + name)
+        got = hip.to_host(d_out, (2,), np.int64)
+        hip.free(d_img, d_out)
+        assert np.array_equal(got, e_out), (name, got, e_out)
+        if closed is not None: assert (int(got[0]), int(got[1])) == closed, (name, got, closed)
+        assert hip.L.svt_hip_tf_noise_sigma(int(got[0]), int(got[1])) == e == tfc.sigma_of(int(got[0]), int(got[1])), name
+
+
+def subpel_on_device(hip, c):
+    """svt_hip_tf_subpel_frame_dev on a SubpelCase -> (the whole block array, the predictor allocations whole)"""
+    pb = c.src[0].itemsize
+    d_src = [hip.to_device(b) for b in c.src]; d_ref = [hip.to_device(b) for b in c.ref]; d_pred = [hip.to_device(b) for b in c.pred]
+    d_jobs = hip.to_device(c.jobs); d_blk = hip.to_device(c.blocks0)
+    hip.check(hip.L.svt_hip_tf_subpel_frame_dev(hip.h, pb, c.bd, P3(*[p.value for p in d_src]), I3(*[b.shape[1] for b in c.src]),
+                                               P3(*[d_ref[p].value + c.ref_offset(p) for p in range(3)]), I3(*[b.shape[1] for b in c.ref]), P3(*[p.value for p in d_pred]),
+                                               I3(*[b.shape[1] for b in c.pred]), c.w // 4, c.h // 4, c.th16, c.tf_hp, c.tf_chroma, d_jobs, len(c.jobs), d_blk), "tf subpel " + c.name)
+    blk = hip.to_host(d_blk, (c.n_blocks,), tfc.BLK_DTYPE)
+    pred = [hip.to_host(d, b.shape, b.dtype) for d, b in zip(d_pred, c.pred)]
+    hip.free(*d_src, *d_ref, *d_pred, d_jobs, d_blk)
+    return blk, pred
+
+
+def check_subpel_case(hip, orc, c):
+    tfc.python_subpel(orc, c)                                     # asserts that the furthest read of every prediction lies inside the reference allocation
+    e_blk, e_pred = c.oracle(orc)
+    g_blk, g_pred = subpel_on_device(hip, c)
+    for k in ("mv32_x", "mv32_y", "err32", "split", "mv16_x", "mv16_y", "err16"):
+        assert np.array_equal(g_blk[k], e_blk[k]), (c.name, k, np.argwhere(g_blk[k] != e_blk[k])[:4], g_blk[k][g_blk[k] != e_blk[k]][:4], e_blk[k][g_blk[k] != e_blk[k]][:4])
+    assert g_blk.tobytes() == e_blk.tobytes(), c.name              # untouched records included
+    for p in range(3):
+        assert np.array_equal(g_pred[p], e_pred[p]), (c.name, p, np.argwhere(g_pred[p] != e_pred[p])[:4])
+    return g_blk
+
+
+@pytest.mark.parametrize("fmt", tfc.SUBPEL_FMTS, ids=[tfc.fmt_id(f) for f in tfc.SUBPEL_FMTS])
+def test_subpel_edge_cases(hip, orc, fmt):
+    """ties (flat and row-periodic content, with and without the eighth-pel round), interpolation overshoot on both clamps, the 32-bit wraps of the 16-bit variance and of
+    the split decision, err32 == th16, start vectors at the int16 edges; cropped central / predictor planes (dst_x != x), three different strides, a permuted and sparse
+    block array -- every record and every predictor plane whole against the oracle, the tie cases against their closed forms as well"""
+    cases = tfc.subpel_edge_cases(fmt)
+    blks = {}
+    for name, c in cases.items():
+        blks[name] = check_subpel_case(hip, orc, c)
+        if c.expect: tfc.check_tie_closed_forms(c, blks[name])
+    sp = cases["split_wrap"]
+    q0 = blks["split_wrap"][int(sp.jobs["blk_index"][0])]
+    pb = sp.src[0].itemsize
+    assert int(q0["err32"][0]) == tfc.FLAT_DIST[(pb, sp.bd)][0] and not q0["err16"][:4].any()
+    assert int(q0["split"][0]) == (0 if sp.bd == 10 else 1)       # 64-bit arithmetic would split at bit depth 10
+    tfc.threshold_equality_runs(lambda k: check_subpel_case(hip, orc, k), cases["texture"])
