@@ -14,7 +14,8 @@
 // table in LDS, after which lane g becomes the reducer of strength g: sum(y), sum(y^2), sum(y*s)
 // come from v_dot4_u32_u8 over 16 dwords (v_dot2 for 16-bit), and the luma perceptual distortion
 // (FP64, sqrt, floor — Encoder/Codec/EbEncCdef.c:100-104) is evaluated per (block, strength) in the
-// reference's operation order with contraction off.
+// reference's operation order with contraction off.  On 8-bit planes the secondary sums and the chroma primary sums read constrain() from tables the
+// workgroup builds in LDS for the launch's damping ("table form" below); the luma primary sums and 16-bit planes use the packed arithmetic.
 // The staging tile marks everything outside the picture CDEF_VERY_LARGE exactly like the
 // reference's inbuf (EbCdefProcess.c:210-226).
 #include <hip/hip_runtime.h>
@@ -175,6 +176,69 @@ __device__ __forceinline__ void minmax_pair(int t0, int t1, s16x2& mn, s16x2& mx
     mx = __builtin_elementwise_max(mx, v & dup2(0x3FFF));   // CDEF_VERY_LARGE (0x4000) never wins the max (EbCdef.c:229-247)
 }
 
+// ---- table form of constrain() for 8-bit planes (coeff_shift 0) -----------------------------------
+// A tap difference d = tap - x of 8-bit samples lies in -255..255, and constrain(d, t, D) is 0 once |d| >= t << max(0, D - msb(t)), which is below
+// n = max(16, 2^(D+1)) for every t <= 15.  The workgroup therefore builds, for its launch's damping D, tables over d = -n..n in LDS (both end entries
+// are zero: a CDEF_VERY_LARGE tap, d >= 16129, is clamped onto the upper one) and a tap costs an add, a clamp, an address and one LDS read:
+//   S[d]    one dword, byte fields b0 = 4 + constrain(d, 2), b1 = 4 + constrain(d, 1), b2 = 4 + constrain(d, 4) (each 0..8).  The secondary weight is
+//           2 at distance 0 and 1 at distance 1, so the four taps of each distance are summed apart and joined as 2 * acc0 + acc1: every field is then
+//           48 + its secondary sum, inside 0..96 -- no carry between fields.  b0 / b2 sit where PixelTerms wants (sec 2, sec 4), b1 one byte below (0, sec 1).
+//   P_k[d]  sixteen bytes, byte t = 64 + w_k(t) * constrain(d, t) with eb_cdef_pri_taps' w_0 = 4 | 3, w_1 = 2 | 3 by the parity of t: |w * c| <= 4 * 14,
+//           a byte is 8..120, and the two mirrored taps of a distance add to 16..240 per byte -- no carry; the two distances keep an accumulator each,
+//           and the primary sum of strength t is byte t of one plus byte t of the other minus 256.  Chroma only (its strength is the header index); the
+//           luma primary strengths are adjusted per block and stay on the packed arithmetic.
+// Layout in the launch's dynamic LDS (dwords): [P_0: 4 (2n + 1)] [P_1: 4 (2n + 1)] [S: 2n + 1]; luma holds S alone.
+extern __shared__ __attribute__((aligned(16))) uint32_t cdef_tab[];
+__host__ __device__ inline int cdef_tab_half(int damping) { return damping >= 7 ? 256 : damping <= 3 ? 16 : 2 << damping; }   // 256 covers every 8-bit difference
+__host__ __device__ inline int cdef_tab_bytes(int damping, bool pri) { return (2 * cdef_tab_half(damping) + 1) * (pri ? 36 : 4); }
+struct CdefTab { int n, s0, p0, p1; };   // half size; dword index of each table's first entry (d = -n)
+__device__ __forceinline__ CdefTab cdef_tab_layout(int damping, bool pri) {
+    CdefTab tb;
+    tb.n = cdef_tab_half(damping);
+    const int ne = 2 * tb.n + 1;
+    tb.p0 = 0; tb.p1 = 4 * ne; tb.s0 = pri ? 8 * ne : 0;
+    return tb;
+}
+// by the whole workgroup, before a barrier; entries come from constrain() above
+__device__ __forceinline__ void build_cdef_tables(const CdefTab& tb, bool pri, int damping, int tid, int nt) {
+    const int n = tb.n, ne = 2 * n + 1;
+    for (int e = tid; e < ne; e += nt) {
+        const int d = e - n;
+        uint32_t v = 0x00040404u;
+        if (abs(d) < n) {
+            const int c1 = constrain(d, 1, max(0, damping)), c2 = constrain(d, 2, max(0, damping - 1)), c4 = constrain(d, 4, max(0, damping - 2));
+            v = (uint32_t)(4 + c2) | (uint32_t)(4 + c1) << 8 | (uint32_t)(4 + c4) << 16;
+        }
+        cdef_tab[tb.s0 + e] = v;
+    }
+    if (!pri) return;
+    for (int it = tid; it < ne * 4; it += nt) {   // dword m (strengths 4m .. 4m + 3) of entry e, for both distances
+        const int e = it >> 2, m = it & 3, d = e - n;
+        uint32_t v0 = 0x40404040u, v1 = 0x40404040u;
+        if (abs(d) < n) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int t = 4 * m + j;
+                const int c = t ? constrain(d, t, max(0, damping - msb(t))) : 0;
+                v0 += (uint32_t)(((j & 1) ? 3 : 4) * c) << (8 * j);   // byte sums stay inside 8..120: adding a negative product borrows from no neighbour's final value
+                v1 += (uint32_t)(((j & 1) ? 3 : 2) * c) << (8 * j);
+            }
+        }
+        cdef_tab[tb.p0 + it] = v0; cdef_tab[tb.p1 + it] = v1;
+    }
+}
+// xb = n - x, once per pixel: entry index of a tap = its difference + n, clamped to 0..2n.  A difference below -n wraps to a large unsigned value and lands on the
+// upper end entry, which is zero like the lower one.
+__device__ __forceinline__ uint32_t tab_index(int tap, int xb, int n) { return min((uint32_t)(tap + xb), (uint32_t)(2 * n)); }
+__device__ __forceinline__ uint32_t sec_entry(const CdefTab& tb, int tap, int xb) { return cdef_tab[tb.s0 + tab_index(tap, xb, tb.n)]; }
+__device__ __forceinline__ uint4 pri_entry(const CdefTab& tb, int k, int tap, int xb) { return *(const uint4*)&cdef_tab[(k ? tb.p1 : tb.p0) + 4 * tab_index(tap, xb, tb.n)]; }
+// acc0 / acc1: sums of the four S entries of distance 0 / 1 -> ((0, sec 1), (sec 2, sec 4))
+__device__ __forceinline__ void unpack_sec(uint32_t acc0, uint32_t acc1, s16x2 (&sec)[2]) {
+    const uint32_t tot = 2 * acc0 + acc1;
+    sec[0] = __builtin_bit_cast(s16x2, (tot << 8) & 0x00FF0000u) - pack2(0, 48);
+    sec[1] = __builtin_bit_cast(s16x2, tot & 0x00FF00FFu) - dup2(48);
+}
+
 struct PixelTerms {
     s16x2 x2;          // (x, x)
     s16x2 pri2[16];    // (pri sum, pri sum); [0] = 0
@@ -198,13 +262,18 @@ __device__ __forceinline__ int dir_offset(int dir, int tstride) {
 // The A part of a pixel's terms -- everything that filters along the block's direction.
 // tile points at the pixel; tstride in elements.  t_of[idx] = effective primary strength of index idx
 // (luma: adjusted by the block variance; PLAIN_T, chroma: idx << cs, not read), cs = coeff_shift, damping already includes "+ cs - (pli != 0)".
-template <bool PLAIN_T>
-__device__ __forceinline__ void pixel_terms_a(const uint16_t* px, int tstride, int dir, const int (&t_of)[16], int cs, int damping,
+// TAB (8-bit planes, cs == 0): the secondary sums, and with PLAIN_T the primary sums, come from the constrain() tables tb instead of the packed arithmetic.
+template <bool PLAIN_T, bool TAB>
+__device__ __forceinline__ void pixel_terms_a(const uint16_t* px, int tstride, int dir, const int (&t_of)[16], int cs, int damping, const CdefTab& tb,
                                               PixelTerms& T) {
+    constexpr bool PRI_TAB = TAB && PLAIN_T;
     const int x = (int)(int16_t)px[0];
     const s16x2 x2 = dup2(x);
     T.x2 = x2;
+    const int xb = tb.n - x;   // tab_index
     TapPair pp[2], sa[2][2];
+    uint32_t sacc[2] = {0, 0};
+    uint4 pacc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     s16x2 mnA = x2, mxA = x2;
     const int d2 = (dir + 2) & 7, d6 = (dir + 6) & 7;
     const int o[2] = {dir_offset<0>(dir, tstride), dir_offset<1>(dir, tstride)};
@@ -212,46 +281,60 @@ __device__ __forceinline__ void pixel_terms_a(const uint16_t* px, int tstride, i
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const int p0 = px[o[k]], p1 = px[-o[k]], a0 = px[o2[k]], a1 = px[-o2[k]], a2 = px[o6[k]], a3 = px[-o6[k]];
-        pp[k] = make_pair(p0, p1, x2); sa[k][0] = make_pair(a0, a1, x2); sa[k][1] = make_pair(a2, a3, x2);
+        if (PRI_TAB) { const uint4 e0 = pri_entry(tb, k, p0, xb), e1 = pri_entry(tb, k, p1, xb); pacc[k] = uint4{e0.x + e1.x, e0.y + e1.y, e0.z + e1.z, e0.w + e1.w}; }
+        else pp[k] = make_pair(p0, p1, x2);
+        if (TAB) sacc[k] = sec_entry(tb, a0, xb) + sec_entry(tb, a1, xb) + sec_entry(tb, a2, xb) + sec_entry(tb, a3, xb);
+        else { sa[k][0] = make_pair(a0, a1, x2); sa[k][1] = make_pair(a2, a3, x2); }
         minmax_pair(p0, p1, mnA, mxA); minmax_pair(a0, a1, mnA, mxA); minmax_pair(a2, a3, mnA, mxA);
     }
     // fold the two halves of the running min / max and duplicate
     T.mnA = __builtin_elementwise_min(mnA, mnA.yx); T.mxA = __builtin_elementwise_max(mxA, mxA.yx);
-    // primary: eb_cdef_pri_taps (EbCdef.c:198) = {4, 2} or {3, 3} by the parity of (t >> cs)
-    const s16x2 w40 = signed_weight(pp[0], 4), w30 = signed_weight(pp[0], 3), w21 = signed_weight(pp[1], 2), w31 = signed_weight(pp[1], 3);
     T.pri2[0] = dup2(0);
-    if (PLAIN_T) {
-        // chroma: t = idx << cs, so |d| >> shift depends on the index only through msb(idx) -- four classes for indices 1..15: one shifted pair per class
-        // instead of one per strength -- and the tap weights through its parity
-        u16x2 sh0 = pp[0].a, sh1 = pp[1].a;
+    if (PRI_TAB) {
+        // chroma: strength idx is byte idx of both distances' accumulators, each biased by 2 x 64
+        const uint32_t w0[4] = {pacc[0].x, pacc[0].y, pacc[0].z, pacc[0].w}, w1[4] = {pacc[1].x, pacc[1].y, pacc[1].z, pacc[1].w};
 #pragma unroll
         for (int idx = 1; idx < 16; idx++) {
-            if ((idx & (idx - 1)) == 0) {   // first index of a class
-                const int shift = max(0, damping - cs - (31 - __builtin_clz(idx)));   // = damping - msb(idx << cs)
-                sh0 = pp[0].a >> (unsigned short)shift; sh1 = pp[1].a >> (unsigned short)shift;
-            }
-            int s = constrain_shifted(pp[0].a, sh0, (idx & 1) ? w30 : w40, idx << cs, 0);
-            s = constrain_shifted(pp[1].a, sh1, (idx & 1) ? w31 : w21, idx << cs, s);
+            const int s = (int)((w0[idx >> 2] >> (8 * (idx & 3))) & 0xFFu) + (int)((w1[idx >> 2] >> (8 * (idx & 3))) & 0xFFu) - 256;
             T.pri2[idx] = dup2(s);
         }
     } else {
+        // primary: eb_cdef_pri_taps (EbCdef.c:198) = {4, 2} or {3, 3} by the parity of (t >> cs)
+        const s16x2 w40 = signed_weight(pp[0], 4), w30 = signed_weight(pp[0], 3), w21 = signed_weight(pp[1], 2), w31 = signed_weight(pp[1], 3);
+        if (PLAIN_T) {
+            // chroma: t = idx << cs, so |d| >> shift depends on the index only through msb(idx) -- four classes for indices 1..15: one shifted pair per class
+            // instead of one per strength -- and the tap weights through its parity
+            u16x2 sh0 = pp[0].a, sh1 = pp[1].a;
 #pragma unroll
-        for (int idx = 1; idx < 16; idx++) {
-            const int t = t_of[idx];   // wave-uniform
-            // luma: adjust_strength() maps the 16 frame-header strengths onto fewer effective ones in a low-variance block (it is monotone, so equal values are
-            // neighbours): the sum of a repeated value is the previous index's
-            if (t == t_of[idx - 1]) { T.pri2[idx] = T.pri2[idx - 1]; continue; }
-            int s = 0;
-            if (t) {
-                const int shift = max(0, damping - msb(t));
-                const bool odd = (t >> cs) & 1;
-                s = constrain_pair(pp[0], odd ? w30 : w40, t, shift, 0);
-                s = constrain_pair(pp[1], odd ? w31 : w21, t, shift, s);
+            for (int idx = 1; idx < 16; idx++) {
+                if ((idx & (idx - 1)) == 0) {   // first index of a class
+                    const int shift = max(0, damping - cs - (31 - __builtin_clz(idx)));   // = damping - msb(idx << cs)
+                    sh0 = pp[0].a >> (unsigned short)shift; sh1 = pp[1].a >> (unsigned short)shift;
+                }
+                int s = constrain_shifted(pp[0].a, sh0, (idx & 1) ? w30 : w40, idx << cs, 0);
+                s = constrain_shifted(pp[1].a, sh1, (idx & 1) ? w31 : w21, idx << cs, s);
+                T.pri2[idx] = dup2(s);
             }
-            T.pri2[idx] = dup2(s);
+        } else {
+#pragma unroll
+            for (int idx = 1; idx < 16; idx++) {
+                const int t = t_of[idx];   // wave-uniform
+                // luma: adjust_strength() maps the 16 frame-header strengths onto fewer effective ones in a low-variance block (it is monotone, so equal values are
+                // neighbours): the sum of a repeated value is the previous index's
+                if (t == t_of[idx - 1]) { T.pri2[idx] = T.pri2[idx - 1]; continue; }
+                int s = 0;
+                if (t) {
+                    const int shift = max(0, damping - msb(t));
+                    const bool odd = (t >> cs) & 1;
+                    s = constrain_pair(pp[0], odd ? w30 : w40, t, shift, 0);
+                    s = constrain_pair(pp[1], odd ? w31 : w21, t, shift, s);
+                }
+                T.pri2[idx] = dup2(s);
+            }
         }
     }
     // secondary: eb_cdef_sec_taps {2, 1}; strengths 1, 2, 4 (index 3 means 4: "sec += sec == 3")
+    if (TAB) { unpack_sec(sacc[0], sacc[1], T.secA); return; }
     s16x2 wa[2][2];
 #pragma unroll
     for (int k = 0; k < 2; k++)
@@ -275,7 +358,8 @@ __device__ __forceinline__ void pixel_terms_a(const uint16_t* px, int tstride, i
 // The B part: the direction-0 variant that serves primary index 0 (pri == 0 -> filter_block is called with dir 0, EbCdef.c:371): its primary taps only
 // feed min/max.  sums = false (wave-uniform) computes the min/max alone -- for a block of direction 4, whose secondary taps (directions 6 and 2) are B's
 // (2 and 6) with the same weights, so that secB = secA.  A block of direction 0 needs no B part at all: B is A, term for term (pixel_terms_b_is_a).
-__device__ __forceinline__ void pixel_terms_b(const uint16_t* px, int tstride, int cs, int damping, bool sums, PixelTerms& T) {
+template <bool TAB>
+__device__ __forceinline__ void pixel_terms_b(const uint16_t* px, int tstride, int cs, int damping, bool sums, const CdefTab& tb, PixelTerms& T) {
     const s16x2 x2 = T.x2;
     int bt[2][4];
     s16x2 mnB = x2, mxB = x2;
@@ -289,6 +373,14 @@ __device__ __forceinline__ void pixel_terms_b(const uint16_t* px, int tstride, i
     T.mnB = __builtin_elementwise_min(mnB, mnB.yx); T.mxB = __builtin_elementwise_max(mxB, mxB.yx);
     T.secB[0] = T.secA[0]; T.secB[1] = T.secA[1];
     if (!sums) return;
+    if (TAB) {
+        const int xb = tb.n - (int)x2.x;
+        uint32_t sacc[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) sacc[k] = sec_entry(tb, bt[k][0], xb) + sec_entry(tb, bt[k][1], xb) + sec_entry(tb, bt[k][2], xb) + sec_entry(tb, bt[k][3], xb);
+        unpack_sec(sacc[0], sacc[1], T.secB);
+        return;
+    }
     TapPair sb[2][2];
     s16x2 wb[2][2];
 #pragma unroll
@@ -313,12 +405,12 @@ __device__ __forceinline__ void pixel_terms_b_is_a(PixelTerms& T) {
     T.secB[0] = T.secA[0]; T.secB[1] = T.secA[1]; T.mnB = T.mnA; T.mxB = T.mxA;
 }
 // uniform_dir: the direction every live pixel of the wave has, or -1 when they differ (then, and for every direction but 0 and 4, the whole B part runs)
-template <bool PLAIN_T>
+template <bool PLAIN_T, bool TAB>
 __device__ __forceinline__ void pixel_terms(const uint16_t* px, int tstride, int dir, int uniform_dir, const int (&t_of)[16], int cs, int damping,
-                                            PixelTerms& T) {
-    pixel_terms_a<PLAIN_T>(px, tstride, dir, t_of, cs, damping, T);
+                                            const CdefTab& tb, PixelTerms& T) {
+    pixel_terms_a<PLAIN_T, TAB>(px, tstride, dir, t_of, cs, damping, tb, T);
     if (uniform_dir == 0) pixel_terms_b_is_a(T);
-    else pixel_terms_b(px, tstride, cs, damping, uniform_dir != 4, T);
+    else pixel_terms_b<TAB>(px, tstride, cs, damping, uniform_dir != 4, tb, T);
 }
 
 // filtered values of strengths (pri_idx, 2 * pair) and (pri_idx, 2 * pair + 1): y = x + ((8 + sum - (sum < 0)) >> 4), clamped
@@ -430,9 +522,13 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
         if (tid < 64 && dir_out) { dir_out[fb * 64 + tid] = 0; var_out[fb * 64 + tid] = 0; }
         return;
     }
+    constexpr bool TAB = sizeof(PIX) == 1;   // 8-bit planes: coeff_shift is 0 and the secondary sums come from the constrain() table
+    if (TAB) cs = 0;
+    const int damping = pri_damping + cs;  // pli == 0 (EbCdef.c:306-307)
+    const CdefTab tb = cdef_tab_layout(damping, false);
+    if (TAB) build_cdef_tables(tb, false, damping, tid, 256);
     stage_tile(tile, TS, rec, rec_stride, w, h, 64 * fbc, 64 * fbr, 64, 64, tid, 256);
     __syncthreads();
-    const int damping = pri_damping + cs;  // pli == 0 (EbCdef.c:306-307)
     unsigned long long acc = 0;            // lane g: sum over this wave's blocks of dist(block, strength g)
     const int i = lane >> 3, j = lane & 7;
     const DirBins bins = load_dir_bins(lane);
@@ -450,7 +546,7 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
 #pragma unroll
         for (int idx = 0; idx < 16; idx++) t_of[idx] = adjust_strength(idx << cs, var);
         PixelTerms T;
-        pixel_terms<false>(px, TS, dir, dir, t_of, cs, damping, T);   // dir is wave-uniform here
+        pixel_terms<false, TAB>(px, TS, dir, dir, t_of, cs, damping, tb, T);   // dir is wave-uniform here
         // Primary indices whose effective strength equals the previous index's filter identically (same sums, same direction, same clamps): only the first index of
         // such a run is combined and stored; rep4 = 16 x 4 bits, the first index of every index's run (wave-uniform).  A block of low directional variance has 5 .. 9
         // distinct effective strengths out of 16 (adjust_strength, EbCdef.c:112-116).
@@ -511,10 +607,14 @@ cdef_search_chroma_kernel(const PIX* __restrict__ rec_u, const PIX* __restrict__
     int any = 0;
     for (int b = lane; b < 64; b += 64) { const int by = b >> 3, bx = b & 7; if (by < nby && bx < nbx && !skip8[(8 * fbr + by) * c8 + 8 * fbc + bx]) any = 1; }
     if (!__any(any)) return;
+    constexpr bool TAB = sizeof(PIX) == 1;   // 8-bit planes: coeff_shift is 0, primary and secondary sums come from the constrain() tables
+    if (TAB) cs = 0;
+    const int damping = pri_damping + cs - 1;  // pli != 0
+    const CdefTab tb = cdef_tab_layout(damping, true);
+    if (TAB) build_cdef_tables(tb, true, damping, tid, 256);
     stage_tile(tile[0], TS, rec_u, rec_stride, w >> 1, h >> 1, 32 * fbc, 32 * fbr, 32, 32, tid, 256);
     stage_tile(tile[1], TS, rec_v, rec_stride, w >> 1, h >> 1, 32 * fbc, 32 * fbr, 32, 32, tid, 256);
     __syncthreads();
-    const int damping = pri_damping + cs - 1;  // pli != 0
     unsigned long long acc[2] = {0, 0};
     // a pass = 4 horizontally adjacent 4x4 blocks (one 4x16 strip); lane -> (block q, row i, col j)
     const int q = lane >> 4, i = (lane >> 2) & 3, j = lane & 3;
@@ -534,7 +634,7 @@ cdef_search_chroma_kernel(const PIX* __restrict__ rec_u, const PIX* __restrict__
 #pragma unroll
             for (int idx = 0; idx < 16; idx++) t_of[idx] = idx << cs;
             PixelTerms T;
-            pixel_terms<true>(px, TS, dir, uniform_dir, t_of, cs, damping, T);
+            pixel_terms<true, TAB>(px, TS, dir, uniform_dir, t_of, cs, damping, tb, T);
 #pragma unroll
             for (int g = 0; g < 64; g += 2) {
                 const s16x2 y = combine2(T, g >> 2, (g >> 1) & 1);
@@ -674,9 +774,13 @@ extern "C" int svt_hip_launch_cdef_search(hipStream_t st, int pix_bytes, const v
     const int nfb = ((w + 63) >> 6) * ((h + 63) >> 6);
     svt_for_pix(pix_bytes, [&](auto f) {
         using PIX = typename decltype(f)::pix;
-        hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[0], rec_stride[0], (const PIX*)src[0], src_stride[0], w, h, skip8,
+        // 8-bit planes: the constrain() tables of this launch's damping live in dynamic LDS (luma: secondary; chroma, one less damping: primary + secondary).
+        // At the frame-header dampings 3..6 that is 132..1028 and 1188..4644 bytes, inside what four workgroups per compute unit leave.
+        const bool tab = sizeof(PIX) == 1;
+        const size_t lds_y = tab ? cdef_tab_bytes(pri_damping, false) : 0, lds_uv = tab ? cdef_tab_bytes(pri_damping - 1, true) : 0;
+        hipLaunchKernelGGL((cdef_search_luma_kernel<PIX>), dim3(nfb), dim3(256), lds_y, st, (const PIX*)rec[0], rec_stride[0], (const PIX*)src[0], src_stride[0], w, h, skip8,
                            pri_damping, cs, mse, dir_buf, var_buf);
-        hipLaunchKernelGGL((cdef_search_chroma_kernel<PIX>), dim3(nfb), dim3(256), 0, st, (const PIX*)rec[1], (const PIX*)rec[2], rec_stride[1], (const PIX*)src[1],
+        hipLaunchKernelGGL((cdef_search_chroma_kernel<PIX>), dim3(nfb), dim3(256), lds_uv, st, (const PIX*)rec[1], (const PIX*)rec[2], rec_stride[1], (const PIX*)src[1],
                            (const PIX*)src[2], src_stride[1], w, h, skip8, pri_damping, cs, mse + (size_t)nfb * 64, dir_buf);
     });
     return (int)hipGetLastError();
