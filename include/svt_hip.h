@@ -1131,7 +1131,7 @@ int svt_hip_screen_content_detect_dev(SvtHipCtx *ctx, int pix_bytes, int bd, con
  * reset per value; a 2x2 block hashes its 4 sample bytes or the 8 bytes of its four 16-bit samples in memory order, a larger block the 16 bytes of its four
  * children's hashes as little-endian words.  Every device entry point is stream-ordered and asynchronous: no allocation, no host synchronisation, no read-back; what
  * it refuses it refuses before any launch.  width, height <= 32767 (an entry's int16), width * height within 31 bits, stride >= width.  The diamond and mesh
- * searches around the hash search, and a hook in the encoder, are not covered. */
+ * searches around the hash search and the final choice are svt_hip_ibc_full_search_batch_dev below; a hook in the encoder is not covered. */
 #define SVT_HIP_IBC_HASH_BUCKETS (1 << 19)
 #define SVT_HIP_IBC_MV_VALS 32767
 typedef struct {
@@ -1199,6 +1199,51 @@ int svt_hip_ibc_hash_table_host(int pix_bytes, int bd, const void *luma, int str
 int svt_hip_ibc_hash_search_host(int pix_bytes, int bd, const void *luma, int stride, int width, int height, const int32_t *bucket_start,
                                  const SvtHipIbcHashEntry *entries, const int32_t *mv_joint_cost, const int32_t *mv_comp_cost, const SvtHipIbcSearchJob *jobs, int njobs,
                                  SvtHipIbcSearchResult *results);
+/* svt_av1_full_pixel_search (Encoder/Codec/av1me.c:1256-1414) whole, for a list of blocks: per job the vector intra_bc_search would put into dv_cand[], with the
+ * stages' own results.  In the reference's order: full_pixel_diamond (av1me.c:578-643: svt_av1_diamond_search_sad_c, :437-573, on the sites of
+ * svt_av1_init3smotion_compensation at step_param and at the later steps its num00 bookkeeping keeps, each winner re-costed by svt_av1_get_mvpred_var, then
+ * svt_av1_refining_search_sad, :712-775); when exhaustive_allowed and var > ((1 << 25) >> (10 - log2(block_w / 4) - log2(block_h / 4))) << ibc_shift,
+ * full_pixel_exhaustive (:650-710) over exhuastive_mesh_search (:346-435), which wins on var_ex < var; then case NSTEP's tail (:1306-1411): the hash search above
+ * for a square block when use_hash, which wins on best_hash_cost < var; last the caller's av1_is_dv_valid of the final vector (Encoder/Codec/EbModeDecision.c:4523)
+ * as dv_valid.  SAD is the plain sum of absolute differences and the variance svt_aom_variance{W}x{H} (bd 10: the form of svt_aom_highbd_10_variance) at every
+ * format.  The mesh reproduces the reference's scan exactly, including the last column it never examines when a row of step 1 has a number of columns that is
+ * no multiple of 4 (:413-429).  x->second_best_mv is not produced: nothing on this path reads it.  mv_check_bounds (EbModeDecision.c:4522) is left out: it cannot
+ * fire on a vector inside limits that are a subset of the outer ones (:4479-4482).
+ *   mesh_patterns : HOST int32[8], {range, interval} x 4 (sf->mesh_patterns).  An invalid FIRST pattern is the reference's `return INT_MAX`: mesh_ran = 1,
+ *                   mesh_passes = 0, mesh_var = INT32_MAX, not taken.  A later pattern the walk can reach with interval < 1 or range outside 1 .. 256 refuses the call
+ *   d_bucket_start, d_entries : the table, or both NULL; then a job that sets use_hash is a bad job
+ * A job is bad (status -1) when its shape is not one of the 22 block sizes 4x4 .. 128x128, the block is not inside the picture, a vector inside the limits would
+ * put the block outside the picture (the reference would read padding this ABI does not have), the limits reach further than 2047 whole samples from ref_mv >> 3
+ * (that keeps every cost-table index within -16383 .. 16383), step_param is outside 0 .. 10, sad_per_bit or error_per_bit is negative, ibc_shift is not 0 or 1, or
+ * the tile and mib_size_log2 fields fail SvtHipIbcSearchJob's rule.  Whenever status != 0 every other field is as for "nothing found": the vars INT32_MAX, hash
+ * {0, 0, 0, 0, INT32_MAX, 0, 0}, all else 0.  Stream-ordered and asynchronous; a fixed number of launches whatever the data; njobs <= 2^24; d_scratch at
+ * least svt_hip_ibc_full_search_scratch_bytes(njobs), 256-byte aligned. */
+typedef struct {
+    int32_t x_pos, y_pos, block_w, block_h;
+    int32_t intra;                                  /* as SvtHipIbcSearchJob */
+    int32_t col_min, col_max, row_min, row_max;     /* x->mv_limits as svt_av1_full_pixel_search sees them, whole samples */
+    int32_t ref_mv_row, ref_mv_col;                 /* dv_ref, 1/8 sample */
+    int32_t mvp_row, mvp_col;                       /* mvp_full, whole samples */
+    int32_t step_param, sad_per_bit, error_per_bit;
+    int32_t exhaustive_allowed, ibc_shift, use_hash;
+    int32_t mi_row_start, mi_row_end, mi_col_start, mi_col_end, mib_size_log2;
+} SvtHipIbcFullSearchJob;
+typedef struct {
+    int32_t status;                                 /* 0 searched; 1 empty limits (the caller's `continue`, EbModeDecision.c:4486-4490); -1 bad job */
+    int32_t dia_passes, dia_refined, dia_var, dia_row, dia_col;   /* diamond passes walked, the refinement ran, full_pixel_diamond's value and vector */
+    int32_t mesh_ran, mesh_passes, mesh_var, mesh_row, mesh_col;  /* the threshold let the mesh run, scans made, full_pixel_exhaustive's value and vector */
+    SvtHipIbcSearchResult hash;                     /* untouched semantics; count = 0, found = 0 when the hash tail does not apply */
+    int32_t source;                                 /* 0 diamond, 1 mesh, 2 hash */
+    int32_t var, best_row, best_col, dv_valid;
+} SvtHipIbcFullSearchResult;
+size_t svt_hip_ibc_full_search_scratch_bytes(int njobs);   /* 0 for njobs < 0 */
+int svt_hip_ibc_full_search_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_luma, int stride, int width, int height, const int32_t *d_bucket_start,
+                                      const SvtHipIbcHashEntry *d_entries, const int32_t *d_mv_joint_cost, const int32_t *d_mv_comp_cost, const int32_t *mesh_patterns,
+                                      const SvtHipIbcFullSearchJob *d_jobs, int njobs, SvtHipIbcFullSearchResult *d_results, void *d_scratch, size_t scratch_bytes);
+/* the same on host pointers, serially, from csrc/ibc_search.h: no context, no scratch */
+int svt_hip_ibc_full_search_host(int pix_bytes, int bd, const void *luma, int stride, int width, int height, const int32_t *bucket_start,
+                                 const SvtHipIbcHashEntry *entries, const int32_t *mv_joint_cost, const int32_t *mv_comp_cost, const int32_t *mesh_patterns,
+                                 const SvtHipIbcFullSearchJob *jobs, int njobs, SvtHipIbcFullSearchResult *results);
 /* open_loop_intra_search_mb (Encoder/Codec/EbMotionEstimation.c:3043-3155, called from the motion-estimation process when the look-ahead model is on) for every
  * 16x16 macroblock of an 8-bit luma picture, one launch: neighbours from the SOURCE picture (update_neighbor_samples_array_open_loop_mb,
  * Encoder/Codec/EbEncIntraPrediction.c:1201), for mode = DC_PRED .. mode_end the edges conditioned by filter_intra_edge (Common/Codec/EbIntraPrediction.c:2545), the

@@ -370,6 +370,19 @@ class IbcSearchResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("count", "n_matched", "n_valid", "found", "best_cost", "best_row", "best_col")]
 
 
+class IbcFullSearchJob(C.Structure):
+    """SvtHipIbcFullSearchJob (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("x_pos", "y_pos", "block_w", "block_h", "intra", "col_min", "col_max", "row_min", "row_max", "ref_mv_row", "ref_mv_col", "mvp_row",
+                                         "mvp_col", "step_param", "sad_per_bit", "error_per_bit", "exhaustive_allowed", "ibc_shift", "use_hash", "mi_row_start",
+                                         "mi_row_end", "mi_col_start", "mi_col_end", "mib_size_log2")]
+
+
+class IbcFullSearchResult(C.Structure):
+    """SvtHipIbcFullSearchResult (include/svt_hip.h)."""
+    _fields_ = ([(n, C.c_int32) for n in ("status", "dia_passes", "dia_refined", "dia_var", "dia_row", "dia_col", "mesh_ran", "mesh_passes", "mesh_var", "mesh_row",
+                                          "mesh_col")] + [("hash", IbcSearchResult)] + [(n, C.c_int32) for n in ("source", "var", "best_row", "best_col", "dv_valid")])
+
+
 IBC_HASH_BUCKETS = 1 << 19   # SVT_HIP_IBC_HASH_BUCKETS
 IBC_MV_VALS = 32767          # SVT_HIP_IBC_MV_VALS
 IBC_ENTRY_DTYPE = [("x", "<i2"), ("y", "<i2"), ("hash_value2", "<u4")]   # SvtHipIbcHashEntry as a numpy record
@@ -406,6 +419,30 @@ def ibc_hash_search_host(plane, bucket_start, entries, joint_cost, comp_cost, jo
                                             j.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.cast(jobs, C.c_void_p), len(jobs), C.cast(res, C.c_void_p))
     if rc != 0:
         raise RuntimeError(f"svt_hip_ibc_hash_search_host refused its arguments: status {rc}")
+    return res
+
+
+def ibc_mesh_patterns(patterns):
+    """[(range, interval), ...], at most four -> int32[8] as svt_hip_ibc_full_search_* take them; the patterns left out are (0, 0)"""
+    p = np.zeros(8, np.int32)
+    flat = np.asarray(patterns, np.int32).reshape(-1)
+    assert flat.size <= 8 and flat.size % 2 == 0
+    p[:flat.size] = flat
+    return p
+
+
+def ibc_full_search_host(plane, table, joint_cost, comp_cost, patterns, jobs, bd=None):
+    """svt_hip_ibc_full_search_host: `jobs` a ctypes array of IbcFullSearchJob; `table` (bucket_start, entries) as ibc_hash_table_host returns them, or None;
+    `patterns` [(range, interval), ...].  -> IbcFullSearchResult * njobs."""
+    pb, p, stride, w, h = _plane_args(plane)
+    j, c = ibc_cost_tables(joint_cost, comp_cost)
+    pat = ibc_mesh_patterns(patterns)
+    res = (IbcFullSearchResult * max(len(jobs), 1))()
+    b, e = (table[0].ctypes.data_as(C.c_void_p), table[1].ctypes.data_as(C.c_void_p)) if table is not None else (None, None)
+    rc = lib().svt_hip_ibc_full_search_host(pb, default_bd(pb, bd), p, stride, w, h, b, e, j.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                                            pat.ctypes.data_as(C.c_void_p), C.cast(jobs, C.c_void_p), len(jobs), C.cast(res, C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_ibc_full_search_host refused its arguments: status {rc}")
     return res
 
 
@@ -669,6 +706,10 @@ PROTOTYPES = {
     "svt_hip_ibc_hash_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
     "svt_hip_ibc_hash_table_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, C.c_int64, vp, vp, sz]),
     "svt_hip_ibc_hash_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    # ---- intra block copy: diamond, mesh and the final choice
+    "svt_hip_ibc_full_search_scratch_bytes": (sz, [i32]),
+    "svt_hip_ibc_full_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, sz]),
+    "svt_hip_ibc_full_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     # ---- TPL flow dispenser
     "svt_hip_tpl_dispenser_scratch_bytes": (sz, [i32, i32]),
     "svt_hip_tpl_dispenser_picture_dev": (i32, [vp, P(TplParams), vp, i32, P(TplRef), vp, vp, vp, vp, vp, i32, vp, vp]),
@@ -967,6 +1008,30 @@ class Context:
             self.call("ibc_hash_search_batch_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, d_b, d_e, d_jc, d_cc, d_j, len(jobs), d_r)
             self.sync()
             return s.structs_back(d_r, type(res))
+
+    def ibc_full_search_batch(self, plane, table, joint_cost, comp_cost, patterns, jobs, bd=None, guard=0, fill=0xC3):
+        """svt_hip_ibc_full_search_batch_dev: `table` (bucket_start, entries) as ibc_hash_table returns them, or None; `patterns` [(range, interval), ...]; `jobs` a
+        ctypes array of IbcFullSearchJob.  The results start as the byte `fill`; `guard` bytes (a multiple of 256) of it lie before and behind the results and the
+        scratch.  -> (IbcFullSearchResult * njobs, the four guard areas as uint8 arrays)."""
+        h, w = plane.shape
+        j, c = ibc_cost_tables(joint_cost, comp_cost)
+        pat = ibc_mesh_patterns(patterns)
+        n = len(jobs)
+        kind = IbcFullSearchResult * max(n, 1)
+        nb_r, nb_s = C.sizeof(kind), self.L.svt_hip_ibc_full_search_scratch_bytes(n)
+        assert guard % 256 == 0
+        with self.scope() as s:
+            p = s.plane(plane)
+            d_b, d_e = (None, None) if table is None else (s.upload(np.ascontiguousarray(table[0], np.int32)), s.upload(np.frombuffer(table[1].tobytes() + bytes(8), np.uint8)))
+            d_jc, d_cc = s.upload(j), s.upload(c)
+            d_j = s.structs(jobs if n else (IbcFullSearchJob * 1)())
+            d_r, d_s = s.filled(nb_r + 2 * guard, fill, np.uint8), s.filled(max(nb_s, 256) + 2 * guard, fill, np.uint8)
+            self.call("ibc_full_search_batch_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, d_b, d_e, d_jc, d_cc,
+                      pat.ctypes.data_as(C.c_void_p), d_j, n, d_r.value + guard, d_s.value + guard, nb_s)
+            self.sync()
+            r, sc = s.download(d_r, (nb_r + 2 * guard,), np.uint8), s.download(d_s, (max(nb_s, 256) + 2 * guard,), np.uint8)
+            res = kind.from_buffer_copy(r[guard:guard + nb_r].tobytes())
+            return res, (r[:guard], r[guard + nb_r:], sc[:guard], sc[guard + nb_s:])
 
     def filter_intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D

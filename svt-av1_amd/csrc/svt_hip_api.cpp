@@ -13,6 +13,7 @@
 #include "tpl_synth.h"
 #include "resize_plan.h"
 #include "ibc_hash.h"
+#include "ibc_search.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -261,7 +262,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -381,6 +382,27 @@ int svt_hip_ibc_hash_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const
     return launched(c, svt_hip_launch_ibc_hash_search(c->stream, pix_bytes, bd, d_luma, stride, width, height, d_bucket_start, d_entries, d_mv_joint_cost, d_mv_comp_cost,
                                                       d_jobs, njobs, d_results),
                     "intra-block-copy hash search launch");
+}
+
+/* ---------------------------------------------------------------------------------- intra block copy: diamond, mesh and the final choice (ibc_search.hip) */
+size_t svt_hip_ibc_full_search_scratch_bytes(int njobs) { return njobs < 0 ? 0 : ibcs::full_scratch(njobs).total; }
+
+int svt_hip_ibc_full_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_luma, int stride, int width, int height, const int32_t* d_bucket_start,
+                                      const SvtHipIbcHashEntry* d_entries, const int32_t* d_mv_joint_cost, const int32_t* d_mv_comp_cost, const int32_t* mesh_patterns,
+                                      const SvtHipIbcFullSearchJob* d_jobs, int njobs, SvtHipIbcFullSearchResult* d_results, void* d_scratch, size_t scratch_bytes) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_luma || !d_mv_joint_cost || !d_mv_comp_cost || !d_jobs || !d_results || njobs < 0 || njobs > ibcs::MAX_JOBS || !ibc::fmt_ok(pix_bytes, bd) ||
+        !ibc::picture_ok(stride, width, height))
+        return bad_arg(c, "svt_hip_ibc_full_search_batch_dev: bad argument");
+    if (!d_bucket_start != !d_entries) return bad_arg(c, "svt_hip_ibc_full_search_batch_dev: bad argument (the two table pointers are both given or both NULL)");
+    if (!ibcs::patterns_ok(mesh_patterns))
+        return bad_arg(c, "svt_hip_ibc_full_search_batch_dev: bad argument (a mesh pattern the walk can reach has interval < 1 or range outside 1 .. 256)");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255) || scratch_bytes < ibcs::full_scratch(njobs).total)
+        return bad_arg(c, "svt_hip_ibc_full_search_batch_dev: bad argument (d_scratch: svt_hip_ibc_full_search_scratch_bytes(njobs), 256-byte aligned)");
+    if (!njobs) return SVT_HIP_OK;
+    return launched(c, svt_hip_launch_ibc_full_search(c->stream, pix_bytes, bd, d_luma, stride, width, height, d_bucket_start, d_entries, d_mv_joint_cost, d_mv_comp_cost,
+                                                      mesh_patterns, d_jobs, njobs, d_results, d_scratch),
+                    "intra-block-copy full search launch");
 }
 
 /* ---------------------------------------------------------------------------------- TPL dispenser */

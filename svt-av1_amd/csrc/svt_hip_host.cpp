@@ -9,6 +9,7 @@
 #include "tpl_synth.h"
 #include "palette.h"
 #include "ibc_hash.h"
+#include "ibc_search.h"
 
 extern "C" {
 
@@ -322,6 +323,16 @@ int svt_hip_ibc_hash_search_host(int pix_bytes, int bd, const void* luma, int st
                                  const int32_t* mv_joint_cost, const int32_t* mv_comp_cost, const SvtHipIbcSearchJob* jobs, int njobs, SvtHipIbcSearchResult* results) {
     if (!ibc::search_args_ok(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, jobs, njobs, results)) return SVT_HIP_ERR_BAD_ARG;
     ibc::search_host(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, jobs, njobs, results);
+    return SVT_HIP_OK;
+}
+
+/* the contract of svt_hip_ibc_full_search_batch_dev on host pointers: ibc_search.h run serially */
+int svt_hip_ibc_full_search_host(int pix_bytes, int bd, const void* luma, int stride, int width, int height, const int32_t* bucket_start, const SvtHipIbcHashEntry* entries,
+                                 const int32_t* mv_joint_cost, const int32_t* mv_comp_cost, const int32_t* mesh_patterns, const SvtHipIbcFullSearchJob* jobs, int njobs,
+                                 SvtHipIbcFullSearchResult* results) {
+    if (!ibcs::full_search_args_ok(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, mesh_patterns, jobs, njobs, results))
+        return SVT_HIP_ERR_BAD_ARG;
+    ibcs::full_search_host(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, mesh_patterns, jobs, njobs, results);
     return SVT_HIP_OK;
 }
 

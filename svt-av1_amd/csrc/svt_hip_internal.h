@@ -129,6 +129,10 @@ int svt_hip_launch_ibc_hash_table(hipStream_t st, int pix_bytes, const void* lum
 int svt_hip_launch_ibc_hash_search(hipStream_t st, int pix_bytes, int bd, const void* luma, int stride, int width, int height, const int32_t* bucket_start,
                                    const SvtHipIbcHashEntry* entries, const int32_t* joint_cost, const int32_t* comp_cost, const SvtHipIbcSearchJob* jobs, int njobs,
                                    SvtHipIbcSearchResult* results);
+/* ibc_search.hip; the arithmetic both sides share is ibc_search.h.  mesh_patterns is a host array */
+int svt_hip_launch_ibc_full_search(hipStream_t st, int pix_bytes, int bd, const void* luma, int stride, int width, int height, const int32_t* bucket_start,
+                                   const SvtHipIbcHashEntry* entries, const int32_t* joint_cost, const int32_t* comp_cost, const int32_t* mesh_patterns,
+                                   const SvtHipIbcFullSearchJob* jobs, int njobs, SvtHipIbcFullSearchResult* results, void* scratch);
 /* md_pre.hip */
 int svt_hip_launch_md_fullpel_sad(hipStream_t st, int pix_bytes, const void* src, int src_stride, int pic_w, int pic_h, int sb_cols, int n_sb, int n_pus, const SvtHipMdPu* pus,
                                   int n_refs, const SvtHipMdRefPlane* refs, const uint32_t* mv, uint32_t* sad);
