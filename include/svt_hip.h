@@ -776,6 +776,64 @@ typedef struct {
 size_t svt_hip_resize_scratch_bytes(int pix_bytes, const SvtHipResizePlane *planes, int n_planes);
 int svt_hip_resize_planes_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const SvtHipResizePlane *planes, int n_planes, void *d_scratch, size_t scratch_bytes);
 
+/* ------------------------------------------------------------------ inter prediction from a reference of another size ---- */
+/* Once a picture and one of its references differ in size (super-resolution, reference scaling) every inter block that predicts from that reference
+ * goes through svt_av1_convolve_2d_scale / svt_av1_highbd_convolve_2d_scale (Common/Codec/EbInterPrediction.c:471-550, :867-946, called by
+ * svt_inter_predictor / svt_highbd_inter_predictor, :1368-1500): the filter phase changes per output column and row, x_qn = subpel_x + x * xs in 1/1024
+ * sample.  Positions and phases come from the scaled branch of compute_subpel_params (Encoder/Codec/EbEncInterPrediction.c:3591-3661), the scale factors
+ * from svt_av1_setup_scale_factors_for_frame (EbInterPrediction.c:178-241).  The arithmetic is csrc/scaled_pred.h, the kernels csrc/scaled_pred.hip
+ * (docs/kernels/scaled_pred.md). */
+typedef struct {
+    int32_t x_scale_fp, y_scale_fp; /* reference size / picture size in 1/16384; -1, -1 = not a valid pair (REF_INVALID_SCALE) */
+    int32_t x_step_q4, y_step_q4;   /* the same in 1/1024: 64 .. 2048, 1024 = not scaled */
+} SvtHipScaleFactors;
+/* Host only.  other_* = the reference's size, this_* = the picture's.  Returns SVT_HIP_OK, or SVT_HIP_ERR_BAD_ARG with out->x_scale_fp = y_scale_fp = -1
+ * (steps 0) for a pair valid_ref_frame_size refuses: 2 * this >= other and this <= 16 * other per axis (and every size 1 .. 65535). */
+int svt_hip_scale_factors(int other_w, int other_h, int this_w, int this_h, SvtHipScaleFactors *out);
+/* Host only: the scaled branch of compute_subpel_params for one plane of one block.  pre_x / pre_y = the block's position in that plane, mv_row / mv_col
+ * in 1/8 luma sample, ss_x / ss_y the plane's sub-sampling, frame_w / frame_h the luma size the reference is clamped against.  Out: the integer position
+ * in the reference plane (may be negative: the border), the phases 0 .. 1023 and the steps.  The branch is applied whatever the factors are; with both
+ * 16384 it gives the position and the filter index of the unscaled branch for a vector clamp_mv_to_umv_border_sb leaves alone (phase = 64 * q4 + 32). */
+void svt_hip_scaled_block_params(const SvtHipScaleFactors *sf, int pre_x, int pre_y, int mv_row, int mv_col, int ss_x, int ss_y, int frame_w, int frame_h,
+                                 int32_t *pos_x, int32_t *pos_y, int32_t *subpel_x, int32_t *subpel_y, int32_t *xs, int32_t *ys);
+/* One job of svt_hip_scaled_predict_batch_dev: position, phase and step per reference, raw.  compound 0 = one reference (reference 0; the *1 members are
+ * not read), pixels as convolve_2d_scale writes them with is_compound = 0; 1 = the two references averaged (do_average, round_1 =
+ * COMPOUND_ROUND1_BITS); 2 = distance-weighted ((d0 * fwd_offset + d1 * bck_offset) >> DIST_PRECISION_BITS, offsets of quant_dist_lookup_table).  The two
+ * references of a pair may have different sizes, so each has its own steps; a reference with both steps 1024 is legal and gives what the reference's
+ * unscaled dispatch (jnt_convolve_{2d,x,y,2d_copy}) gives at phase subpel >> 6.  Kernel banks as in SvtHipConvBlk.  A job with a step outside 1 .. 2048,
+ * a phase above 1023 or a size outside 1 .. 128 writes nothing. */
+typedef struct {
+    int32_t pos0_x, pos0_y, pos1_x, pos1_y;                 /* integer position of the block's top-left sample in reference plane 0 / 1 */
+    int32_t dst_x, dst_y;
+    uint16_t subpel0_x, subpel0_y, subpel1_x, subpel1_y;    /* 0 .. 1023 */
+    uint16_t xs0, ys0, xs1, ys1;                            /* 1/1024 sample per output sample */
+    uint8_t w, h;                                           /* 4 .. 128 */
+    uint8_t bank_x, bank_y;
+    uint8_t compound, fwd_offset, bck_offset, reserved;
+} SvtHipScaledBlk;
+/* One block as the encoder holds it, for svt_hip_scaled_jobs_dev: everything of SvtHipScaledBlk that does not depend on the scale factors, and the
+ * vectors (1/8 luma sample; mv1_* read when compound != 0). */
+typedef struct {
+    int32_t pre_x, pre_y; /* the block's position in the plane being predicted */
+    int32_t dst_x, dst_y;
+    int16_t mv0_row, mv0_col, mv1_row, mv1_col;
+    uint8_t ss_x, ss_y;   /* the plane's sub-sampling, 0 / 1 */
+    uint8_t w, h;
+    uint8_t bank_x, bank_y;
+    uint8_t compound, fwd_offset, bck_offset, reserved[3];
+} SvtHipScaledRec;
+/* d_jobs[i] = d_recs[i] through svt_hip_scaled_block_params, on the device: vectors that live there never visit the host.  sf0 / sf1 (host pointers) and
+ * frame_w / frame_h [2] belong to reference 0 / 1; sf1 == NULL: reference 1 is reference 0's twin (same factors, same size).  Both must be valid. */
+int svt_hip_scaled_jobs_dev(SvtHipCtx *ctx, const SvtHipScaleFactors *sf0, const SvtHipScaleFactors *sf1, const int frame_w[2], const int frame_h[2],
+                            const SvtHipScaledRec *d_recs, SvtHipScaledBlk *d_jobs, int n);
+/* The prediction of n jobs in one launch; (pix_bytes, bd) = (1, 8), (2, 8), (2, 10) or (2, 12).  d_ref1 may be NULL when no job is compound: the jobs are
+ * device memory the host cannot see, so a compound job with d_ref1 == NULL is the caller's error and is not caught.  What the caller owes, for every job
+ * and each reference it uses: the plane is readable from pos_x - 3 to pos_x + (((w - 1) * xs + subpel_x) >> 10) + 4 in x, and from pos_y - 3 to
+ * pos_y + (((h - 1) * ys + subpel_y) >> 10) + 4 in y (the reference's 288-sample border guarantees it after the clamp of svt_hip_scaled_block_params), and
+ * the destinations of a launch are disjoint.  Nothing outside a job's w x h destination is written.  strides in samples. */
+int svt_hip_scaled_predict_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_ref0, int ref0_stride, const void *d_ref1, int ref1_stride,
+                                     void *d_dst, int dst_stride, const SvtHipScaledBlk *d_jobs, int n);
+
 /* ------------------------------------------------------------------ per-call forms ------------- */
 /* Operations that the frame entry points above run fused inside larger kernels, exposed on their own for a list of units, so that every
  * pointer of the reference's dispatch table on this path has a device form (include/svt_hip_rtcd.h launches these with a list of one).

@@ -458,6 +458,28 @@ class ResizePlane(C.Structure):
                 ("out_w", C.c_int32), ("out_h", C.c_int32)]
 
 
+class ScaleFactors(C.Structure):
+    """SvtHipScaleFactors (include/svt_hip.h)."""
+    _fields_ = [("x_scale_fp", C.c_int32), ("y_scale_fp", C.c_int32), ("x_step_q4", C.c_int32), ("y_step_q4", C.c_int32)]
+
+
+class ScaledBlk(C.Structure):
+    """SvtHipScaledBlk (include/svt_hip.h)."""
+    _fields_ = [("pos0_x", C.c_int32), ("pos0_y", C.c_int32), ("pos1_x", C.c_int32), ("pos1_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
+                ("subpel0_x", C.c_uint16), ("subpel0_y", C.c_uint16), ("subpel1_x", C.c_uint16), ("subpel1_y", C.c_uint16),
+                ("xs0", C.c_uint16), ("ys0", C.c_uint16), ("xs1", C.c_uint16), ("ys1", C.c_uint16), ("w", C.c_uint8), ("h", C.c_uint8),
+                ("bank_x", C.c_uint8), ("bank_y", C.c_uint8), ("compound", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class ScaledRec(C.Structure):
+    """SvtHipScaledRec (include/svt_hip.h)."""
+    _fields_ = [("pre_x", C.c_int32), ("pre_y", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("mv0_row", C.c_int16), ("mv0_col", C.c_int16),
+                ("mv1_row", C.c_int16), ("mv1_col", C.c_int16), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("w", C.c_uint8), ("h", C.c_uint8),
+                ("bank_x", C.c_uint8), ("bank_y", C.c_uint8), ("compound", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
 GM_MAX_REFS = 8    # SVT_HIP_GM_MAX_REFS
 GM_FIT_MAX_JOBS = 64   # SVT_HIP_GM_FIT_MAX_JOBS
 GM_MAX_CORNERS = 4096   # SVT_HIP_GM_MAX_CORNERS
@@ -654,6 +676,11 @@ PROTOTYPES = {
     "svt_hip_superres_upscale_planes_dev": (i32, [vp, i32, i32, P(UpscalePlane), i32]),
     "svt_hip_resize_scratch_bytes": (sz, [i32, P(ResizePlane), i32]),
     "svt_hip_resize_planes_dev": (i32, [vp, i32, i32, P(ResizePlane), i32, vp, sz]),
+    # ---- inter prediction from a reference of another size
+    "svt_hip_scale_factors": (i32, [i32, i32, i32, i32, P(ScaleFactors)]),
+    "svt_hip_scaled_block_params": (None, [P(ScaleFactors), i32, i32, i32, i32, i32, i32, i32, i32] + [P(C.c_int32)] * 6),
+    "svt_hip_scaled_jobs_dev": (i32, [vp, P(ScaleFactors), P(ScaleFactors), P(i32), P(i32), vp, vp, i32]),
+    "svt_hip_scaled_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32]),
     # ---- per-call forms
     "svt_hip_quantize_batch_dev": (i32, [vp, vp, i32, i32, P(QuantParams), vp, vp, vp, vp]),
     "svt_hip_residual_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]),
@@ -1202,6 +1229,28 @@ class Context:
             if scratch is not None:
                 scratch[...] = s.download(d_x, scratch.shape, np.uint8)
             return [s.plane_back(b) for _, b in recs]
+
+    def scaled_jobs(self, sf0, sf1, frame_sizes, recs, fill=0xC3):
+        """svt_hip_scaled_jobs_dev: `sf0` / `sf1` ScaleFactors of reference 0 / 1 (sf1 None: reference 1 is reference 0's twin), `frame_sizes` ((w0, h0), (w1, h1)),
+        `recs` a ctypes array of ScaledRec.  -> ScaledBlk * n as the device left them (started as the byte `fill`)."""
+        (w0, h0), (w1, h1) = frame_sizes
+        with self.scope() as s:
+            d_r, d_j = s.structs(recs), s.filled(len(recs) * C.sizeof(ScaledBlk), fill, np.uint8)
+            self.call("scaled_jobs_dev", sf0, sf1, (i32 * 2)(w0, w1), (i32 * 2)(h0, h1), d_r, d_j, len(recs))
+            self.sync()
+            return s.structs_back(d_j, ScaledBlk * len(recs))
+
+    def scaled_predict(self, ref0, ref1, dst, jobs, bd=None):
+        """svt_hip_scaled_predict_batch_dev: `ref0`, `ref1` (None when no job is compound) and `dst` 2-D planes, all uint8 (bd 8) or all uint16 (bd 10 unless
+        `bd` says otherwise); each may be an offset / strided view, and a job may read around its reference's view (a negative position) as far as the array
+        the view lies in reaches.  `jobs` a ctypes array of ScaledBlk.  -> `dst` after the launch: a view like the one given of a fresh copy of the whole array."""
+        pix_bytes = ref0.dtype.itemsize
+        assert dst.dtype == ref0.dtype and (ref1 is None or ref1.dtype == ref0.dtype)
+        with self.scope() as s:
+            a, b, d, d_j = s.plane(ref0), s.plane(ref1) if ref1 is not None else None, s.plane(dst), s.structs(jobs)
+            self.call("scaled_predict_batch_dev", pix_bytes, default_bd(pix_bytes, bd), a.ptr, a.stride, b and b.ptr, b.stride if b else 0, d.ptr, d.stride, d_j, len(jobs))
+            self.sync()
+            return s.plane_back(d)
 
     def gm_cross_correlation_batch(self, im1, im2, pairs):
         """svt_hip_gm_cross_correlation_batch_dev: `im1` / `im2` 2-D uint8 planes of one size, `pairs` [n][4] int32 x1, y1, x2, y2 -> float64 [n]."""

@@ -14,6 +14,7 @@
 #include "resize_plan.h"
 #include "ibc_hash.h"
 #include "ibc_search.h"
+#include "scaled_pred.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -262,7 +263,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(scaled_pred) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -1637,6 +1638,41 @@ int svt_hip_resize_planes_dev(SvtHipCtx* c, int pix_bytes, int bd, const SvtHipR
     const size_t need = svt_hip_resize_scratch_layout_bytes(pix_bytes, planes, n_planes);
     if (need && (!d_scratch || scratch_bytes < need)) return bad_arg(c, "svt_hip_resize_planes_dev: d_scratch holds less than svt_hip_resize_scratch_bytes");
     return launched(c, svt_hip_launch_resize_planes(c->stream, pix_bytes, bd, planes, n_planes, d_scratch), "resize launch");
+}
+
+
+/* ------------------------------------------------------------------ prediction from a reference of another size (scaled_pred.hip; the arithmetic is scaled_pred.h) */
+int svt_hip_scale_factors(int other_w, int other_h, int this_w, int this_h, SvtHipScaleFactors* out) {
+    if (!out) return SVT_HIP_ERR_BAD_ARG;
+    return sp_scale_factors(other_w, other_h, this_w, this_h, out) ? SVT_HIP_OK : SVT_HIP_ERR_BAD_ARG;
+}
+
+void svt_hip_scaled_block_params(const SvtHipScaleFactors* sf, int pre_x, int pre_y, int mv_row, int mv_col, int ss_x, int ss_y, int frame_w, int frame_h, int32_t* pos_x,
+                                 int32_t* pos_y, int32_t* subpel_x, int32_t* subpel_y, int32_t* xs, int32_t* ys) {
+    sp_block_params(*sf, pre_x, pre_y, mv_row, mv_col, ss_x & 1, ss_y & 1, frame_w, frame_h, pos_x, pos_y, subpel_x, subpel_y, xs, ys);
+}
+
+int svt_hip_scaled_jobs_dev(SvtHipCtx* c, const SvtHipScaleFactors* sf0, const SvtHipScaleFactors* sf1, const int frame_w[2], const int frame_h[2],
+                            const SvtHipScaledRec* d_recs, SvtHipScaledBlk* d_jobs, int n) {
+    SVT_HIP_ENTER(c);
+    if (!c || n < 0 || !sf0 || !frame_w || !frame_h || !sp_scale_factors_ok(*sf0) || (sf1 && !sp_scale_factors_ok(*sf1)) || frame_w[0] < 1 || frame_w[0] > 65535 ||
+        frame_h[0] < 1 || frame_h[0] > 65535 || (sf1 && (frame_w[1] < 1 || frame_w[1] > 65535 || frame_h[1] < 1 || frame_h[1] > 65535)))
+        return bad_arg(c, "svt_hip_scaled_jobs_dev: bad argument (n >= 0, valid scale factors, every frame size 1 .. 65535)");
+    if (n == 0) return SVT_HIP_OK;
+    if (!d_recs || !d_jobs) return bad_arg(c, "svt_hip_scaled_jobs_dev: d_recs or d_jobs is NULL");
+    const int fw[2] = {frame_w[0], sf1 ? frame_w[1] : frame_w[0]}, fh[2] = {frame_h[0], sf1 ? frame_h[1] : frame_h[0]};
+    return launched(c, svt_hip_launch_scaled_jobs(c->stream, sf0, sf1 ? sf1 : sf0, fw, fh, d_recs, d_jobs, n), "scaled jobs launch");
+}
+
+int svt_hip_scaled_predict_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_ref0, int ref0_stride, const void* d_ref1, int ref1_stride, void* d_dst,
+                                     int dst_stride, const SvtHipScaledBlk* d_jobs, int n) {
+    SVT_HIP_ENTER(c);
+    if (!c || n < 0 || !fmt12_ok(pix_bytes, bd))
+        return bad_arg(c, "svt_hip_scaled_predict_batch_dev: bad argument (n >= 0; samples (1, 8), (2, 8), (2, 10) or (2, 12))");
+    if (n == 0) return SVT_HIP_OK;
+    if (!d_ref0 || !d_dst || !d_jobs) return bad_arg(c, "svt_hip_scaled_predict_batch_dev: d_ref0, d_dst or d_jobs is NULL");   // d_ref1 may be: no job is compound
+    return launched(c, svt_hip_launch_scaled_predict(c->stream, pix_bytes, bd, d_ref0, ref0_stride, d_ref1, ref1_stride, d_dst, dst_stride, d_jobs, n),
+                    "scaled predict launch");
 }
 
 

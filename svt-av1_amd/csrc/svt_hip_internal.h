@@ -182,6 +182,11 @@ int svt_hip_launch_sad_loop(hipStream_t st, const uint8_t* src, int src_stride, 
 int svt_hip_launch_superres_upscale(hipStream_t st, int pix_bytes, int bd, const SvtHipUpscalePlane* planes, int n);
 size_t svt_hip_resize_scratch_layout_bytes(int pix_bytes, const SvtHipResizePlane* planes, int n);
 int svt_hip_launch_resize_planes(hipStream_t st, int pix_bytes, int bd, const SvtHipResizePlane* planes, int n, void* scratch);
+/* scaled_pred.hip; the arithmetic both sides share is scaled_pred.h.  sf0 / sf1 / frame_w / frame_h are host pointers */
+int svt_hip_launch_scaled_predict(hipStream_t st, int pix_bytes, int bd, const void* ref0, int ref0_stride, const void* ref1, int ref1_stride, void* dst, int dst_stride,
+                                  const SvtHipScaledBlk* jobs, int n);
+int svt_hip_launch_scaled_jobs(hipStream_t st, const SvtHipScaleFactors* sf0, const SvtHipScaleFactors* sf1, const int frame_w[2], const int frame_h[2],
+                               const SvtHipScaledRec* recs, SvtHipScaledBlk* jobs, int n);
 /* sgr.hip */
 int svt_hip_launch_sgr_proj_error(hipStream_t st, int pix_bytes, int bd, const void* dgd, int stride, const void* src, int src_stride, int pw, int ph,
                                   int unit_size, int units_x, int units_y, int ss_y, uint32_t ep_mask, int ncand, const int32_t* xqd, int64_t* err);
