@@ -720,6 +720,77 @@ typedef struct {
 int svt_hip_blend_a64_batch_dev(SvtHipCtx *ctx, int pix_bytes, const void *d_src0, int src0_stride, const void *d_src1, int src1_stride, void *d_dst,
                                 int dst_stride, const uint8_t *d_masks, const SvtHipBlendBlk *d_blks, int nblk);
 
+/* ------------------------------------------------------------------ masked compound and inter-intra: choosing the mask ---- */
+/* The wedge mask set of the AV1 specification (7.11.3.11 "Wedge mask process", Wedge_Codebook), generated by the library: what svt_av1_init_wedge_masks builds
+ * (Common/Codec/EbInterPrediction.c:1550-1615 the codebooks and wedge_params_lookup, :1672-1734 the primary masks, :1737-1767 the sign flips, :1770-1809 the
+ * contiguous copies) and av1_get_contiguous_soft_mask returns.  Nine block sizes have wedges (BlockSize 3 .. 9 = 8x8, 8x16, 16x8, 16x16, 16x32, 32x16, 32x32; 18 = 8x32;
+ * 19 = 32x8), 16 indices x 2 signs of bw * bh bytes (stride bw) each, 100 352 bytes in all: for each size in BlockSize order, for each index, sign 0 then sign 1.
+ *   svt_hip_wedge_mask_table_bytes : 100352
+ *   svt_hip_wedge_mask_offset      : byte offset of a mask in the table; -1 for a size without wedges, a sign outside 0 / 1, an index outside 0 .. 15
+ *   svt_hip_wedge_masks_host       : fills dst[100352]; no device
+ *   svt_hip_wedge_masks_dev        : the context's device copy, built and uploaded by the first call that needs it and kept until svt_hip_destroy.  The pointer is
+ *                                    valid as d_masks of svt_hip_compound_predict_batch_dev (type 3: mask_off = the offset, mask_stride = bw; that call only reads the
+ *                                    table for type 3, so its non-const parameter may be given this pointer) and of svt_hip_blend_a64_batch_dev. */
+size_t svt_hip_wedge_mask_table_bytes(void);
+int svt_hip_wedge_mask_offset(int bsize, int sign, int index);
+int svt_hip_wedge_masks_host(uint8_t *dst);
+int svt_hip_wedge_masks_dev(SvtHipCtx *ctx, const uint8_t **d_masks);
+/* The tables of model_rd_with_curvfit / av1_model_rd_curvfit (Encoder/Codec/EbEncInterPrediction.c:432-503): rate = interp_rgrid_curv[4][65], dist =
+ * interp_dgrid_curv[2][65], bsize_cat = bsize_curvfit_model_cat_lookup[22] (each 0 .. 3).  They are the caller's data: the library holds no copy of its own.  Copied
+ * to the context (host and device) before the call returns; may be set again.  A search call made before is refused. */
+int svt_hip_set_rd_curvfit_grids(SvtHipCtx *ctx, const double *rate, const double *dist, const int32_t *bsize_cat);
+/* The mask decisions of compound mode decision for a list of blocks, one launch: search_compound_diff_wedge -> pick_interinter_mask -> pick_wedge /
+ * pick_interinter_seg (Encoder/Codec/EbEncInterPrediction.c:562-631, :700-756, with the residual1 / diff10 set-up of calc_pred_masked_compound, :6120-6162) and the
+ * decision part of inter_intra_search (Encoder/Codec/EbModeDecision.c:387-475) with pick_interintra_wedge (:214-242) -> pick_wedge_fixed_sign
+ * (EbEncInterPrediction.c:635-675).  The leaves are the C forms: svt_av1_wedge_compute_delta_squares_c (:517-521, saturating to int16),
+ * svt_av1_wedge_sign_from_residuals_c (:554-560), svt_av1_wedge_sse_from_residuals_c (Common/Codec/EbInterPrediction.c:2141-2151, each term clamped to int16),
+ * aom_sum_squares_i16, svt_av1_build_compound_diffwtd_mask[_highbd] (:78-175), combine_interintra[_highbd] over build_smooth_interintra_mask (:1823-1875),
+ * svt_aom_[highbd_]sse, model_rd_for_sb_with_curvfit (EbEncInterPrediction.c:819-869, luma), model_rd_with_curvfit (:432-503) and RDCOST
+ * (Encoder/Codec/EbRateDistortionCost.h:106).  svt_log2f(0) (log2f_32, Common/Codec/EbUtility.c:251), undefined in the reference's C, is 0 as its C build gives it (csrc/comp_search.h).
+ *   kind 0  inter-inter wedge: p0 at pred0, p1 at pred1.  Decides wedge_index, wedge_sign, rd.  Candidates 0 .. 15 = the wedge indices.  The nine wedge sizes.
+ *   kind 1  inter-inter diff-weighted: decides mask_type (0 DIFFWTD_38, 1 DIFFWTD_38_INV), rd.  Candidates 0, 1.  Every size with min(bw, bh) >= 8.
+ *   kind 2  inter-intra: the intra predictions II_DC, II_V, II_H, II_SMOOTH back to back (bw * bh samples each) at pred0, the inter prediction at pred1.  Decides
+ *           interintra_mode with rd (RDCOST of rate + inter_intra_mode_fac_bits), then interintra_wedge_index with rd_wedge on the winner's intra prediction, sign
+ *           0, wedge_idx_fac_bits added to the rate.  Candidates 0 .. 3 = the modes, 4 .. 19 = the wedge indices.  The nine wedge sizes.
+ * A strict `<` from INT64_MAX keeps the first minimum.  Fields a kind does not decide are -1 (indices, sign, type, mode) and 0 (rd values, reserved).
+ *   d_src, src_stride, width, height : the source luma plane (pix_bytes 1 with bd 8; pix_bytes 2 with bd 8 or 10); every block lies inside it
+ *   d_pred, pred_samples : the predictor pool, blocks stored with stride bw as the reference's pred0 / pred1 / intrapred_buf; offsets are in samples
+ *   d_rates, nrates      : int32 rate tables; kind 2 reads 16 values at wedge_rate (wedge_idx_fac_bits[bsize]) and 4 at mode_rate
+ *                          (inter_intra_mode_fac_bits[size_group]); may be NULL when nrates is 0
+ *   jobs                 : HOST memory, checked before anything is launched and copied to the device by the call (stream-ordered)
+ *   d_results            : njobs results
+ *   d_cand               : NULL, or njobs * SVT_HIP_COMP_SEARCH_MAX_CANDS records, one per candidate evaluated; slots a kind does not use are {-1, 0, 0, 0, 0}
+ * Refused with SVT_HIP_ERR_BAD_ARG before anything touches the device: a NULL where a pointer is needed, njobs < 0 or above 2^24, a sample format other than the three,
+ * an unknown kind, a size the kind does not allow, a block outside the plane, a predictor or rate offset outside its array, quantizer outside 1 .. 32767, grids not
+ * set.  Stream-ordered and asynchronous apart from the job upload. */
+#define SVT_HIP_COMP_SEARCH_WEDGE 0
+#define SVT_HIP_COMP_SEARCH_DIFFWTD 1
+#define SVT_HIP_COMP_SEARCH_INTERINTRA 2
+#define SVT_HIP_COMP_SEARCH_MAX_CANDS 20
+typedef struct {
+    int32_t  kind, bsize;          /* bsize: the reference's BlockSize (0 = 4x4 .. 21 = 64x16) */
+    int32_t  x, y;                 /* the block's top-left sample in the source plane */
+    int32_t  pred0, pred1;         /* sample offsets into d_pred */
+    int32_t  quantizer;            /* y_dequant_q3[base_q_idx][1] of the depth in use */
+    uint32_t full_lambda;          /* full_lambda_md of the depth in use */
+    int32_t  wedge_rate, mode_rate; /* kind 2: offsets into d_rates */
+} SvtHipCompSearchJob;
+typedef struct {
+    int32_t wedge_index, wedge_sign, mask_type, interintra_mode, interintra_wedge_index, reserved;
+    int64_t rd, rd_wedge;
+} SvtHipCompSearchResult;
+typedef struct {
+    int32_t sign, rate;            /* rate: as it enters RDCOST, the caller's rate included */
+    int64_t sse, dist, rd;
+} SvtHipCompSearchCand;
+int svt_hip_compound_search_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_src, int src_stride, int width, int height, const void *d_pred,
+                                      int64_t pred_samples, const int32_t *d_rates, int nrates, const SvtHipCompSearchJob *jobs, int njobs,
+                                      SvtHipCompSearchResult *d_results, SvtHipCompSearchCand *d_cand);
+/* the same on host pointers, serially, from csrc/comp_search.h: no context, the three tables of svt_hip_set_rd_curvfit_grids first */
+int svt_hip_compound_search_host(const double *rate, const double *dist, const int32_t *bsize_cat, int pix_bytes, int bd, const void *src, int src_stride, int width,
+                                 int height, const void *pred, int64_t pred_samples, const int32_t *rates, int nrates, const SvtHipCompSearchJob *jobs, int njobs,
+                                 SvtHipCompSearchResult *results, SvtHipCompSearchCand *cand);
+
 /* ------------------------------------------------------------------ picture formats around the high-bit-depth path ---- */
 /* The reference keeps 10-bit pictures as an 8-bit plane + a 2-bit plane; these are its conversions to / from the 16-bit samples the
  * kernels above take (Common/C_DEFAULT/EbPackUnPack_C.c):

@@ -446,6 +446,61 @@ def ibc_full_search_host(plane, table, joint_cost, comp_cost, patterns, jobs, bd
     return res
 
 
+class CompSearchJob(C.Structure):
+    """SvtHipCompSearchJob (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_uint32 if n == "full_lambda" else C.c_int32) for n in ("kind", "bsize", "x", "y", "pred0", "pred1", "quantizer", "full_lambda", "wedge_rate",
+                                                                            "mode_rate")]
+
+
+class CompSearchResult(C.Structure):
+    """SvtHipCompSearchResult (include/svt_hip.h)."""
+    _fields_ = ([(n, C.c_int32) for n in ("wedge_index", "wedge_sign", "mask_type", "interintra_mode", "interintra_wedge_index", "reserved")] +
+                [("rd", C.c_int64), ("rd_wedge", C.c_int64)])
+
+
+class CompSearchCand(C.Structure):
+    """SvtHipCompSearchCand (include/svt_hip.h)."""
+    _fields_ = [("sign", C.c_int32), ("rate", C.c_int32), ("sse", C.c_int64), ("dist", C.c_int64), ("rd", C.c_int64)]
+
+
+COMP_SEARCH_MAX_CANDS = 20   # SVT_HIP_COMP_SEARCH_MAX_CANDS
+
+
+def wedge_masks_host():
+    """svt_hip_wedge_masks_host -> the contiguous wedge mask table, uint8[svt_hip_wedge_mask_table_bytes()]"""
+    L = lib()
+    out = np.zeros(L.svt_hip_wedge_mask_table_bytes(), np.uint8)
+    rc = L.svt_hip_wedge_masks_host(out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_wedge_masks_host failed: status {rc}")
+    return out
+
+
+def rd_curvfit_grids(grids):
+    """(rate[4][65], dist[2][65], bsize_cat[22]) -> the three arrays as svt_hip_set_rd_curvfit_grids and svt_hip_compound_search_host take them"""
+    rate, dist, cat = np.ascontiguousarray(grids[0], np.float64), np.ascontiguousarray(grids[1], np.float64), np.ascontiguousarray(grids[2], np.int32)
+    assert rate.shape == (4, 65) and dist.shape == (2, 65) and cat.shape == (22,)
+    return rate, dist, cat
+
+
+def compound_search_host(grids, plane, pool, rates, jobs, bd=None, cands=True):
+    """svt_hip_compound_search_host: `grids` (rate, dist, bsize_cat), `plane` the 2-D source luma plane (may be a strided view), `pool` the flat predictor pool of the
+    same dtype, `rates` int32, `jobs` a ctypes array of CompSearchJob.  -> (CompSearchResult * njobs, CompSearchCand * (20 njobs) or None)."""
+    pb, p, stride, w, h = _plane_args(plane)
+    rate, dist, cat = rd_curvfit_grids(grids)
+    pool, rates = np.ascontiguousarray(pool), np.ascontiguousarray(rates, np.int32)
+    assert pool.dtype == plane.dtype
+    n = len(jobs)
+    res = (CompSearchResult * max(n, 1))()
+    cand = (CompSearchCand * (COMP_SEARCH_MAX_CANDS * max(n, 1)))() if cands else None
+    rc = lib().svt_hip_compound_search_host(rate.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), cat.ctypes.data_as(C.c_void_p), pb, default_bd(pb, bd), p, stride,
+                                            w, h, pool.ctypes.data_as(C.c_void_p), pool.size, rates.ctypes.data_as(C.c_void_p) if rates.size else None, rates.size,
+                                            C.cast(jobs, C.c_void_p), n, C.cast(res, C.c_void_p), C.cast(cand, C.c_void_p) if cands else None)
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_compound_search_host refused its arguments: status {rc}")
+    return res, cand
+
+
 class UpscalePlane(C.Structure):
     """SvtHipUpscalePlane (include/svt_hip.h)."""
     _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32), ("out_w", C.c_int32),
@@ -734,6 +789,13 @@ PROTOTYPES = {
     "svt_hip_ibc_hash_table_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, C.c_int64, vp, vp, sz]),
     "svt_hip_ibc_hash_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
     # ---- intra block copy: diamond, mesh and the final choice
+    "svt_hip_wedge_mask_table_bytes": (sz, []),
+    "svt_hip_wedge_mask_offset": (i32, [i32, i32, i32]),
+    "svt_hip_wedge_masks_host": (i32, [vp]),
+    "svt_hip_wedge_masks_dev": (i32, [vp, vp]),
+    "svt_hip_set_rd_curvfit_grids": (i32, [vp, vp, vp, vp]),
+    "svt_hip_compound_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, i32, vp, vp]),
+    "svt_hip_compound_search_host": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, i32, vp, vp]),
     "svt_hip_ibc_full_search_scratch_bytes": (sz, [i32]),
     "svt_hip_ibc_full_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, sz]),
     "svt_hip_ibc_full_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
@@ -1059,6 +1121,36 @@ class Context:
             r, sc = s.download(d_r, (nb_r + 2 * guard,), np.uint8), s.download(d_s, (max(nb_s, 256) + 2 * guard,), np.uint8)
             res = kind.from_buffer_copy(r[guard:guard + nb_r].tobytes())
             return res, (r[:guard], r[guard + nb_r:], sc[:guard], sc[guard + nb_s:])
+
+    # ---- masked compound and inter-intra: choosing the mask
+    def wedge_masks(self):
+        """svt_hip_wedge_masks_dev -> the device pointer of the context's wedge mask table (owned by the context: not to be freed)"""
+        p = C.c_void_p()
+        self.call("wedge_masks_dev", C.byref(p))
+        return p
+
+    def set_rd_curvfit_grids(self, grids):
+        """svt_hip_set_rd_curvfit_grids: `grids` (rate[4][65], dist[2][65], bsize_cat[22])"""
+        rate, dist, cat = rd_curvfit_grids(grids)
+        self.call("set_rd_curvfit_grids", rate.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), cat.ctypes.data_as(C.c_void_p))
+
+    def compound_search_batch(self, plane, pool, rates, jobs, bd=None, cands=True, fill=0xC3):
+        """svt_hip_compound_search_batch_dev on the grids set before: `plane` the 2-D source luma plane (may be a strided view), `pool` the flat predictor pool of the
+        same dtype, `rates` int32, `jobs` a ctypes array of CompSearchJob.  Results and candidate records start as the byte `fill`.
+        -> (CompSearchResult * njobs, CompSearchCand * (20 njobs) or None)."""
+        h, w = plane.shape
+        pool, rates = np.ascontiguousarray(pool), np.ascontiguousarray(rates, np.int32)
+        assert pool.dtype == plane.dtype
+        n = len(jobs)
+        rk, ck = CompSearchResult * max(n, 1), CompSearchCand * (COMP_SEARCH_MAX_CANDS * max(n, 1))
+        with self.scope() as s:
+            p, d_pool, d_rates = s.plane(plane), s.upload(pool), s.upload(rates)
+            d_r = s.filled(C.sizeof(rk), fill, np.uint8)
+            d_c = s.filled(C.sizeof(ck), fill, np.uint8) if cands else None
+            self.call("compound_search_batch_dev", plane.itemsize, default_bd(plane.itemsize, bd), p.ptr, p.stride, w, h, d_pool, pool.size, d_rates if rates.size else None,
+                      rates.size, C.cast(jobs, C.c_void_p), n, d_r, d_c)
+            self.sync()
+            return s.structs_back(d_r, rk), (s.structs_back(d_c, ck) if cands else None)
 
     def filter_intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D

@@ -15,6 +15,7 @@
 #include "ibc_hash.h"
 #include "ibc_search.h"
 #include "scaled_pred.h"
+#include "comp_search.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -34,6 +35,11 @@ struct SvtHipCtx {
     void*       me_buf = nullptr;         // device staging of svt_hip_me_fullpel_frame (host-pointer form), grown on demand
     size_t      me_buf_bytes = 0;
     uint16_t*   gm_lut = nullptr;         // device copy of the global-motion error table, made by the first global-motion call
+    uint8_t*    wedge_masks = nullptr;    // device copy of the wedge mask table (comp_search.h), made by the first call that needs it
+    void*       rd_grids = nullptr;       // device copy of the tables of svt_hip_set_rd_curvfit_grids: rate[4][65], dist[2][65] as double, then cat[22] as int32
+    bool        rd_grids_set = false;
+    void*       comp_jobs = nullptr;      // device staging of svt_hip_compound_search_batch_dev's job list, grown on demand
+    size_t      comp_jobs_bytes = 0;
     std::string err;
 };
 
@@ -130,6 +136,9 @@ void svt_hip_destroy(SvtHipCtx* c) {
     if (c->host_scratch) (void)hipHostFree(c->host_scratch);
     if (c->me_buf) (void)hipFree(c->me_buf);
     if (c->gm_lut) (void)hipFree(c->gm_lut);
+    if (c->wedge_masks) (void)hipFree(c->wedge_masks);
+    if (c->rd_grids) (void)hipFree(c->rd_grids);
+    if (c->comp_jobs) (void)hipFree(c->comp_jobs);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -263,7 +272,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(scaled_pred) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(comp_search) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(palette) X(percall) X(pyramid) X(resize) X(scaled_pred) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -404,6 +413,71 @@ int svt_hip_ibc_full_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const
     return launched(c, svt_hip_launch_ibc_full_search(c->stream, pix_bytes, bd, d_luma, stride, width, height, d_bucket_start, d_entries, d_mv_joint_cost, d_mv_comp_cost,
                                                       mesh_patterns, d_jobs, njobs, d_results, d_scratch),
                     "intra-block-copy full search launch");
+}
+
+/* ---------------------------------------------------------------------------------- masked compound and inter-intra: choosing the mask (comp_search.hip) */
+size_t svt_hip_wedge_mask_table_bytes(void) { return cs::WEDGE_TABLE_BYTES; }
+int    svt_hip_wedge_mask_offset(int bsize, int sign, int index) { return cs::wedge_offset(bsize, sign, index); }
+
+static int wedge_masks(SvtHipCtx* c) {
+    if (c->wedge_masks) return SVT_HIP_OK;
+    std::vector<uint8_t> table(cs::WEDGE_TABLE_BYTES);
+    cs::wedge_table_build(table.data());
+    HIPCHK(c, hipMalloc((void**)&c->wedge_masks, table.size()));
+    hipError_t e = hipMemcpy(c->wedge_masks, table.data(), table.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(c->wedge_masks); c->wedge_masks = nullptr; return fail(c, e, "wedge mask table upload"); }
+    return SVT_HIP_OK;
+}
+
+int svt_hip_wedge_masks_dev(SvtHipCtx* c, const uint8_t** d_masks) {
+    SVT_HIP_ENTER(c);
+    if (!c || !d_masks) return bad_arg(c, "svt_hip_wedge_masks_dev: bad argument");
+    if (int rc = wedge_masks(c)) return rc;
+    *d_masks = c->wedge_masks;
+    return SVT_HIP_OK;
+}
+
+namespace {
+constexpr size_t kRdGridDoubles = (size_t)(cs::RATE_CATS + cs::DIST_CATS) * cs::GRID_COLS, kRdGridBytes = kRdGridDoubles * sizeof(double) + cs::BLOCK_SIZES * sizeof(int32_t);
+}
+int svt_hip_set_rd_curvfit_grids(SvtHipCtx* c, const double* rate, const double* dist, const int32_t* bsize_cat) {
+    SVT_HIP_ENTER(c);
+    if (!c || !cs::rd_tables_ok(rate, dist, bsize_cat)) return bad_arg(c, "svt_hip_set_rd_curvfit_grids: bad argument (three tables, every category 0 .. 3)");
+    uint8_t host[kRdGridBytes];
+    memcpy(host, rate, (size_t)cs::RATE_CATS * cs::GRID_COLS * sizeof(double));
+    memcpy(host + (size_t)cs::RATE_CATS * cs::GRID_COLS * sizeof(double), dist, (size_t)cs::DIST_CATS * cs::GRID_COLS * sizeof(double));
+    memcpy(host + kRdGridDoubles * sizeof(double), bsize_cat, cs::BLOCK_SIZES * sizeof(int32_t));
+    if (!c->rd_grids) HIPCHK(c, hipMalloc(&c->rd_grids, kRdGridBytes));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // a search still in flight reads the tables it was launched with
+    HIPCHK(c, hipMemcpy(c->rd_grids, host, kRdGridBytes, hipMemcpyHostToDevice));
+    c->rd_grids_set = true;
+    return SVT_HIP_OK;
+}
+
+int svt_hip_compound_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_src, int src_stride, int width, int height, const void* d_pred,
+                                      int64_t pred_samples, const int32_t* d_rates, int nrates, const SvtHipCompSearchJob* jobs, int njobs,
+                                      SvtHipCompSearchResult* d_results, SvtHipCompSearchCand* d_cand) {
+    SVT_HIP_ENTER(c);
+    if (!c || !cs::search_args_ok(pix_bytes, bd, d_src, src_stride, width, height, d_pred, pred_samples, d_rates, nrates, jobs, njobs, d_results))
+        return bad_arg(c, "svt_hip_compound_search_batch_dev: bad argument");
+    if (!c->rd_grids_set) return bad_arg(c, "svt_hip_compound_search_batch_dev: bad argument (svt_hip_set_rd_curvfit_grids has not been called on this context)");
+    if (!njobs) return SVT_HIP_OK;
+    if (int rc = wedge_masks(c)) return rc;
+    const size_t bytes = (size_t)njobs * sizeof(SvtHipCompSearchJob);
+    if (bytes > c->comp_jobs_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier search may still read the old list
+        if (c->comp_jobs) (void)hipFree(c->comp_jobs);
+        c->comp_jobs = nullptr;
+        c->comp_jobs_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->comp_jobs, bytes));
+        c->comp_jobs_bytes = bytes;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->comp_jobs, jobs, bytes, hipMemcpyHostToDevice, c->stream));
+    const double* grids = (const double*)c->rd_grids;
+    return launched(c, svt_hip_launch_compound_search(c->stream, pix_bytes, bd, d_src, src_stride, d_pred, d_rates, c->wedge_masks, grids,
+                                                      grids + (size_t)cs::RATE_CATS * cs::GRID_COLS, (const int32_t*)(grids + kRdGridDoubles),
+                                                      (const SvtHipCompSearchJob*)c->comp_jobs, njobs, d_results, d_cand),
+                    "compound search launch");
 }
 
 /* ---------------------------------------------------------------------------------- TPL dispenser */

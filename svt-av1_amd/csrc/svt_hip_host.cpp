@@ -10,6 +10,8 @@
 #include "palette.h"
 #include "ibc_hash.h"
 #include "ibc_search.h"
+#include "comp_search.h"
+#include <vector>
 
 extern "C" {
 
@@ -333,6 +335,26 @@ int svt_hip_ibc_full_search_host(int pix_bytes, int bd, const void* luma, int st
     if (!ibcs::full_search_args_ok(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, mesh_patterns, jobs, njobs, results))
         return SVT_HIP_ERR_BAD_ARG;
     ibcs::full_search_host(pix_bytes, bd, luma, stride, width, height, bucket_start, entries, mv_joint_cost, mv_comp_cost, mesh_patterns, jobs, njobs, results);
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- masked compound and inter-intra: choosing the mask */
+int svt_hip_wedge_masks_host(uint8_t* dst) {
+    if (!dst) return SVT_HIP_ERR_BAD_ARG;
+    cs::wedge_table_build(dst);
+    return SVT_HIP_OK;
+}
+
+/* the contract of svt_hip_compound_search_batch_dev on host pointers: comp_search.h run serially */
+int svt_hip_compound_search_host(const double* rate, const double* dist, const int32_t* bsize_cat, int pix_bytes, int bd, const void* src, int src_stride, int width,
+                                 int height, const void* pred, int64_t pred_samples, const int32_t* rates, int nrates, const SvtHipCompSearchJob* jobs, int njobs,
+                                 SvtHipCompSearchResult* results, SvtHipCompSearchCand* cand) {
+    if (!cs::rd_tables_ok(rate, dist, bsize_cat) || !cs::search_args_ok(pix_bytes, bd, src, src_stride, width, height, pred, pred_samples, rates, nrates, jobs, njobs, results))
+        return SVT_HIP_ERR_BAD_ARG;
+    if (!njobs) return SVT_HIP_OK;
+    std::vector<uint8_t> masks(cs::WEDGE_TABLE_BYTES);
+    cs::wedge_table_build(masks.data());
+    cs::search_host(pix_bytes, bd, src, src_stride, pred, rates, masks.data(), cs::RdTables{rate, dist, bsize_cat}, jobs, njobs, results, cand);
     return SVT_HIP_OK;
 }
 

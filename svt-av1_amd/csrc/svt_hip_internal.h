@@ -61,6 +61,10 @@ int svt_hip_launch_compound_predict(hipStream_t st, int pix_bytes, int bd, const
 int svt_hip_launch_obmc_cost(hipStream_t st, const uint8_t* pre, int pre_stride, const int32_t* wsrc, const int32_t* mask, const SvtHipObmcBlk* blks, int n, uint32_t* out);
 int svt_hip_launch_blend_a64(hipStream_t st, int pix_bytes, const void* src0, int src0_stride, const void* src1, int src1_stride, void* dst, int dst_stride,
                              const uint8_t* masks, const SvtHipBlendBlk* blks, int n);
+/* comp_search.hip; the arithmetic both sides share is comp_search.h.  Every pointer is device memory; the jobs have passed cs::job_ok */
+int svt_hip_launch_compound_search(hipStream_t st, int pix_bytes, int bd, const void* src, int stride, const void* pred, const int32_t* rates, const uint8_t* masks,
+                                   const double* rate_grid, const double* dist_grid, const int32_t* bsize_cat, const SvtHipCompSearchJob* jobs, int njobs,
+                                   SvtHipCompSearchResult* results, SvtHipCompSearchCand* cands);
 /* conv.hip */
 int svt_hip_launch_subpel_jobs_from_me(hipStream_t st, const uint32_t* mv, int sb_cols, int w, int h, const uint8_t* frac, SvtHipConvBlk* out);
 int svt_hip_launch_subpel_predict(hipStream_t st, int pix_bytes, int bd, const void* ref, int ref_stride, void* dst, int dst_stride,
