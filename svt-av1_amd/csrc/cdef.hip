@@ -16,6 +16,7 @@
 // (FP64, sqrt, floor — Encoder/Codec/EbEncCdef.c:100-104) is evaluated per (block, strength) in the
 // reference's operation order with contraction off.  On 8-bit planes the secondary sums and the chroma primary sums read constrain() from tables the
 // workgroup builds in LDS for the launch's damping ("table form" below); the luma primary sums and 16-bit planes use the packed arithmetic.
+// The luma search finds the directions of a wave's sixteen blocks in one pass before its block loop, as seven i8 MFMAs (find_dir_batch16).
 // The staging tile marks everything outside the picture CDEF_VERY_LARGE exactly like the
 // reference's inbuf (EbCdefProcess.c:210-226).
 #include <hip/hip_runtime.h>
@@ -65,7 +66,7 @@ __device__ __forceinline__ void stage_tile(uint16_t* tile, int tstride, const PI
 // lane (d & 3, bin) sums the <= 8 pixels of its line (pixel lists precomputed below), squares and weights it
 // (div_table), and a 16-lane DPP row reduction yields the cost of direction d; two passes cover d = 0..3, 4..7.
 // xs: per-wave LDS scratch of 64 ints.  Returns dir, writes var (both wave-uniform).
-__device__ __constant__ uint8_t kDirBinPix[8][16][8] = {
+__device__ __constant__ constexpr uint8_t kDirBinPix[8][16][8] = {
     {{0,255,255,255,255,255,255,255},{1,8,255,255,255,255,255,255},{2,9,16,255,255,255,255,255},{3,10,17,24,255,255,255,255},{4,11,18,25,32,255,255,255},{5,12,19,26,33,40,255,255},{6,13,20,27,34,41,48,255},{7,14,21,28,35,42,49,56},{15,22,29,36,43,50,57,255},{23,30,37,44,51,58,255,255},{31,38,45,52,59,255,255,255},{39,46,53,60,255,255,255,255},{47,54,61,255,255,255,255,255},{55,62,255,255,255,255,255,255},{63,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
     {{0,1,255,255,255,255,255,255},{2,3,8,9,255,255,255,255},{4,5,10,11,16,17,255,255},{6,7,12,13,18,19,24,25},{14,15,20,21,26,27,32,33},{22,23,28,29,34,35,40,41},{30,31,36,37,42,43,48,49},{38,39,44,45,50,51,56,57},{46,47,52,53,58,59,255,255},{54,55,60,61,255,255,255,255},{62,63,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
     {{0,1,2,3,4,5,6,7},{8,9,10,11,12,13,14,15},{16,17,18,19,20,21,22,23},{24,25,26,27,28,29,30,31},{32,33,34,35,36,37,38,39},{40,41,42,43,44,45,46,47},{48,49,50,51,52,53,54,55},{56,57,58,59,60,61,62,63},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
@@ -74,7 +75,7 @@ __device__ __constant__ uint8_t kDirBinPix[8][16][8] = {
     {{48,56,255,255,255,255,255,255},{32,40,49,57,255,255,255,255},{16,24,33,41,50,58,255,255},{0,8,17,25,34,42,51,59},{1,9,18,26,35,43,52,60},{2,10,19,27,36,44,53,61},{3,11,20,28,37,45,54,62},{4,12,21,29,38,46,55,63},{5,13,22,30,39,47,255,255},{6,14,23,31,255,255,255,255},{7,15,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
     {{0,8,16,24,32,40,48,56},{1,9,17,25,33,41,49,57},{2,10,18,26,34,42,50,58},{3,11,19,27,35,43,51,59},{4,12,20,28,36,44,52,60},{5,13,21,29,37,45,53,61},{6,14,22,30,38,46,54,62},{7,15,23,31,39,47,55,63},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}},
     {{0,8,255,255,255,255,255,255},{1,9,16,24,255,255,255,255},{2,10,17,25,32,40,255,255},{3,11,18,26,33,41,48,56},{4,12,19,27,34,42,49,57},{5,13,20,28,35,43,50,58},{6,14,21,29,36,44,51,59},{7,15,22,30,37,45,52,60},{23,31,38,46,53,61,255,255},{39,47,54,62,255,255,255,255},{55,63,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255},{255,255,255,255,255,255,255,255}}};
-__device__ __constant__ int kDirBinWeight[8][16] = {{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0}};
+__device__ __constant__ constexpr int kDirBinWeight[8][16] = {{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{840,420,280,210,168,140,120,105,120,140,168,210,280,420,840,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0},{105,105,105,105,105,105,105,105,0,0,0,0,0,0,0,0},{420,210,140,105,105,105,105,105,140,210,420,0,0,0,0,0}};
 __device__ __forceinline__ int row_sum16(int v) {   // row16_sum in the builtin's other spelling: the header's gives the kernels that find a direction other code
     v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP1, 0xF, 0xF, false);
     v += __builtin_amdgcn_update_dpp(0, v, DPP_QUAD_SWAP2, 0xF, 0xF, false);
@@ -95,6 +96,18 @@ __device__ __forceinline__ DirBins load_dir_bins(int lane) {
     }
     return B;
 }
+// EbCdef.c:178-194: the first direction of the largest cost wins; var = (best - cost of the orthogonal direction) >> 10
+__device__ __forceinline__ int dir_of_costs(const int (&costs)[8], int& var_out) {
+    int best = 0, best_cost = 0;
+#pragma unroll
+    for (int d = 0; d < 8; d++)
+        if (costs[d] > best_cost) { best_cost = costs[d]; best = d; }
+    int orth = 0;
+#pragma unroll
+    for (int d = 0; d < 8; d++) if (d == ((best + 4) & 7)) orth = costs[d];
+    var_out = (best_cost - orth) >> 10;
+    return best;
+}
 __device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out, const DirBins& B) {
     xs[lane] = x_px - 128;
     __builtin_amdgcn_wave_barrier();
@@ -113,17 +126,75 @@ __device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& v
         for (int q = 0; q < 4; q++) costs[4 * pass + q] = __builtin_amdgcn_readlane(c, 16 * q);
     }
     __builtin_amdgcn_wave_barrier();
-    int best = 0, best_cost = 0;
-#pragma unroll
-    for (int d = 0; d < 8; d++)
-        if (costs[d] > best_cost) { best_cost = costs[d]; best = d; }
-    int orth = 0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) if (d == ((best + 4) & 7)) orth = costs[d];
-    var_out = (best_cost - orth) >> 10;
-    return best;
+    return dir_of_costs(costs, var_out);
 }
 __device__ __forceinline__ int find_dir_wave(int x_px, int lane, int* xs, int& var_out) { return find_dir_wave(x_px, lane, xs, var_out, load_dir_bins(lane)); }
+
+// ---- the same search for sixteen blocks at once, on the matrix cores (luma strength search) ----
+// The line sums of a block are a 0/1 matrix (90 lines x 64 samples) times its samples, and (px >> coeff_shift) - 128 is a signed byte at every bit depth, so
+// v_mfma_i32_16x16x64_i8 computes sixteen lines of sixteen blocks exactly: K = the 64 samples of a block, N = the blocks, M = the lines of one tile.  Seven tiles
+// hold the 90 lines: directions 0, 1, 3, 4, 5 and 7 one tile each (15 or 11 lines, the other rows zero), directions 2 and 6 (8 lines each) share the last.
+// Both operands put sample 16 * (lane >> 4) + e into byte e of the lane's four dwords (rows 2g and 2g + 1 of the block for lane group g = lane >> 4); A has its
+// line on lane & 15, B its block; lane (n, g) gets lines 4g .. 4g + 3 of block n in its four result registers.  kDirLines is built from kDirBinPix /
+// kDirBinWeight at compile time: .a[tile][lane] the lane's sixteen coefficient bytes, .w[tile][g] the weights of its four result rows.
+constexpr int kTileDir[6] = {0, 1, 3, 4, 5, 7};
+struct DirLineTables { uint32_t a[7][64][4]; int32_t w[7][4][4]; };
+constexpr DirLineTables make_dir_line_tables() {
+    DirLineTables t = {};
+    for (int tile = 0; tile < 7; tile++)
+        for (int row = 0; row < 16; row++) {
+            const int d = tile < 6 ? kTileDir[tile] : (row < 8 ? 2 : 6), line = tile < 6 ? row : (row & 7);
+            t.w[tile][row >> 2][row & 3] = kDirBinWeight[d][line];
+            for (int k = 0; k < 8; k++) {
+                const int idx = kDirBinPix[d][line][k];
+                if (idx < 64) t.a[tile][16 * (idx >> 4) + row][(idx & 15) >> 2] |= 1u << (8 * (idx & 3));
+            }
+        }
+    return t;
+}
+// every sample lies on exactly one line of a direction, and lines 8..15 of directions 2 and 6 are empty (what lets them share a tile)
+constexpr bool dir_line_tables_cover(const DirLineTables& t) {
+    for (int tile = 0; tile < 7; tile++)
+        for (int s = 0; s < 64; s++) {
+            int n = 0;
+            for (int row = 0; row < 16; row++) n += (t.a[tile][16 * (s >> 4) + row][(s & 15) >> 2] >> (8 * (s & 3))) & 0xFF;
+            if (n != (tile < 6 ? 1 : 2)) return false;
+        }
+    for (int line = 8; line < 16; line++)
+        if (kDirBinPix[2][line][0] != 255 || kDirBinPix[6][line][0] != 255 || kDirBinWeight[2][line] || kDirBinWeight[6][line]) return false;
+    return true;
+}
+static_assert(dir_line_tables_cover(make_dir_line_tables()), "kDirBinPix: a sample off its line, or directions 2 / 6 with more than 8 lines");
+__device__ __constant__ DirLineTables kDirLines = make_dir_line_tables();
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+// rows: the lane's first sample row (8 samples, 16-byte aligned) of block lane & 15, the second one tstride further.  A block that is not live feeds zeros.
+// Returns the direction and writes the variance of block lane & 15, in all four lanes that share it.
+__device__ __forceinline__ int find_dir_batch16(const uint16_t* rows, int tstride, bool live, int cs, int lane, int& var_out) {
+    const uint4 r0 = *(const uint4*)rows, r1 = *(const uint4*)(rows + tstride);
+    // two samples per dword, each below 256 << cs: after the shift their bytes are bytes 0 and 2; ^ 0x80 is - 128 on a byte
+    i32x4 b;
+    b.x = (int)(__builtin_amdgcn_perm(r0.y >> cs, r0.x >> cs, 0x06040200u) ^ 0x80808080u);
+    b.y = (int)(__builtin_amdgcn_perm(r0.w >> cs, r0.z >> cs, 0x06040200u) ^ 0x80808080u);
+    b.z = (int)(__builtin_amdgcn_perm(r1.y >> cs, r1.x >> cs, 0x06040200u) ^ 0x80808080u);
+    b.w = (int)(__builtin_amdgcn_perm(r1.w >> cs, r1.z >> cs, 0x06040200u) ^ 0x80808080u);
+    if (!live) b = (i32x4){0, 0, 0, 0};
+    const int g = lane >> 4;
+    int costs[8];
+#pragma unroll
+    for (int tile = 0; tile < 7; tile++) {
+        const i32x4 a = *(const i32x4*)kDirLines.a[tile][lane];
+        const i32x4 w = *(const i32x4*)kDirLines.w[tile][g];
+        const i32x4 s = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, (i32x4){0, 0, 0, 0}, 0, 0, 0);
+        // |s| <= 8 * 128 and s * s * w <= 2^20 * 105 (a line of one sample: 2^14 * 840): both products are exact in v_mul_i32_i24
+        int c = __mul24(__mul24(s.x, s.x), w.x) + __mul24(__mul24(s.y, s.y), w.y) + __mul24(__mul24(s.z, s.z), w.z) + __mul24(__mul24(s.w, s.w), w.w);
+        c += lane_xor(c, 16);                       // lines 0..7 in lane groups 0 and 1, lines 8..15 in 2 and 3
+        const int o = lane_xor(c, 32);
+        if (tile < 6) costs[kTileDir[tile]] = c + o;
+        else { costs[2] = g < 2 ? c : o; costs[6] = g < 2 ? o : c; }
+    }
+    return dir_of_costs(costs, var_out);
+}
 
 // ---- packed 16-bit search arithmetic ------------------------------------------------------------
 // Everything the 64 strength pairs need for one pixel: primary sums for pri = 1..15, secondary sums
@@ -507,10 +578,9 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
                         const uint8_t* __restrict__ skip8, int pri_damping, int cs, uint64_t* __restrict__ mse,
                         uint8_t* __restrict__ dir_out, int32_t* __restrict__ var_out) {
     constexpr int TS = 64 + 2 * kHB;  // tile stride (elements)
-    __shared__ uint16_t tile[(64 + 2 * kVB) * TS];
+    __shared__ __attribute__((aligned(16))) uint16_t tile[(64 + 2 * kVB) * TS];   // (a block's rows are 16-byte aligned: TS and kHB are multiples of 8 samples)
     __shared__ __attribute__((aligned(16))) PIX ytab[4][64][64 + 16 / sizeof(PIX)];  // [wave][strength][pixel] (+pad)
     __shared__ __attribute__((aligned(16))) PIX stab[4][64];
-    __shared__ int part[4][128];
     __shared__ unsigned long long accum[4][64];
     const int nhfb = (w + 63) >> 6, fb = svt_xcd_order(blockIdx.x, gridDim.x), fbr = fb / nhfb, fbc = fb - fbr * nhfb, c8 = w >> 3;
     const int nbx = min(8, c8 - 8 * fbc), nby = min(8, (h >> 3) - 8 * fbr);
@@ -531,17 +601,23 @@ cdef_search_luma_kernel(const PIX* __restrict__ rec, int rec_stride, const PIX* 
     __syncthreads();
     unsigned long long acc = 0;            // lane g: sum over this wave's blocks of dist(block, strength g)
     const int i = lane >> 3, j = lane & 7;
-    const DirBins bins = load_dir_bins(lane);
-    for (int b = wave; b < 64; b += 4) {
+    // The directions of the wave's sixteen blocks b = wave + 4n in one pass: lane (n, g) = (lane & 15, lane >> 4) brings rows 2g and 2g + 1 of block n and ends
+    // up with the block's direction and variance (0 / 0 for a block that is skipped or outside the picture, which is also what the two outputs report).
+    int dir16, var16;
+    unsigned long long live16;
+    {
+        const int b = wave + 4 * (lane & 15), by = b >> 3, bx = b & 7;
+        const bool live = by < nby && bx < nbx && !skip8[(8 * fbr + min(by, nby - 1)) * c8 + 8 * fbc + min(bx, nbx - 1)];
+        dir16 = find_dir_batch16(tile + (8 * by + 2 * (lane >> 4) + kVB) * TS + 8 * bx + kHB, TS, live, cs, lane, var16);
+        if (!live) dir16 = var16 = 0;
+        if (lane < 16 && dir_out) { dir_out[fb * 64 + b] = (uint8_t)dir16; var_out[fb * 64 + b] = var16; }
+        live16 = __ballot(live);
+    }
+    for (int b = wave, n = 0; b < 64; b += 4, n++) {
+        if (!((live16 >> n) & 1)) continue;
         const int by = b >> 3, bx = b & 7;
-        if (by >= nby || bx >= nbx || skip8[(8 * fbr + by) * c8 + 8 * fbc + bx]) {
-            if (lane == 0 && dir_out) { dir_out[fb * 64 + b] = 0; var_out[fb * 64 + b] = 0; }
-            continue;
-        }
         const uint16_t* px = tile + (8 * by + i + kVB) * TS + 8 * bx + j + kHB;
-        int var;
-        const int dir = find_dir_wave(((int)px[0] >> cs), lane, part[wave], var, bins);
-        if (lane == 0 && dir_out) { dir_out[fb * 64 + b] = (uint8_t)dir; var_out[fb * 64 + b] = var; }
+        const int dir = __builtin_amdgcn_readlane(dir16, n), var = __builtin_amdgcn_readlane(var16, n);
         int t_of[16];
 #pragma unroll
         for (int idx = 0; idx < 16; idx++) t_of[idx] = adjust_strength(idx << cs, var);
