@@ -37,9 +37,12 @@ constexpr int PW = TW + 2, PH1 = TH + 2;   // A/B positions incl. the 1-px borde
 constexpr int PH2 = TH / 2 + 1;            // r = 2: rows -1, 1, ..., TH - 1
 
 // eb_sgr_params {r0, r1, s0, s1} (EbRestoration.c:136-153)
-__device__ __constant__ int kSgr[16][4] = {{2, 1, 140, 3236}, {2, 1, 112, 2158}, {2, 1, 93, 1618}, {2, 1, 80, 1438}, {2, 1, 70, 1295}, {2, 1, 58, 1177},
-                                           {2, 1, 47, 1079},  {2, 1, 37, 996},   {2, 1, 30, 925},  {2, 1, 25, 863},  {0, 1, -1, 2589}, {0, 1, -1, 1618},
-                                           {0, 1, -1, 1177},  {0, 1, -1, 925},   {2, 0, 56, -1},   {2, 0, 22, -1}};
+#define SGR_PARAMS_ {{2, 1, 140, 3236}, {2, 1, 112, 2158}, {2, 1, 93, 1618}, {2, 1, 80, 1438}, {2, 1, 70, 1295}, {2, 1, 58, 1177}, \
+                     {2, 1, 47, 1079},  {2, 1, 37, 996},   {2, 1, 30, 925},  {2, 1, 25, 863},  {0, 1, -1, 2589}, {0, 1, -1, 1618}, \
+                     {0, 1, -1, 1177},  {0, 1, -1, 925},   {2, 0, 56, -1},   {2, 0, 22, -1}}
+__device__ __constant__ int kSgr[16][4] = SGR_PARAMS_;
+constexpr int kSgrHost[16][4] = SGR_PARAMS_;   // the same table for constant expressions (the bounds next to sgr8_fill_table)
+#undef SGR_PARAMS_
 
 struct TileLds {
     uint16_t in[IH * IW];
@@ -175,12 +178,14 @@ sgr_filter_kernel(const PIX* __restrict__ plane, int stride, int pw, int ph, int
 //  * everything that does not depend on the parameter set is hoisted out of the 16-set loop and kept
 //    in REGISTERS: p = max(n*sumsq - sum^2, 0) and m = sum * one_by_n of the ~13 A/B positions a thread
 //    owns.  For 8-bit data p < 2^24 and the set's s < 2^12, so z and B are single v_mad_u32_u24;
-//  * A' and B' are packed as A' << 20 | B' (A' <= 256, B' <= 65088): the un-weighted sum of a 3x3
-//    neighbourhood (9 * 256 < 2^12, 9 * 65088 < 2^20) stays inside its field, so the neighbourhood is
-//    gathered with PACKED adds and the 4/3 (r = 1) and 6/5 (r = 2) weights become 3*S9 + S5 and
-//    5*S6 + S2 on the unpacked fields;
+//  * the COMPLEMENT Ab = 256 - A' and B' are packed as Ab << 20 | B' (Ab <= 255, B' <= 65089): the
+//    un-weighted sum of a 3x3 neighbourhood (9 * 255 < 2^12, 9 * 65089 < 2^20) stays inside its field,
+//    so the neighbourhood is gathered with PACKED adds and the 4/3 (r = 1) and 6/5 (r = 2) weights
+//    become 3*S9 + S5 and 5*S6 + S2: of the Ab fields for ab (<= 8160), of the whole words modulo 2^32
+//    for W = ab * 2^20 + b + rounding (b < 32 * 65089 < 2^21);
 //  * a lane walks 8 rows of one column, so the horizontal triple sums are reused by three output rows;
-//  * flt - u is formed inside the rounding shift ((a*x + b + 256 - (x << 13)) >> 9), the five projection
+//  * flt - u is formed inside the rounding shift without the u << 9 term ((b - ab*x + 256) >> 9 as
+//    ab * -(x + 2^20) + W, see sgr8_filter), the five projection
 //    sums are v_mad_i32_i24 in int32 (|flt - u| <= 4084, 8 px * 16 lanes * 4084^2 < 2^31), reduced over
 //    16-lane rows with DPP adds and accumulated per parameter set with 64-bit LDS atomics: one global
 //    atomic per (tile, set, sum) at the very end;
@@ -252,27 +257,66 @@ __device__ __forceinline__ void sgr8_precompute(const uint16_t* __restrict__ in,
 
 }
 
-// A'/B' of one parameter set for the positions this thread owns (EbRestoration.c:787-858 / :926-985), packed A' << 20 | B'
-__device__ __forceinline__ void sgr8_build(uint32_t* __restrict__ abw, const uint32_t* __restrict__ xt, const uint32_t (&P)[S_KP], const uint32_t (&M)[S_KP],
+// The table of the 64 x 32-tile kernels: Ab = 256 - A' = 256 - eb_x_by_xplus1[min(z, 255)] as BYTES (Ab <= 255: A' >= 1), indexed by the UNCLAMPED
+// z = (p * s + 2^19) >> 20 and zero from index 255 on.  A 32-bit value >> 20 is at most 4095, so the read stays inside the table whatever p and s are;
+// what the assertions below guard is that z is EXACT: p fits the 24-bit multiply and p * s + 2^19 does not wrap, for the largest s of each radius in
+// kSgr and the largest p of sgr8_precompute at the deepest bit depth the kernels are instantiated for (10, which contains 8).
+constexpr int kSgrZTab = 4096, kSgrMaxBD = 10;
+constexpr unsigned long long sgr_max_s(int col) { unsigned long long m = 0; for (int e = 0; e < 16; e++) if (kSgrHost[e][col] > 0 && (unsigned long long)kSgrHost[e][col] > m) m = kSgrHost[e][col]; return m; }
+// p = a * n - d * d with a = round(sumsq / 4^(BD - 8)), d = round(sum / 2^(BD - 8)): for n samples of which k are mx and the others 0,
+// 4^(BD - 8) p <= k (n - k) mx^2 + 2^(BD - 8) n mx + 4^(BD - 8) n / 2 (both roundings against p), largest at k = n / 2
+constexpr unsigned long long sgr_max_p(int n, int bd) {
+    const unsigned long long mx = (1ull << bd) - 1, sh = 1ull << (bd - 8), k = n / 2;
+    return (k * (n - k) * mx * mx + sh * n * mx + sh * sh * n / 2 + sh * sh - 1) / (sh * sh);
+}
+constexpr unsigned long long kSgrPMax1 = sgr_max_p(9, kSgrMaxBD), kSgrPMax2 = sgr_max_p(25, kSgrMaxBD);   // 1 310 468, 10 210 064
+constexpr unsigned long long kSgrSMax1 = sgr_max_s(3), kSgrSMax2 = sgr_max_s(2);                           // r = 1: 3236, r = 2: 140
+constexpr unsigned long long kSgrZMax1 = (kSgrPMax1 * kSgrSMax1 + (1ull << 19)) >> 20, kSgrZMax2 = (kSgrPMax2 * kSgrSMax2 + (1ull << 19)) >> 20;   // 4044, 1363
+static_assert(kSgrPMax1 == 1310468ull && kSgrPMax2 == 10210064ull && kSgrSMax1 == 3236 && kSgrSMax2 == 140, "the figures quoted in the comments and in docs/kernels/sgr.md");
+static_assert(kSgrPMax1 * kSgrSMax1 + (1ull << 19) < (1ull << 32) && kSgrPMax2 * kSgrSMax2 + (1ull << 19) < (1ull << 32), "p * s + rounding must fit 32 bits");
+static_assert(kSgrPMax1 < (1ull << 24) && kSgrPMax2 < (1ull << 24), "p must fit a 24-bit multiply");
+static_assert(kSgrZMax1 < kSgrZTab && kSgrZMax2 < kSgrZTab, "the unclamped z must stay inside the table");
+// xt: kSgrZTab bytes, 16-byte aligned; 256 threads (the caller's next barrier publishes it)
+__device__ __forceinline__ void sgr8_fill_table(uint8_t* __restrict__ xt, int tid) {
+    const uint32_t A = tid == 0 ? 1u : (tid == 255 ? 256u : (uint32_t)((256 * tid + (tid + 1) / 2) / (tid + 1)));
+    xt[tid] = (uint8_t)(256u - A);
+    if (tid < (kSgrZTab - 256) / 16) ((uint4*)(xt + 256))[tid] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// Ab/B' of one position and parameter set (EbRestoration.c:787-858 / :926-985), packed Ab << 20 | B' with B' = (Ab * M + 2^11) >> 12 <= 65 089 at bit
+// depth 8 (Ab = 255, M = 25 * 255 * 164) and < 2^18 at bit depth 10: two multiply-adds, a shift, a byte read and a shift-or (compiled to one v_alignbit_b32)
+__device__ __forceinline__ uint32_t sgr8_ab_word(const uint8_t* __restrict__ xt, uint32_t p, uint32_t m, uint32_t s) {
+    const uint32_t z = (__umul24(p, s) + (1u << 19)) >> 20;
+    const uint32_t t = xt[z];
+    return (t << 20) | ((__umul24(t, m) + (1u << 11)) >> 12);
+}
+
+// Ab/B' of one parameter set for the positions this thread owns
+__device__ __forceinline__ void sgr8_build(uint32_t* __restrict__ abw, const uint8_t* __restrict__ xt, const uint32_t (&P)[S_KP], const uint32_t (&M)[S_KP],
                                            bool has0, bool has1, uint32_t s0, uint32_t s1, int tid) {
 #pragma unroll
     for (int k = 0; k < S_KP; k++) {
         const int i = tid + 256 * k;
-        if (i < S_N1 ? has1 : (has0 && i < S_NP)) {
-            const uint32_t z = (__umul24(P[k], i < S_N1 ? s1 : s0) + (1u << 19)) >> 20;
-            const uint32_t t = xt[min(z, 255u)];
-            const uint32_t B = (__umul24(t & 0x1FFu, M[k]) + (1u << 11)) >> 12;
-            abw[i] = (t & 0xFFF00000u) | B;
-        }
+        if (i < S_N1 ? has1 : (has0 && i < S_NP)) abw[i] = sgr8_ab_word(xt, P[k], M[k], i < S_N1 ? s1 : s0);
     }
 }
 
-#define FA_(v) ((v) >> 20)
-#define FB_(v) ((v) & 0xFFFFFu)
-// flt0 - u (D0) and flt1 - u (D1) of the 8 pixels (column j, rows i0 .. i0 + 7) of a lane; X = pixel, CX = 256 - (X << 13)
-__device__ __forceinline__ void sgr8_filter(const uint32_t* __restrict__ abw, int i0, int j, const uint32_t (&X)[8], const int32_t (&CX)[8], bool has0, bool has1,
+// 3 v and 5 v of a full 32-bit word, modulo 2^32, as ONE v_lshl_add_u32.  Written in C++ inside sgr8_filter -- (S6 << 2) + S6 + S2 + 256u next to
+// __mul24(ab, NX) -- the compiler (AMD clang 22.0.0git, roc-7.2.0) folds the shift-add into S6 * 5 and emits v_mov_b32 + v_mad_u64_u32 with S2 as the
+// addend, a quarter-rate instruction: 48 of them in sgr_search8_kernel<uint8_t, 8, 1> (profiles/r09/static_isa.txt).  The expression alone compiles to
+// v_lshl_add_u32 + v_add3_u32, so try the plain form again with a later compiler.
+__device__ __forceinline__ uint32_t sgr_times3(uint32_t v) { uint32_t r; asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(r) : "v"(v)); return r; }
+__device__ __forceinline__ uint32_t sgr_times5(uint32_t v) { uint32_t r; asm("v_lshl_add_u32 %0, %1, 2, %1" : "=v"(r) : "v"(v)); return r; }
+
+// flt0 - u (D0) and flt1 - u (D1) of the 8 pixels (column j, rows i0 .. i0 + 7) of a lane, in COMPLEMENT form.  The weights of a neighbourhood add up to
+// 32, so the weighted sum of A' is a = 8192 - ab with ab the same weighted sum of Ab (<= 32 * 255 = 8160), and a * x - (x << 13) = -ab * x: the reference's
+// (a * x + b + 256) >> 9 - (x << 4) is (b - ab * x + 256) >> 9.  The weighted sum of the PACKED words, W = 3 * S9 + S5 + 256 taken modulo 2^32, is
+// ab * 2^20 + b + 256 whatever its fields overflow into (it is linear), so the numerator is ab * NX + W with NX = -(x + 2^20) kept per pixel: one
+// v_mad_i32_i24 (|NX| < 2^23; the product wraps, the numerator itself is below 2^22 in magnitude, 2^24 at bit depth 10).  Only ab is unpacked, from the
+// un-weighted sums whose B' fields do not overflow (9 * 65 089 < 2^20).  Odd rows of r = 2 have weights that add up to 16: a = 4096 - ab, rounding 128, >> 8.
+__device__ __forceinline__ void sgr8_filter(const uint32_t* __restrict__ abw, int i0, int j, const int32_t (&NX)[8], bool has0, bool has1,
                                             int32_t (&D0)[8], int32_t (&D1)[8]) {
-        if (has1) {
+    if (has1) {
         const uint32_t* a1 = abw + i0 * S_PW + j + 1;   // row index = picture row + 1
         uint32_t Rm, Cm, R0, C0;
         { const uint32_t l = a1[-1], c = a1[0], r = a1[1]; Rm = l + c + r; Cm = c; }
@@ -283,8 +327,8 @@ __device__ __forceinline__ void sgr8_filter(const uint32_t* __restrict__ abw, in
             const uint32_t l = q[-1], c = q[0], rt = q[1];
             const uint32_t Rp = l + c + rt;
             const uint32_t S9 = Rm + R0 + Rp, S5 = Cm + R0 + c;     // 4 * cross + 3 * corners = 3 * S9 + S5
-            const uint32_t a = __umul24(FA_(S9), 3u) + FA_(S5), b = __umul24(FB_(S9), 3u) + FB_(S5);
-            D1[r] = (int32_t)(__umul24(a, X[r]) + b + (uint32_t)CX[r]) >> 9;
+            const uint32_t ab = __umul24(S9 >> 20, 3u) + (S5 >> 20), W = sgr_times3(S9) + S5 + 256u;
+            D1[r] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[r]) + W) >> 9;
             Rm = R0; Cm = C0; R0 = Rp; C0 = c;
         }
     }
@@ -297,56 +341,56 @@ __device__ __forceinline__ void sgr8_filter(const uint32_t* __restrict__ abw, in
         for (int q = 0; q < 4; q++) {
             {   // even row 2q: rows above/below, 6 * centres + 5 * sides = 5 * S6 + S2, >> 9
                 const uint32_t S6 = H[q] + H[q + 1], S2 = C[q] + C[q + 1];
-                const uint32_t a = __umul24(FA_(S6), 5u) + FA_(S2), b = __umul24(FB_(S6), 5u) + FB_(S2);
-                D0[2 * q] = (int32_t)(__umul24(a, X[2 * q]) + b + (uint32_t)CX[2 * q]) >> 9;
+                const uint32_t ab = __umul24(S6 >> 20, 5u) + (S2 >> 20), W = sgr_times5(S6) + S2 + 256u;
+                D0[2 * q] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[2 * q]) + W) >> 9;
             }
-            {   // odd row 2q + 1: own row, >> 8 (rounding and u scale by one bit less: CX >> 1 is exact)
-                const uint32_t a = __umul24(FA_(H[q + 1]), 5u) + FA_(C[q + 1]), b = __umul24(FB_(H[q + 1]), 5u) + FB_(C[q + 1]);
-                D0[2 * q + 1] = (int32_t)(__umul24(a, X[2 * q + 1]) + b + (uint32_t)(CX[2 * q + 1] >> 1)) >> 8;
+            {   // odd row 2q + 1: own row, >> 8
+                const uint32_t ab = __umul24(H[q + 1] >> 20, 5u) + (C[q + 1] >> 20), W = sgr_times5(H[q + 1]) + C[q + 1] + 128u;
+                D0[2 * q + 1] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[2 * q + 1]) + W) >> 8;
             }
         }
     }
 }
-#undef FA_
-#undef FB_
 
 
-// The same for bit depth 10: B' <= 2^18, so only the horizontal triple (3 B' < 2^20) stays packed; the vertical part of the
-// neighbourhood sums is formed on the unpacked halves.
-__device__ __forceinline__ void sgr10_filter(const uint32_t* __restrict__ abw, int i0, int j, const uint32_t (&X)[8], const int32_t (&CX)[8], bool has0, bool has1,
+// The same for bit depth 10: B' < 2^18, so only the horizontal triple (3 B' < 2^20) keeps its Ab field clean; ab is formed from the triples' and the centres'
+// upper fields, W from the packed words as they are (linear modulo 2^32: no B' half is ever unpacked).
+__device__ __forceinline__ void sgr10_filter(const uint32_t* __restrict__ abw, int i0, int j, const int32_t (&NX)[8], bool has0, bool has1,
                                              int32_t (&D0)[8], int32_t (&D1)[8]) {
     if (has1) {
         const uint32_t* a1 = abw + i0 * S_PW + j + 1;
-        uint32_t RmA, RmB, CmA, CmB, R0A, R0B, C0A, C0B;
-        { const uint32_t l = a1[-1], c = a1[0], r = a1[1], t = l + c + r; RmA = t >> 20; RmB = t & 0xFFFFFu; CmA = c >> 20; CmB = c & 0xFFFFFu; }
-        { const uint32_t l = a1[S_PW - 1], c = a1[S_PW], r = a1[S_PW + 1], t = l + c + r; R0A = t >> 20; R0B = t & 0xFFFFFu; C0A = c >> 20; C0B = c & 0xFFFFFu; }
+        uint32_t Rm, Cm, R0, C0, RmA, CmA, R0A, C0A;
+        { const uint32_t l = a1[-1], c = a1[0], r = a1[1]; Rm = l + c + r; Cm = c; RmA = Rm >> 20; CmA = c >> 20; }
+        { const uint32_t l = a1[S_PW - 1], c = a1[S_PW], r = a1[S_PW + 1]; R0 = l + c + r; C0 = c; R0A = R0 >> 20; C0A = c >> 20; }
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const uint32_t* q = a1 + (r + 2) * S_PW;
-            const uint32_t l = q[-1], c = q[0], rt = q[1], t = l + c + rt;
-            const uint32_t RpA = t >> 20, RpB = t & 0xFFFFFu, cA = c >> 20, cB = c & 0xFFFFFu;
-            const uint32_t a = __umul24(RmA + R0A + RpA, 3u) + (CmA + R0A + cA), b = __umul24(RmB + R0B + RpB, 3u) + (CmB + R0B + cB);
-            D1[r] = (int32_t)(__umul24(a, X[r]) + b + (uint32_t)CX[r]) >> 9;
-            RmA = R0A; RmB = R0B; CmA = C0A; CmB = C0B; R0A = RpA; R0B = RpB; C0A = cA; C0B = cB;
+            const uint32_t l = q[-1], c = q[0], rt = q[1], Rp = l + c + rt;
+            const uint32_t RpA = Rp >> 20, cA = c >> 20;
+            const uint32_t S9 = Rm + R0 + Rp, S5 = Cm + R0 + c;
+            const uint32_t ab = __umul24(RmA + R0A + RpA, 3u) + (CmA + R0A + cA), W = sgr_times3(S9) + S5 + 256u;
+            D1[r] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[r]) + W) >> 9;
+            Rm = R0; Cm = C0; R0 = Rp; C0 = c; RmA = R0A; CmA = C0A; R0A = RpA; C0A = cA;
         }
     }
     if (has0) {
         const uint32_t* a2 = abw + S_N1 + (i0 / 2) * S_PW + j + 1;
-        uint32_t HA[5], HB[5], CA[5], CB[5];
+        uint32_t H[5], C[5], HA[5], CA[5];
 #pragma unroll
         for (int q = 0; q < 5; q++) {
-            const uint32_t l = a2[q * S_PW - 1], c = a2[q * S_PW], r = a2[q * S_PW + 1], t = l + c + r;
-            HA[q] = t >> 20; HB[q] = t & 0xFFFFFu; CA[q] = c >> 20; CB[q] = c & 0xFFFFFu;
+            const uint32_t l = a2[q * S_PW - 1], c = a2[q * S_PW], r = a2[q * S_PW + 1];
+            H[q] = l + c + r; C[q] = c; HA[q] = H[q] >> 20; CA[q] = c >> 20;
         }
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             {
-                const uint32_t a = __umul24(HA[q] + HA[q + 1], 5u) + CA[q] + CA[q + 1], b = __umul24(HB[q] + HB[q + 1], 5u) + CB[q] + CB[q + 1];
-                D0[2 * q] = (int32_t)(__umul24(a, X[2 * q]) + b + (uint32_t)CX[2 * q]) >> 9;
+                const uint32_t S6 = H[q] + H[q + 1], S2 = C[q] + C[q + 1];
+                const uint32_t ab = __umul24(HA[q] + HA[q + 1], 5u) + CA[q] + CA[q + 1], W = sgr_times5(S6) + S2 + 256u;
+                D0[2 * q] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[2 * q]) + W) >> 9;
             }
             {
-                const uint32_t a = __umul24(HA[q + 1], 5u) + CA[q + 1], b = __umul24(HB[q + 1], 5u) + CB[q + 1];
-                D0[2 * q + 1] = (int32_t)(__umul24(a, X[2 * q + 1]) + b + (uint32_t)(CX[2 * q + 1] >> 1)) >> 8;
+                const uint32_t ab = __umul24(HA[q + 1], 5u) + CA[q + 1], W = sgr_times5(H[q + 1]) + C[q + 1] + 128u;
+                D0[2 * q + 1] = (int32_t)((uint32_t)__mul24((int32_t)ab, NX[2 * q + 1]) + W) >> 8;
             }
         }
     }
@@ -361,8 +405,8 @@ __device__ __forceinline__ void sgr10_filter(const uint32_t* __restrict__ abw, i
 #define SGR_STEP_(x, n, live, ctl) _Pragma("unroll") for (int q = 0; q < n; q++) if (live) x[q] += __builtin_amdgcn_mov_dpp(x[q], ctl, 0xF, 0xF, true);
 #define SGR_ROW_SUMS_(x, n, live) SGR_STEP_(x, n, live, DPP_QUAD_SWAP1) SGR_STEP_(x, n, live, DPP_QUAD_SWAP2) SGR_STEP_(x, n, live, DPP_ROW_HALF_MIRROR) SGR_STEP_(x, n, live, DPP_ROW_MIRROR)
 template <bool H0, bool H1, int STORE, int BD = 8>
-__device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, const uint32_t* __restrict__ xt, const uint32_t (&P)[S_KP], const uint32_t (&M)[S_KP], uint32_t s0,
-                                                  uint32_t s1, int tid, int i0, int j, const uint32_t (&X)[8], const int32_t (&CX)[8], const int32_t (&SV)[8],
+__device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, const uint8_t* __restrict__ xt, const uint32_t (&P)[S_KP], const uint32_t (&M)[S_KP], uint32_t s0,
+                                                  uint32_t s1, int tid, int i0, int j, const int32_t (&NX)[8], const int32_t (&SV)[8],
                                                   uint32_t* __restrict__ pairs_px, int dstride, int32_t* __restrict__ part_ep) {
 #pragma unroll
     for (int k = 0; k < S_KP; k++) {
@@ -371,16 +415,11 @@ __device__ __forceinline__ void sgr8_set_interior(uint32_t* __restrict__ abw, co
         const bool all1 = 256 * k + 255 < S_N1, none1 = 256 * k >= S_N1, in_np = 256 * k + 255 < S_NP;
         const bool is1 = all1 ? true : (none1 ? false : i < S_N1);
         const bool live = (in_np ? true : i < S_NP) && (is1 ? H1 : H0);
-        if (live) {
-            const uint32_t z = (__umul24(P[k], is1 ? s1 : s0) + (1u << 19)) >> 20;
-            const uint32_t t = xt[min(z, 255u)];
-            const uint32_t B = (__umul24(t & 0x1FFu, M[k]) + (1u << 11)) >> 12;
-            abw[i] = (t & 0xFFF00000u) | B;
-        }
+        if (live) abw[i] = sgr8_ab_word(xt, P[k], M[k], is1 ? s1 : s0);
     }
     __syncthreads();   // also orders this set's build after every lane's reads of the set before last (double buffer)
     int32_t D0[8], D1[8];
-    if (BD == 8) sgr8_filter(abw, i0, j, X, CX, H0, H1, D0, D1); else sgr10_filter(abw, i0, j, X, CX, H0, H1, D0, D1);
+    if (BD == 8) sgr8_filter(abw, i0, j, NX, H0, H1, D0, D1); else sgr10_filter(abw, i0, j, NX, H0, H1, D0, D1);
     if (STORE == 1) {
 #pragma unroll
         for (int r = 0; r < 8; r++) SGR_ST(&pairs_px[(size_t)r * dstride], ((uint32_t)(H0 ? D0[r] : 0) & 0xFFFFu) | ((uint32_t)(H1 ? D1[r] : 0) << 16));
@@ -469,8 +508,8 @@ sgr_search8_kernel(const SgrSearchPic a) {
     const uint32_t ep_mask = a.p[z].ep_mask;
     static_assert(STORE != 2 || BD == 8, "the packed difference words hold bit depth 8 only");
     __shared__ uint16_t in[S_IH * S_IW];
-    __shared__ uint32_t ab[2][S_NP];             // [0, N1): r = 1 positions, [N1, NP): r = 2 positions (odd rows)
-    __shared__ uint32_t xt[256];                 // eb_x_by_xplus1[z] << 20 | (256 - eb_x_by_xplus1[z])
+    __shared__ uint32_t ab[2][S_NP];             // [0, N1): r = 1 positions, [N1, NP): r = 2 positions (odd rows); 36 992 bytes of LDS in all: four workgroups per compute unit
+    __shared__ __attribute__((aligned(16))) uint8_t xt[kSgrZTab];   // 256 - eb_x_by_xplus1[min(z, 255)] (sgr8_fill_table)
     __shared__ unsigned long long acc[16][5];
     __shared__ unsigned long long acc_d2;
     const int tile = svt_xcd_order((int)blockIdx.x - a.first_tile[z], n_tiles), tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
@@ -484,8 +523,7 @@ sgr_search8_kernel(const SgrSearchPic a) {
     }
 
     {
-        const uint32_t A = tid == 0 ? 1u : (tid == 255 ? 256u : (uint32_t)((256 * tid + (tid + 1) / 2) / (tid + 1)));
-        xt[tid] = (A << 20) | (256u - A);
+        sgr8_fill_table(xt, tid);
         if (tid < 80) acc[tid / 5][tid % 5] = 0ull;
         if (tid == 80) acc_d2 = 0ull;
     }
@@ -505,13 +543,13 @@ sgr_search8_kernel(const SgrSearchPic a) {
     const int j = tid & 63, i0 = (tid >> 6) * 8;
     const int rlo = min(max(-(y0 + i0), 0), 8), rhi = min(max(ph - (y0 + i0), 0), 8);   // rows [rlo, rhi) of the 8 are inside the picture
     const bool colvalid = x0 + j < pw;
-    uint32_t X[8]; int32_t SV[8], CX[8];
+    uint32_t X[8]; int32_t SV[8], NX[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         X[r] = in[(i0 + r + 3) * S_IW + j + 3];
         const int yy = min(max(y0 + i0 + r, 0), ph - 1), xx = min(x0 + j, pw - 1);
         SV[r] = ((int32_t)src[(size_t)yy * src_stride + xx] - (int32_t)X[r]) << 4;     // (src << 4) - u
-        CX[r] = 256 - (int32_t)(X[r] << 13);                                           // rounding - (u << 9)
+        NX[r] = -(int32_t)(X[r] + (1u << 20));                                         // sgr8_filter's per-pixel factor
         if (STORE == 1 && colvalid && r >= rlo && r < rhi) sd[(size_t)(y0 + i0 + r) * dstride + x0 + j] = (int16_t)(-(SV[r] >> 4));   // dat - src
     }
     if (STORE) {   // sum of (dat - src)^2 over the unit: the constant term of the quadratic error model the walk speculates on
@@ -540,9 +578,9 @@ sgr_search8_kernel(const SgrSearchPic a) {
         uint32_t* abw = ab[buf];
         if (STORE != 2 && interior) {   // the common case as straight-line code, one instance per filter pair
             uint32_t* ppx = STORE == 1 ? &pairs[(size_t)ep * dplane + (size_t)(y0 + i0) * dstride + x0 + j] : nullptr;
-            if (has0 && has1) sgr8_set_interior<true, true, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, X, CX, SV, ppx, dstride, part + ep * 80);
-            else if (has1) sgr8_set_interior<false, true, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, X, CX, SV, ppx, dstride, part + ep * 80);
-            else sgr8_set_interior<true, false, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, X, CX, SV, ppx, dstride, part + ep * 80);
+            if (has0 && has1) sgr8_set_interior<true, true, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, NX, SV, ppx, dstride, part + ep * 80);
+            else if (has1) sgr8_set_interior<false, true, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, NX, SV, ppx, dstride, part + ep * 80);
+            else sgr8_set_interior<true, false, STORE, BD>(abw, xt, P, M, s0, s1, tid, i0, j, NX, SV, ppx, dstride, part + ep * 80);
             buf ^= 1;
             continue;
         }
@@ -551,7 +589,7 @@ sgr_search8_kernel(const SgrSearchPic a) {
 
         if (BD == 8) {
             int32_t D0[8], D1[8];
-            sgr8_filter(abw, i0, j, X, CX, has0, has1, D0, D1);
+            sgr8_filter(abw, i0, j, NX, has0, has1, D0, D1);
             if (STORE == 1 && colvalid) {   // (flt0 - u) | (flt1 - u) << 16: one dword per pixel and filter pair (64 lanes = 256 contiguous bytes per row)
 #pragma unroll
                 for (int r = 0; r < 8; r++)
@@ -593,7 +631,7 @@ sgr_search8_kernel(const SgrSearchPic a) {
         } else {
             // bit depth 10: |flt - u| < 2^14.1, a product < 2^28.1 -> four rows per int32 partial, 64-bit from the row reduction on
             int32_t D0[8], D1[8];
-            sgr10_filter(abw, i0, j, X, CX, has0, has1, D0, D1);
+            sgr10_filter(abw, i0, j, NX, has0, has1, D0, D1);
             if (STORE == 1 && colvalid) {   // (flt0 - u) | (flt1 - u) << 16: one dword per pixel and filter pair (64 lanes = 256 contiguous bytes per row)
 #pragma unroll
                 for (int r = 0; r < 8; r++)
@@ -661,7 +699,7 @@ sgr_proj_error_kernel(const PIX* __restrict__ dgd, int stride, const PIX* __rest
                       unsigned long long* __restrict__ err) {
     __shared__ uint16_t in[S_IH * S_IW];
     __shared__ uint32_t ab[2][S_NP];
-    __shared__ uint32_t xt[256];
+    __shared__ __attribute__((aligned(16))) uint8_t xt[kSgrZTab];
     __shared__ unsigned long long acc[16][kSgrMaxCand];
     const int x0 = blockIdx.x * S_TW, y0 = blockIdx.y * S_TH - voff, tid = threadIdx.x;
     const int unit = min((y0 + voff) / unit_size, units_y - 1) * units_x + min(x0 / unit_size, units_x - 1);
@@ -670,8 +708,7 @@ sgr_proj_error_kernel(const PIX* __restrict__ dgd, int stride, const PIX* __rest
         if (((ep_mask >> ep) & 1) && xqd[((size_t)unit * 16 + ep) * ncand * 2] == INT32_MIN) ep_mask &= ~(1u << ep);
     if (!ep_mask) return;
     {
-        const uint32_t A = tid == 0 ? 1u : (tid == 255 ? 256u : (uint32_t)((256 * tid + (tid + 1) / 2) / (tid + 1)));
-        xt[tid] = (A << 20) | (256u - A);
+        sgr8_fill_table(xt, tid);
         for (int k = tid; k < 16 * kSgrMaxCand; k += 256) acc[k / kSgrMaxCand][k % kSgrMaxCand] = 0ull;
     }
     batched_stage<6, uint16_t>(S_IH * S_IW, tid, 256,
@@ -687,13 +724,13 @@ sgr_proj_error_kernel(const PIX* __restrict__ dgd, int stride, const PIX* __rest
     const int j = tid & 63, i0 = (tid >> 6) * 8;
     const int rlo = min(max(-(y0 + i0), 0), 8), rhi = min(max(ph - (y0 + i0), 0), 8);
     const bool colvalid = x0 + j < pw;
-    uint32_t X[8]; int32_t BS[8], CX[8];
+    uint32_t X[8]; int32_t BS[8], NX[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         X[r] = in[(i0 + r + 3) * S_IW + j + 3];
         const int yy = min(max(y0 + i0 + r, 0), ph - 1), xx = min(x0 + j, pw - 1);
         BS[r] = (int32_t)(X[r] << 11) + (1 << 10) - ((int32_t)src[(size_t)yy * src_stride + xx] << 11);   // (u << 7) + rounding - (src << 11): e = (BS + xq . D) >> 11
-        CX[r] = 256 - (int32_t)(X[r] << 13);
+        NX[r] = -(int32_t)(X[r] + (1u << 20));
     }
     int buf = 0;
     for (int ep = 0; ep < 16; ep++) {
@@ -703,8 +740,8 @@ sgr_proj_error_kernel(const PIX* __restrict__ dgd, int stride, const PIX* __rest
         sgr8_build(abw, xt, P, M, has0, has1, (uint32_t)kSgr[ep][2], (uint32_t)kSgr[ep][3], tid);
         __syncthreads();
         int32_t D0[8], D1[8];
-        if constexpr (BD == 8) sgr8_filter(abw, i0, j, X, CX, has0, has1, D0, D1);
-        else sgr10_filter(abw, i0, j, X, CX, has0, has1, D0, D1);
+        if constexpr (BD == 8) sgr8_filter(abw, i0, j, NX, has0, has1, D0, D1);
+        else sgr10_filter(abw, i0, j, NX, has0, has1, D0, D1);
         const int32_t* q = xqd + ((size_t)unit * 16 + ep) * ncand * 2;
         for (int c = 0; c < ncand; c++) {
             const int32_t xqd0 = q[2 * c], xqd1 = q[2 * c + 1];
@@ -815,7 +852,7 @@ lr_apply8_kernel(const PIX* __restrict__ dgd, int stride, PIX* __restrict__ dst,
                  const int32_t* __restrict__ unit_xqd, const int16_t* __restrict__ unit_wiener, int tile_x0, int tile_y0) {
     __shared__ __attribute__((aligned(16))) uint16_t in[S_IH * S_IW];   // (rows are read as dwords by wiener_hpass)
     __shared__ uint32_t ab[2][S_NP];
-    __shared__ uint32_t xt[256];
+    __shared__ __attribute__((aligned(16))) uint8_t xt[kSgrZTab];
     const int tile = svt_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y), tile_y = tile / (int)gridDim.x, tile_x = tile - tile_y * (int)gridDim.x;
     const int x0 = (tile_x + tile_x0) * S_TW, y0 = (tile_y + tile_y0) * S_TH - voff, tid = threadIdx.x;   // (tile_x0, tile_y0): first tile of a partial launch
     const int unit = min((y0 + voff) / unit_size, units_y - 1) * units_x + min(x0 / unit_size, units_x - 1);
@@ -829,10 +866,7 @@ lr_apply8_kernel(const PIX* __restrict__ dgd, int stride, PIX* __restrict__ dst,
         return;
     }
     const StripeCtx<PIX> sc = lr_stripe_of<PIX>(dbl, dbl_stride, y0, voff, stripe_h, ph);
-    {
-        const uint32_t A = tid == 0 ? 1u : (tid == 255 ? 256u : (uint32_t)((256 * tid + (tid + 1) / 2) / (tid + 1)));
-        xt[tid] = (A << 20) | (256u - A);
-    }
+    sgr8_fill_table(xt, tid);
     lr_stage_tile<PIX>(in, dgd, stride, pw, ph, x0, y0, sc, tid, 256);
     __syncthreads();
     const int j = tid & 63, i0 = (tid >> 6) * 8;
@@ -858,12 +892,12 @@ lr_apply8_kernel(const PIX* __restrict__ dgd, int stride, PIX* __restrict__ dst,
     const bool has0 = kSgr[ep][0] > 0, has1 = kSgr[ep][1] > 0;
     sgr8_build(ab[0], xt, P, M, has0, has1, (uint32_t)kSgr[ep][2], (uint32_t)kSgr[ep][3], tid);
     __syncthreads();
-    uint32_t X[8]; int32_t CX[8];
+    uint32_t X[8]; int32_t NX[8];
 #pragma unroll
-    for (int r = 0; r < 8; r++) { X[r] = in[(i0 + r + 3) * S_IW + j + 3]; CX[r] = 256 - (int32_t)(X[r] << 13); }
+    for (int r = 0; r < 8; r++) { X[r] = in[(i0 + r + 3) * S_IW + j + 3]; NX[r] = -(int32_t)(X[r] + (1u << 20)); }
     int32_t D0[8], D1[8];
-    if constexpr (BD == 8) sgr8_filter(ab[0], i0, j, X, CX, has0, has1, D0, D1);
-    else sgr10_filter(ab[0], i0, j, X, CX, has0, has1, D0, D1);
+    if constexpr (BD == 8) sgr8_filter(ab[0], i0, j, NX, has0, has1, D0, D1);
+    else sgr10_filter(ab[0], i0, j, NX, has0, has1, D0, D1);
     // svt_decode_xq (EbRestoration.c:707-718)
     const int32_t xqd0 = unit_xqd[2 * unit], xqd1 = unit_xqd[2 * unit + 1];
     int32_t xq0, xq1;

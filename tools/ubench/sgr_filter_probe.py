@@ -5,7 +5,8 @@ a 3840x2160 picture 20 times under HIP events.
     python tools/ubench/sgr_filter_probe.py build     # here: hipcc, one executable per variant under tools/ubench/probe_bin/
     python tools/ubench/sgr_filter_probe.py run       # on the GPU box: runs them all, prints one line each
 
-PROBE bits: 1 no difference-word stores, 2 no projection sums (DPP reductions + LDS atomics), 4 no per-set barrier, 8 no A'/B' build, 16 no filter."""
+PROBE bits: 1 no difference-word stores, 2 no projection sums (DPP reductions + LDS atomics), 4 no per-set barrier, 8 no A'/B' build, 16 no filter, 32 no set at
+all, 64 every tile through the general body; 128 (results stay right) the pair word of the straight-line body as one v_perm_b32."""
 import os
 import subprocess
 import sys
@@ -14,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 SRC = os.path.join(ROOT, "svt-av1_amd", "csrc", "sgr.hip")
 BIN = os.path.join(HERE, "probe_bin")
-VARIANTS = [0, 1, 3, 11, 19, 27, 32, 64, 64 + 27]
+VARIANTS = [0, 1, 3, 11, 19, 27, 32, 64, 64 + 27, 128]
 
 MAIN = r'''
 #include <cstdio>
@@ -57,15 +58,18 @@ def patched():
         t = t.replace(old, new, count)
 
     # the patches go into sgr8_set_interior, the straight-line body every tile inside the picture runs
+    rep("SGR_ST(&pairs_px[(size_t)r * dstride], ((uint32_t)(H0 ? D0[r] : 0) & 0xFFFFu) | ((uint32_t)(H1 ? D1[r] : 0) << 16));",
+        "SGR_ST(&pairs_px[(size_t)r * dstride], (PROBE & 128) ? __builtin_amdgcn_perm((uint32_t)(H1 ? D1[r] : 0), (uint32_t)(H0 ? D0[r] : 0), 0x05040100u) : "
+        "(((uint32_t)(H0 ? D0[r] : 0) & 0xFFFFu) | ((uint32_t)(H1 ? D1[r] : 0) << 16)));")
     rep("    if (STORE == 1) {\n#pragma unroll\n        for (int r = 0; r < 8; r++) SGR_ST(&pairs_px", "    if (STORE == 1 && !(PROBE & 1)) {\n#pragma unroll\n        for (int r = 0; r < 8; r++) SGR_ST(&pairs_px")
     rep("    int32_t h[5] = {0, 0, 0, 0, 0};   // H00, H01, H11, C0, C1\n",
         "    if (PROBE & 2) { int32_t sk = 0;\n#pragma unroll\n for (int r = 0; r < 8; r++) sk ^= (H0 ? D0[r] : 0) ^ (H1 ? D1[r] : 0);\n if (sk == 0x7ABCDEF1) part_ep[0] = 1; return; }\n"
         "    int32_t h[5] = {0, 0, 0, 0, 0};   // H00, H01, H11, C0, C1\n")
     rep("    __syncthreads();   // also orders this set's build after every lane's reads of the set before last (double buffer)\n    int32_t D0[8], D1[8];",
         "    if (!(PROBE & 4)) __syncthreads();\n    int32_t D0[8], D1[8];")
-    rep("        if (live) {\n            const uint32_t z = (__umul24(P[k], is1 ? s1 : s0)", "        if (live && !(PROBE & 8)) {\n            const uint32_t z = (__umul24(P[k], is1 ? s1 : s0)")
-    rep("    if (BD == 8) sgr8_filter(abw, i0, j, X, CX, H0, H1, D0, D1); else sgr10_filter(abw, i0, j, X, CX, H0, H1, D0, D1);\n    if (STORE == 1",
-        "    if (!(PROBE & 16)) sgr8_filter(abw, i0, j, X, CX, H0, H1, D0, D1);\n    else {\n#pragma unroll\n for (int r = 0; r < 8; r++) { D0[r] = (int32_t)X[r] + (int32_t)s0; D1[r] = CX[r] - (int32_t)s1; } }\n    if (STORE == 1")
+    rep("        if (live) abw[i] = sgr8_ab_word(xt, P[k], M[k], is1 ? s1 : s0);", "        if (live && !(PROBE & 8)) abw[i] = sgr8_ab_word(xt, P[k], M[k], is1 ? s1 : s0);")
+    rep("    if (BD == 8) sgr8_filter(abw, i0, j, NX, H0, H1, D0, D1); else sgr10_filter(abw, i0, j, NX, H0, H1, D0, D1);\n    if (STORE == 1",
+        "    if (!(PROBE & 16)) sgr8_filter(abw, i0, j, NX, H0, H1, D0, D1);\n    else {\n#pragma unroll\n for (int r = 0; r < 8; r++) { D0[r] = NX[r] + (int32_t)s0; D1[r] = -NX[r] - (int32_t)s1; } }\n    if (STORE == 1")
     rep("    int buf = 0;\n    for (int ep = 0; ep < 16; ep++) {\n        if (!((cmask >> ep) & 1)) continue;", "    int buf = 0;\n    if (PROBE & 32) cmask = 0;\n    for (int ep = 0; ep < 16; ep++) {\n        if (!((cmask >> ep) & 1)) continue;", 1)
     rep("    const bool interior = x0 + S_TW <= pw && y0 >= 0 && y0 + S_TH <= ph;", "    const bool interior = x0 + S_TW <= pw && y0 >= 0 && y0 + S_TH <= ph && !(PROBE & 64);")
     # the general path (edge tiles; every tile with bit 64)
@@ -76,8 +80,8 @@ def patched():
     rep("                if (has0 && has1) atomicAdd(&acc[ep][1], (unsigned long long)(long long)h01);\n            }\n",
         "                if (has0 && has1) atomicAdd(&acc[ep][1], (unsigned long long)(long long)h01);\n            }\n            }\n")
     rep("        sgr8_build(abw, xt, P, M, has0, has1, s0, s1, tid);", "        if (!(PROBE & 8)) sgr8_build(abw, xt, P, M, has0, has1, s0, s1, tid);")
-    rep("            sgr8_filter(abw, i0, j, X, CX, has0, has1, D0, D1);",
-        "            if (!(PROBE & 16)) sgr8_filter(abw, i0, j, X, CX, has0, has1, D0, D1);\n            else {\n#pragma unroll\n for (int r = 0; r < 8; r++) { D0[r] = (int32_t)X[r] + ep; D1[r] = CX[r] - ep; } }")
+    rep("            sgr8_filter(abw, i0, j, NX, has0, has1, D0, D1);",
+        "            if (!(PROBE & 16)) sgr8_filter(abw, i0, j, NX, has0, has1, D0, D1);\n            else {\n#pragma unroll\n for (int r = 0; r < 8; r++) { D0[r] = NX[r] + ep; D1[r] = -NX[r] - ep; } }")
     return t + MAIN
 
 
