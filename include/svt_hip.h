@@ -681,6 +681,91 @@ typedef struct {
 int svt_hip_obmc_cost_batch_dev(SvtHipCtx *ctx, const uint8_t *d_pre, int pre_stride, const int32_t *d_wsrc, const int32_t *d_mask,
                                 const SvtHipObmcBlk *d_blks, int nblk, uint32_t *d_out);
 
+/* OBMC in mode decision, the two stages around those costs (csrc/obmc_search.h, obmc_search.hip; docs/kernels/obmc.md).  8-bit only, as in the reference: its
+ * high-bit-depth mode decision unpacks the neighbour predictions to 8 bits and reads the 8-bit source (precompute_obmc_data,
+ * Encoder/Codec/EbEncInterPrediction.c:2495-2522), and single_motion_search is "8bit path only" (Encoder/Codec/EbModeDecision.c:2958).
+ *
+ * 1. The weighted target: calc_target_weighted_pred (EbEncInterPrediction.c:2376-2437) with its visitors calc_target_weighted_pred_above (:2196-2224) and _left
+ *    (:2226-2256), for a list of blocks in one launch.  wsrc = 0, mask = 64; over the above segments, rows 0 .. (min(bh, 64) >> 1) - 1: wsrc = m1 * above, mask = m0;
+ *    both * 64; over the left segments, columns 0 .. (min(bw, 64) >> 1) - 1: wsrc = (wsrc >> 6) * m0 + (left << 6) * m1, mask = (mask >> 6) * m0; then
+ *    wsrc = src * 4096 - wsrc.  m0 = obmc_mask_N[position] (Common/Codec/EbInterPrediction.c:2233-2260, svt_av1_get_obmc_mask; the specification's Obmc_Mask_N),
+ *    m1 = 64 - m0.
+ *      bsize                : the reference's BlockSize; the 17 sizes with min(bw, bh) >= 8 (is_motion_variation_allowed_bsize)
+ *      x, y                 : the block's top-left sample in the source luma plane; the block lies inside the plane
+ *      n_above, above_rel[], above_len[] : 0 .. 4 segments in 4-sample units, what foreach_overlappable_nb_above (:918-958) hands its visitor (rel_mi_col,
+ *                             nb_mi_width); ascending, not overlapping, inside the block.  n_above = 0: !up_available, or no overlappable neighbour
+ *      n_left, left_rel[], left_len[]    : likewise for foreach_overlappable_nb_left (:960-996)
+ *      above_off, above_stride, left_off, left_stride : the neighbour predictions in the 8-bit pool d_nbr, addressed as the reference's `above` / `left`
+ *                             pointers: the sample of block column c, row r is d_nbr[off + r * stride + c].  Strides >= 0; only samples the passes read are checked
+ *      wm_off               : where the block's bw * bh wsrc and mask values go, as SvtHipObmcBlk::wm_off.  Ranges of two jobs must not overlap
+ *    jobs is HOST memory, checked before anything is launched and copied to the device by the call (stream-ordered).  Refused with SVT_HIP_ERR_BAD_ARG before the
+ *    device is touched: a NULL where a pointer is needed, njobs < 0 or above 2^24, a size outside the 17, a block outside the plane, a segment list that is not
+ *    ascending inside the block, a neighbour sample outside d_nbr, a wm_off range outside the arrays.
+ *    svt_hip_obmc_neighbours_host fills the segment lists of a job from the per-4x4 sb_type and is_neighbor_overlappable flag of the n4_w positions above and the
+ *    n4_h positions left of the block (index 0 = the block's first column / row; NULL = !up_available / !left_available): the mi_step == 1 pairing rule (back to
+ *    the even position, the flag of the odd one, step 2), the cap of a step at 16 units (BLOCK_64X64), nb_max = max_neighbor_obmc[log2 of the side in units] and the
+ *    cut at the picture's last column / row (mi_cols, mi_rows).  No device.  The neighbour predictions are plain single-reference predictions (the prediction entry
+ *    points above); the geometry of av1_setup_build_prediction_by_above_pred stays with the caller.
+ *
+ * 2. The motion refinement: single_motion_search (EbModeDecision.c:2951-3036) for a list of jobs in one launch.  mv_limits from mi_row, mi_col, the size, mi_rows,
+ *    mi_cols and AOM_INTERP_EXTEND, narrowed by svt_av1_set_mv_search_range(ref_mv) for the full-pel stage.  Full-pel: svt_av1_obmc_full_pixel_search
+ *    (Encoder/Codec/av1me.c:836-855): mv >> 3, clamp_mv, obmc_refining_search_sad (:791-834: neighbours {-1,0} {0,-1} {0,1} {1,0}, is_mv_in, `sad < best` then
+ *    `sad + mvsad_err_cost < best`, at most search_range = 8 steps), get_obmc_mvpred_var (:776-790).  Sub-pel: svt_av1_find_best_obmc_sub_pixel_tree_up (:1069-1254)
+ *    with forced_stop 0, iters_per_step 2, USE_8_TAPS, round 3 (2 when !allow_hp), on the limits as they were before the narrowing: set_subpel_mv_search_range,
+ *    upsampled_setup_obmc_center_error, per round the four axis probes, the diagonal chosen by cost_array[0] <= [1] / [2] <= [3], SECOND_LEVEL_CHECKS_BEST(1); the
+ *    unsigned / int mix of besterr, cost_array and INT_MAX, the slots of probes outside the range, the strict < and distortion / sse1 following the winner are the
+ *    reference's.  A probe is upsampled_obmc_pref_error (:973-1035) = svt_aom_upsampled_pred_c (Encoder/C_DEFAULT/variance.c:212-269, EIGHTTAP_REGULAR) +
+ *    svt_aom_obmc_variance{W}x{H}_c (:270-299).  rate_mv = svt_av1_mv_bit_cost with MV_COST_WEIGHT (108).
+ *      d_ref, ref_stride, width, height, pad_w, pad_h : the 8-bit reference luma plane; d_ref points at picture sample (0, 0), pad_w columns / pad_h rows of border
+ *                             lie around the picture (svt_hip_generate_padding_dev makes them).  The block of a job is at (4 mi_col, 4 mi_row) (svt_av1_setup_pred_block)
+ *      d_wsrc, d_mask, wm_samples : the arrays of stage 1; a mask value is 0 .. 4096
+ *      d_mv_joint_cost, d_mv_comp_cost : as svt_hip_ibc_full_search_batch_dev takes them
+ *      mv_*, ref_mv_*       : the candidate's vector and ref_mv in 1/8 sample, each inside -32768 .. 32767 (the reference's MV is two int16): with that, no
+ *                             difference the walks cost leaves the tables (the limits keep a probe within 1023 samples of ref_mv)
+ *    Result: status 0 = searched; full_row / full_col, refining, steps (moves of the refinement, 0 .. 8), bestsme of the full-pel stage; row / col (1/8 sample),
+ *    besterr, distortion, sse, rate_mv of the sub-pel stage.  status 1 = the narrowed limits are empty (the reference's clamp_mv has no meaning there): every
+ *    vector, steps, distortion, sse and rate_mv are 0 and refining, bestsme and besterr are INT32_MAX.
+ *    jobs is HOST memory, as in stage 1.  Refused with SVT_HIP_ERR_BAD_ARG before the device is touched: a NULL where a pointer is needed, njobs < 0 or above 2^24, a
+ *    size outside the 17, mi_row / mi_col outside the picture, a wm_off range outside the arrays, a vector component outside int16, negative sad_per_bit /
+ *    error_per_bit, allow_hp outside 0 / 1, and a plane whose border does not cover every sample the walk COULD read under its limits: the limits themselves, one
+ *    more whole sample, and the 8-tap filter's -3 .. +4 around the block.
+ * Not covered: force_integer_mv, scaled references (use_scaled_rec_refs_if_needed), choose_best_av1_mv_pred after the search, the chroma side of the final OBMC
+ * prediction, and a hook in the reference encoder.  Stream-ordered and asynchronous apart from the job upload. */
+typedef struct {
+    int32_t bsize, x, y;
+    int32_t n_above, above_rel[4], above_len[4];
+    int32_t n_left, left_rel[4], left_len[4];
+    int32_t above_off, above_stride, left_off, left_stride;
+    int32_t wm_off;
+} SvtHipObmcTargetJob;
+typedef struct {
+    int32_t bsize, mi_row, mi_col, wm_off;
+    int32_t mv_row, mv_col, ref_mv_row, ref_mv_col;
+    int32_t sad_per_bit, error_per_bit, allow_hp;
+} SvtHipObmcSearchJob;
+typedef struct {
+    int32_t  status;
+    int32_t  full_row, full_col, refining, steps, bestsme;
+    int32_t  row, col;
+    uint32_t besterr;
+    int32_t  distortion;
+    uint32_t sse;
+    int32_t  rate_mv;
+} SvtHipObmcSearchResult;
+int svt_hip_obmc_neighbours_host(const uint8_t *above_sb_type, const uint8_t *above_overlappable, const uint8_t *left_sb_type, const uint8_t *left_overlappable,
+                                 int mi_rows, int mi_cols, int mi_row, int mi_col, int bsize, SvtHipObmcTargetJob *job);
+int svt_hip_obmc_target_batch_dev(SvtHipCtx *ctx, const uint8_t *d_src, int src_stride, int width, int height, const uint8_t *d_nbr, int64_t nbr_samples,
+                                  const SvtHipObmcTargetJob *jobs, int njobs, int32_t *d_wsrc, int32_t *d_mask, int64_t wm_samples);
+int svt_hip_obmc_search_batch_dev(SvtHipCtx *ctx, const uint8_t *d_ref, int ref_stride, int width, int height, int pad_w, int pad_h, int mi_rows, int mi_cols,
+                                  const int32_t *d_wsrc, const int32_t *d_mask, int64_t wm_samples, const int32_t *d_mv_joint_cost, const int32_t *d_mv_comp_cost,
+                                  const SvtHipObmcSearchJob *jobs, int njobs, SvtHipObmcSearchResult *d_results);
+/* the same two contracts on host pointers, serially, from csrc/obmc_search.h: no context */
+int svt_hip_obmc_target_host(const uint8_t *src, int src_stride, int width, int height, const uint8_t *nbr, int64_t nbr_samples, const SvtHipObmcTargetJob *jobs,
+                             int njobs, int32_t *wsrc, int32_t *mask, int64_t wm_samples);
+int svt_hip_obmc_search_host(const uint8_t *ref, int ref_stride, int width, int height, int pad_w, int pad_h, int mi_rows, int mi_cols, const int32_t *wsrc,
+                             const int32_t *mask, int64_t wm_samples, const int32_t *mv_joint_cost, const int32_t *mv_comp_cost, const SvtHipObmcSearchJob *jobs,
+                             int njobs, SvtHipObmcSearchResult *results);
+
 /* Warped (affine) prediction of a list of blocks of one plane: svt_av1_warp_affine / svt_av1_highbd_warp_affine (Common/Codec/EbWarpedMotion.c:577, :733),
  * the non-compound path of svt_warp_plane / svt_highbd_warp_plane.  mat = EbWarpedMotionParams::wmmat[0..5], alpha .. delta = its shear
  * parameters (svt_get_shear_params, :921, stays on the host); (p_col, p_row, p_width, p_height) = the block in the destination plane, any size

@@ -144,6 +144,24 @@ class ObmcBlk(C.Structure):
     _fields_ = [("pre_x", C.c_int32), ("pre_y", C.c_int32), ("w", C.c_uint8), ("h", C.c_uint8), ("xoffset", C.c_uint8), ("yoffset", C.c_uint8), ("wm_off", C.c_int32)]
 
 
+class ObmcTargetJob(C.Structure):
+    """SvtHipObmcTargetJob (include/svt_hip.h)."""
+    _fields_ = [("bsize", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("n_above", C.c_int32), ("above_rel", C.c_int32 * 4), ("above_len", C.c_int32 * 4),
+                ("n_left", C.c_int32), ("left_rel", C.c_int32 * 4), ("left_len", C.c_int32 * 4), ("above_off", C.c_int32), ("above_stride", C.c_int32),
+                ("left_off", C.c_int32), ("left_stride", C.c_int32), ("wm_off", C.c_int32)]
+
+
+class ObmcSearchJob(C.Structure):
+    """SvtHipObmcSearchJob (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "mi_row", "mi_col", "wm_off", "mv_row", "mv_col", "ref_mv_row", "ref_mv_col", "sad_per_bit", "error_per_bit", "allow_hp")]
+
+
+class ObmcSearchResult(C.Structure):
+    """SvtHipObmcSearchResult (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_uint32 if n in ("besterr", "sse") else C.c_int32) for n in ("status", "full_row", "full_col", "refining", "steps", "bestsme", "row", "col", "besterr",
+                                                                                   "distortion", "sse", "rate_mv")]
+
+
 class WarpBlk(C.Structure):
     """SvtHipWarpBlk (include/svt_hip.h)."""
     _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16),
@@ -446,6 +464,46 @@ def ibc_full_search_host(plane, table, joint_cost, comp_cost, patterns, jobs, bd
     return res
 
 
+def obmc_neighbours_host(above, left, mi_rows, mi_cols, mi_row, mi_col, bsize, job=None):
+    """svt_hip_obmc_neighbours_host: `above` / `left` = (sb_type, overlappable) of the 4x4 units along the block's top / left edge, or None when there is no such
+    neighbour.  Fills the segment lists of `job` (a fresh ObmcTargetJob when None) and returns it."""
+    job = ObmcTargetJob(bsize=bsize) if job is None else job
+    keep = [None if side is None else [np.ascontiguousarray(a, np.uint8) for a in side] for side in (above, left)]
+    args = [None if a is None else a.ctypes.data_as(C.c_void_p) for side in keep for a in (side or (None, None))]
+    rc = lib().svt_hip_obmc_neighbours_host(*args, mi_rows, mi_cols, mi_row, mi_col, bsize, C.byref(job))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_obmc_neighbours_host refused its arguments: status {rc}")
+    return job
+
+
+def obmc_target_host(plane, nbr, jobs, wm_samples):
+    """svt_hip_obmc_target_host: `plane` the 2-D uint8 source luma plane, `nbr` the flat uint8 pool of neighbour predictions, `jobs` a ctypes array of
+    ObmcTargetJob.  -> (wsrc, mask), int32[wm_samples] each, zero where no job writes."""
+    _, p, stride, w, h = _plane_args(plane)
+    nbr = np.ascontiguousarray(nbr, np.uint8)
+    wsrc, mask = np.zeros(max(wm_samples, 1), np.int32), np.zeros(max(wm_samples, 1), np.int32)
+    rc = lib().svt_hip_obmc_target_host(p, stride, w, h, nbr.ctypes.data_as(C.c_void_p), nbr.size, C.cast(jobs, C.c_void_p), len(jobs), wsrc.ctypes.data_as(C.c_void_p),
+                                        mask.ctypes.data_as(C.c_void_p), wm_samples)
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_obmc_target_host refused its arguments: status {rc}")
+    return wsrc[:wm_samples], mask[:wm_samples]
+
+
+def obmc_search_host(picture, pad_w, pad_h, mi_rows, mi_cols, wsrc, mask, joint_cost, comp_cost, jobs):
+    """svt_hip_obmc_search_host: `picture` the 2-D uint8 view of the reference picture inside its padded plane (pad_w / pad_h samples of border around it), `wsrc` /
+    `mask` int32 as obmc_target_host returns them, the cost tables as ibc_cost_tables takes them, `jobs` a ctypes array of ObmcSearchJob.  -> ObmcSearchResult * njobs."""
+    _, p, stride, w, h = _plane_args(picture)
+    j, c = ibc_cost_tables(joint_cost, comp_cost)
+    wsrc, mask = np.ascontiguousarray(wsrc, np.int32), np.ascontiguousarray(mask, np.int32)
+    assert wsrc.size == mask.size
+    res = (ObmcSearchResult * max(len(jobs), 1))()
+    rc = lib().svt_hip_obmc_search_host(p, stride, w, h, pad_w, pad_h, mi_rows, mi_cols, wsrc.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), wsrc.size,
+                                        j.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), C.cast(jobs, C.c_void_p), len(jobs), C.cast(res, C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_obmc_search_host refused its arguments: status {rc}")
+    return res
+
+
 class CompSearchJob(C.Structure):
     """SvtHipCompSearchJob (include/svt_hip.h)."""
     _fields_ = [(n, C.c_uint32 if n == "full_lambda" else C.c_int32) for n in ("kind", "bsize", "x", "y", "pred0", "pred1", "quantizer", "full_lambda", "wedge_rate",
@@ -719,6 +777,11 @@ PROTOTYPES = {
     # ---- compound inter prediction
     "svt_hip_compound_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]),
     "svt_hip_obmc_cost_batch_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, vp]),
+    "svt_hip_obmc_neighbours_host": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svt_hip_obmc_target_batch_dev": (i32, [vp, vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, vp, C.c_int64]),
+    "svt_hip_obmc_search_batch_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, i32, vp]),
+    "svt_hip_obmc_target_host": (i32, [vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, vp, C.c_int64]),
+    "svt_hip_obmc_search_host": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, i32, vp]),
     "svt_hip_warp_predict_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32]),
     "svt_hip_warp_compound_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, i32]),
     "svt_hip_blend_a64_batch_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32]),
@@ -1151,6 +1214,43 @@ class Context:
                       rates.size, C.cast(jobs, C.c_void_p), n, d_r, d_c)
             self.sync()
             return s.structs_back(d_r, rk), (s.structs_back(d_c, ck) if cands else None)
+
+    # ---- OBMC in mode decision: the weighted target and the motion refinement
+    def obmc_batch(self, plane=None, nbr=None, target_jobs=None, wm_samples=0, search=None, wsrc=None, mask=None, fill=0xC3):
+        """svt_hip_obmc_target_batch_dev and / or svt_hip_obmc_search_batch_dev, back to back on the context's stream with no synchronisation between them.
+        Target (when `target_jobs` is not None): `plane` the 2-D uint8 source luma plane, `nbr` the flat uint8 pool of neighbour predictions, `target_jobs` a ctypes
+        array of ObmcTargetJob; wsrc / mask start as the byte `fill`.  Search (when `search` is not None): a dict of picture (the 2-D uint8 view of the reference
+        picture inside its padded plane), pad_w, pad_h, mi_rows, mi_cols, joint_cost, comp_cost, jobs (a ctypes array of ObmcSearchJob); it reads the target
+        stage's arrays, or `wsrc` / `mask` (int32) when there is no target stage; the results start as the byte `fill`.
+        -> (wsrc, mask, ObmcSearchResult * njobs or None); wsrc / mask are None without a target stage."""
+        with self.scope() as s:
+            res = d_r = None
+            if target_jobs is not None:
+                h, w = plane.shape
+                nbr = np.ascontiguousarray(nbr, np.uint8)
+                p, d_n = s.plane(plane), s.upload(nbr)
+                d_w, d_m = s.filled(max(wm_samples, 1) * 4, fill, np.uint8), s.filled(max(wm_samples, 1) * 4, fill, np.uint8)
+                self.call("obmc_target_batch_dev", p.ptr, p.stride, w, h, d_n, nbr.size, C.cast(target_jobs, C.c_void_p), len(target_jobs), d_w, d_m, wm_samples)
+            else:
+                wsrc, mask = np.ascontiguousarray(wsrc, np.int32), np.ascontiguousarray(mask, np.int32)
+                assert wsrc.size == mask.size
+                d_w, d_m, wm_samples = s.upload(wsrc), s.upload(mask), wsrc.size
+            if search is not None:
+                pic = search["picture"]
+                h, w = pic.shape
+                j, c = ibc_cost_tables(search["joint_cost"], search["comp_cost"])
+                r, d_jc, d_cc = s.plane(pic), s.upload(j), s.upload(c)
+                n = len(search["jobs"])
+                kind = ObmcSearchResult * max(n, 1)
+                d_r = s.filled(C.sizeof(kind), fill, np.uint8)
+                self.call("obmc_search_batch_dev", r.ptr, r.stride, w, h, search["pad_w"], search["pad_h"], search["mi_rows"], search["mi_cols"], d_w, d_m, wm_samples,
+                          d_jc, d_cc, C.cast(search["jobs"], C.c_void_p), n, d_r)
+            self.sync()
+            if d_r is not None:
+                res = s.structs_back(d_r, kind)
+            if target_jobs is None:
+                return None, None, res
+            return s.download(d_w, (max(wm_samples, 1),), np.int32)[:wm_samples], s.download(d_m, (max(wm_samples, 1),), np.int32)[:wm_samples], res
 
     def filter_intra_predict_batch(self, edges, jobs, dst, bd=None):
         """svt_hip_filter_intra_predict_batch_dev: `edges` a flat uint8 / uint16 array of edge records, `jobs` a ctypes array of FilterIntraJob, `dst` the 2-D

@@ -11,6 +11,7 @@
 #include "ibc_hash.h"
 #include "ibc_search.h"
 #include "comp_search.h"
+#include "obmc_search.h"
 #include <vector>
 
 extern "C" {
@@ -355,6 +356,31 @@ int svt_hip_compound_search_host(const double* rate, const double* dist, const i
     std::vector<uint8_t> masks(cs::WEDGE_TABLE_BYTES);
     cs::wedge_table_build(masks.data());
     cs::search_host(pix_bytes, bd, src, src_stride, pred, rates, masks.data(), cs::RdTables{rate, dist, bsize_cat}, jobs, njobs, results, cand);
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- OBMC in mode decision: obmc_search.h run serially */
+int svt_hip_obmc_neighbours_host(const uint8_t* above_sb_type, const uint8_t* above_overlappable, const uint8_t* left_sb_type, const uint8_t* left_overlappable, int mi_rows,
+                                 int mi_cols, int mi_row, int mi_col, int bsize, SvtHipObmcTargetJob* job) {
+    return obmc::neighbours_host(above_sb_type, above_overlappable, left_sb_type, left_overlappable, mi_rows, mi_cols, mi_row, mi_col, bsize, job) ? SVT_HIP_OK
+                                                                                                                                                   : SVT_HIP_ERR_BAD_ARG;
+}
+
+/* the contract of svt_hip_obmc_target_batch_dev on host pointers */
+int svt_hip_obmc_target_host(const uint8_t* src, int src_stride, int width, int height, const uint8_t* nbr, int64_t nbr_samples, const SvtHipObmcTargetJob* jobs, int njobs,
+                             int32_t* wsrc, int32_t* mask, int64_t wm_samples) {
+    if (!obmc::target_args_ok(src, src_stride, width, height, nbr, nbr_samples, jobs, njobs, wsrc, mask, wm_samples)) return SVT_HIP_ERR_BAD_ARG;
+    obmc::target_host(src, src_stride, nbr, jobs, njobs, wsrc, mask);
+    return SVT_HIP_OK;
+}
+
+/* the contract of svt_hip_obmc_search_batch_dev on host pointers */
+int svt_hip_obmc_search_host(const uint8_t* ref, int ref_stride, int width, int height, int pad_w, int pad_h, int mi_rows, int mi_cols, const int32_t* wsrc,
+                             const int32_t* mask, int64_t wm_samples, const int32_t* mv_joint_cost, const int32_t* mv_comp_cost, const SvtHipObmcSearchJob* jobs, int njobs,
+                             SvtHipObmcSearchResult* results) {
+    const obmc::Plane P{ref, ref_stride, width, height, pad_w, pad_h, mi_rows, mi_cols};
+    if (!obmc::search_args_ok(P, wsrc, mask, wm_samples, mv_joint_cost, mv_comp_cost, jobs, njobs, results)) return SVT_HIP_ERR_BAD_ARG;
+    obmc::search_host(P, wsrc, mask, wm_samples, mv_joint_cost, mv_comp_cost, jobs, njobs, results);
     return SVT_HIP_OK;
 }
 

@@ -61,6 +61,11 @@ int svt_hip_launch_compound_predict(hipStream_t st, int pix_bytes, int bd, const
 int svt_hip_launch_obmc_cost(hipStream_t st, const uint8_t* pre, int pre_stride, const int32_t* wsrc, const int32_t* mask, const SvtHipObmcBlk* blks, int n, uint32_t* out);
 int svt_hip_launch_blend_a64(hipStream_t st, int pix_bytes, const void* src0, int src0_stride, const void* src1, int src1_stride, void* dst, int dst_stride,
                              const uint8_t* masks, const SvtHipBlendBlk* blks, int n);
+/* obmc_search.hip; the arithmetic both sides share is obmc_search.h.  Every pointer is device memory; the jobs have passed obmc::target_job_ok / obmc::job_status */
+int svt_hip_launch_obmc_target(hipStream_t st, const uint8_t* src, int stride, const uint8_t* nbr, const SvtHipObmcTargetJob* jobs, int njobs, int32_t* wsrc, int32_t* mask);
+int svt_hip_launch_obmc_search(hipStream_t st, const uint8_t* ref, int stride, int width, int height, int pad_w, int pad_h, int mi_rows, int mi_cols, const int32_t* wsrc,
+                               const int32_t* mask, int64_t wm_samples, const int32_t* joint_cost, const int32_t* comp_cost, const SvtHipObmcSearchJob* jobs, int njobs,
+                               SvtHipObmcSearchResult* results);
 /* comp_search.hip; the arithmetic both sides share is comp_search.h.  Every pointer is device memory; the jobs have passed cs::job_ok */
 int svt_hip_launch_compound_search(hipStream_t st, int pix_bytes, int bd, const void* src, int stride, const void* pred, const int32_t* rates, const uint8_t* masks,
                                    const double* rate_grid, const double* dist_grid, const int32_t* bsize_cat, const SvtHipCompSearchJob* jobs, int njobs,
