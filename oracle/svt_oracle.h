@@ -208,6 +208,8 @@ void orc_wiener_compute_stats(int win, const void *dgd, const void *src, int pix
                               int dgd_stride, int src_stride, int64_t *M, int64_t *H);
 void orc_wiener_convolve_add_src(const void *src, int src_stride, void *dst, int dst_stride, int pix_bytes, const int16_t *filter_x,
                                  const int16_t *filter_y, int w, int h, int bd);
+void orc_wiener_convolve_add_src_rounds(const void *src, int src_stride, void *dst, int dst_stride, int pix_bytes, const int16_t *filter_x,
+                                        const int16_t *filter_y, int w, int h, int bd, int r0, int r1);
 void orc_wiener_stats_plane(int win, const void *dgd, int dgd_stride, const void *src, int src_stride, int pix_bytes, int bd, int pw, int ph, int ss_y,
                             int unit_size, int64_t *M, int64_t *H);
 /* search_wiener_seg between the statistics and the refinement (EbRestorationPick.c:1388-1407): 1 = refine vfilter / hfilter, 2 = no Wiener filter for the unit */

@@ -49,8 +49,13 @@ void orc_wiener_compute_stats(int win, const void *dgd, const void *src, int pix
  * filter_x / filter_y: 8 int16 (tap 7 = 0), round_0 = 3, round_1 = 11 for 8 / 10 bit (get_conv_params_wiener, convolve.h:78-95). */
 void orc_wiener_convolve_add_src(const void *src, int src_stride, void *dst, int dst_stride, int pix_bytes, const int16_t *filter_x,
                                  const int16_t *filter_y, int w, int h, int bd) {
-    const int r0 = 3, r1 = 11, ih = h + 6;   /* tap 7 is 0 (the reference still reads row h + 3 / column w + 3 for it, its pictures have wide
-                                               * borders; here nothing outside the 3-sample context is touched) */
+    orc_wiener_convolve_add_src_rounds(src, src_stride, dst, dst_stride, pix_bytes, filter_x, filter_y, w, h, bd, 3, 11);
+}
+/* ... with the rounding pair of the caller's ConvolveParams: (3, 11) at 8 / 10 bit, (5, 9) at 12 bit (get_conv_params_wiener) */
+void orc_wiener_convolve_add_src_rounds(const void *src, int src_stride, void *dst, int dst_stride, int pix_bytes, const int16_t *filter_x,
+                                        const int16_t *filter_y, int w, int h, int bd, int r0, int r1) {
+    const int ih = h + 6;   /* tap 7 is 0 (the reference still reads row h + 3 / column w + 3 for it, its pictures have wide
+                             * borders; here nothing outside the 3-sample context is touched) */
     const int lim = (1 << (bd + 1 + 7 - r0)) - 1;   /* WIENER_CLAMP_LIMIT - 1 */
     uint16_t *tmp = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)w * ih);
     for (int y = 0; y < ih; y++)           /* rows -3 .. h+2 */

@@ -1,8 +1,8 @@
 """GPU: what the C-ABI layer (csrc/svt_hip_api.cpp) answers to calls it refuses, with a live context: the return code and the exact text svt_hip_last_error()
 gives afterwards.  Some refusals carry a text and some leave the context's text as it was; the per-call table (csrc/rtcd_hip.cpp) tells a device failure from a
 domain delegation by exactly that, so both are pinned.  The families here are the ones the other live-context tests do not refuse anything in: transforms,
-deblocking, the CDEF frame calls, the md_* pictures, pyramids / SAD loops, the temporal filter's three entry points, the 2-D copies and the self-guided unit search, plus the zero-size successes that
-return before anything is enqueued.
+deblocking, the CDEF frame calls, the md_* pictures, pyramids / SAD loops, the temporal filter's three entry points, the 2-D copies and the self-guided unit search, the per-call list and single-unit
+forms (percall.hip), plus the zero-size successes that return before anything is enqueued.
 
 No kernel is meant to run.  Every case is built so that a lost check shows as a failed assertion and not as a launch on bad memory: every pointer lies in one
 allocation of the context, every count (nblk, n, njobs, n_sb) is 0 and the one wrong thing is a scalar.  The expected values are the ones the entry points had
@@ -277,6 +277,40 @@ CASES = [
     ("cdef_find_dir-coeff_shift", lambda e: e.L.svt_hip_cdef_find_dir_batch_dev(e.h, e.d, 64, e.d, 0, 5, e.d, e.d), BAD_ARG, SAME),
     ("cdef_finish-sb_count", lambda e: e.L.svt_hip_cdef_finish_dev(e.h, e.d, e.d, -1, e.d, 0, None, e.d, None, None, None), BAD_ARG, SAME),
     ("cdef_select-end_gi", lambda e: e.L.svt_hip_cdef_strength_select_dev(e.h, e.d, e.d, 0, 0, 65, e.d, e.pkg.CDEF_SELECT_STATE_BYTES), BAD_ARG, SAME),
+    # the per-call list and single-unit forms: none of their refusals sets a text (the per-call table reads that as "delegate", not as a device failure)
+    ("ext_all_sad-n", lambda e: e.L.svt_hip_ext_all_sad_8x8_16x16_batch_dev(e.h, e.d, 64, e.d, 64, e.d, -1, e.d), BAD_ARG, SAME),
+    ("ext_all_sad-empty", lambda e: e.L.svt_hip_ext_all_sad_8x8_16x16_batch_dev(e.h, e.d, 64, e.d, 64, e.d, 0, e.d), OK, SAME),
+    ("ext_eight_sad-n", lambda e: e.L.svt_hip_ext_eight_sad_32x32_64x64_batch_dev(e.h, e.d, -1, e.d), BAD_ARG, SAME),
+    ("ext_eight_sad-empty", lambda e: e.L.svt_hip_ext_eight_sad_32x32_64x64_batch_dev(e.h, e.d, 0, e.d), OK, SAME),
+    ("interm_var-n", lambda e: e.L.svt_hip_interm_var_four8x8_batch_dev(e.h, e.d, 64, e.d, -1, e.d, e.d), BAD_ARG, SAME),
+    ("interm_var-empty", lambda e: e.L.svt_hip_interm_var_four8x8_batch_dev(e.h, e.d, 64, e.d, 0, e.d, e.d), OK, SAME),
+    ("upsampled_pred-n", lambda e: e.L.svt_hip_upsampled_pred_batch_dev(e.h, e.d, 64, e.d, e.d, -1), BAD_ARG, SAME),
+    ("upsampled_pred-empty", lambda e: e.L.svt_hip_upsampled_pred_batch_dev(e.h, e.d, 64, e.d, e.d, 0), OK, SAME),
+    ("cdef_filter_block-n", lambda e: e.L.svt_hip_cdef_filter_block_batch_dev(e.h, e.d, 144, e.d, -1, e.d, None, 64), BAD_ARG, SAME),
+    ("cdef_filter_block-empty", lambda e: e.L.svt_hip_cdef_filter_block_batch_dev(e.h, e.d, 144, e.d, 0, None, e.d, 64), OK, SAME),
+    ("search_one_dual-nb_strengths", lambda e: e.L.svt_hip_cdef_search_one_dual_dev(e.h, e.d, e.d, 0, e.d, e.d, 8, 0, 64, e.d), BAD_ARG, SAME),
+    ("search_one_dual-end_gi", lambda e: e.L.svt_hip_cdef_search_one_dual_dev(e.h, e.d, e.d, 0, e.d, e.d, 0, 0, 65, e.d), BAD_ARG, SAME),
+    ("search_one_dual-start_gi", lambda e: e.L.svt_hip_cdef_search_one_dual_dev(e.h, e.d, e.d, 0, e.d, e.d, 0, 17, 16, e.d), BAD_ARG, SAME),
+    ("search_one_dual-sb_count", lambda e: e.L.svt_hip_cdef_search_one_dual_dev(e.h, e.d, e.d, -1, e.d, e.d, 0, 0, 64, e.d), BAD_ARG, SAME),
+    ("convolve8-step", lambda e: e.L.svt_hip_convolve8_dev(e.h, 0, e.d, 64, e.d, 64, e.d, 0, 65, 8, 8), BAD_ARG, SAME),
+    ("convolve8-q0", lambda e: e.L.svt_hip_convolve8_dev(e.h, 1, e.d, 64, e.d, 64, e.d, 16, 16, 8, 8), BAD_ARG, SAME),
+    ("convolve8-w", lambda e: e.L.svt_hip_convolve8_dev(e.h, 0, e.d, 64, e.d, 64, e.d, 0, 16, 0, 8), BAD_ARG, SAME),
+    ("wiener_convolve-round_0", lambda e: e.L.svt_hip_wiener_convolve_add_src_dev(e.h, 1, 8, e.d, 64, e.d, 64, e.d, 8, 8, 8, 11), BAD_ARG, SAME),
+    ("wiener_convolve-bd", lambda e: e.L.svt_hip_wiener_convolve_add_src_dev(e.h, 2, 13, e.d, 64, e.d, 64, e.d, 8, 8, 3, 11), BAD_ARG, SAME),
+    ("wiener_convolve-h", lambda e: e.L.svt_hip_wiener_convolve_add_src_dev(e.h, 1, 8, e.d, 64, e.d, 64, e.d, 8, 0, 3, 11), BAD_ARG, SAME),
+    ("jnt_convolve-variant", lambda e: e.L.svt_hip_jnt_convolve_dev(e.h, 1, 8, 4, e.d, 64, e.d, 64, e.d, 64, e.d, 8, 8, 3, 7, 0, 0, 0, 0), BAD_ARG, SAME),
+    ("jnt_convolve-round_0", lambda e: e.L.svt_hip_jnt_convolve_dev(e.h, 1, 8, 0, e.d, 64, e.d, 64, e.d, 64, e.d, 8, 8, 2, 7, 0, 0, 0, 0), BAD_ARG, SAME),
+    ("jnt_convolve-round_1", lambda e: e.L.svt_hip_jnt_convolve_dev(e.h, 2, 10, 0, e.d, 64, e.d, 64, e.d, 64, e.d, 8, 8, 5, 10, 0, 0, 0, 0), BAD_ARG, SAME),
+    ("jnt_convolve-8bit-bytes-bd10", lambda e: e.L.svt_hip_jnt_convolve_dev(e.h, 1, 10, 0, e.d, 64, e.d, 64, e.d, 64, e.d, 8, 8, 3, 7, 0, 0, 0, 0), BAD_ARG, SAME),
+    ("diffwtd_mask-round", lambda e: e.L.svt_hip_diffwtd_mask_dev(e.h, 2, e.d, e.d, 64, e.d, 64, 8, 8, 0, 16, 0), BAD_ARG, SAME),
+    ("diffwtd_mask-shift", lambda e: e.L.svt_hip_diffwtd_mask_dev(e.h, 2, e.d, e.d, 64, e.d, 64, 8, 8, 0, 0, 9), BAD_ARG, SAME),
+    ("diffwtd_mask-elem_bytes", lambda e: e.L.svt_hip_diffwtd_mask_dev(e.h, 3, e.d, e.d, 64, e.d, 64, 8, 8, 0, 0, 0), BAD_ARG, SAME),
+    ("blend_a64_d16-round_0", lambda e: e.L.svt_hip_blend_a64_d16_dev(e.h, 1, 8, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 8, 8, 0, 0, 6, 7), BAD_ARG, SAME),
+    ("blend_a64_d16-bd", lambda e: e.L.svt_hip_blend_a64_d16_dev(e.h, 2, 13, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 8, 8, 0, 0, 3, 7), BAD_ARG, SAME),
+    ("blend_a64_d16-w", lambda e: e.L.svt_hip_blend_a64_d16_dev(e.h, 1, 8, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 0, 8, 0, 0, 3, 7), BAD_ARG, SAME),
+    ("sgr_flt_proj-mode", lambda e: e.L.svt_hip_sgr_flt_proj_dev(e.h, 1, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 8, 8, 2, 1, 2, e.hp, e.d, e.d), BAD_ARG, SAME),
+    ("sgr_flt_proj-pix_bytes", lambda e: e.L.svt_hip_sgr_flt_proj_dev(e.h, 3, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 8, 8, 2, 1, 0, e.hp, e.d, e.d), BAD_ARG, SAME),
+    ("sgr_flt_proj-w", lambda e: e.L.svt_hip_sgr_flt_proj_dev(e.h, 1, e.d, 64, e.d, 64, e.d, 64, e.d, 64, 0, 8, 2, 1, 1, e.hp, e.d, e.d), BAD_ARG, SAME),
     # md pictures
     ("md_sad-n_pus", lambda e: md_sad(e, n_pus=0), BAD_ARG, SAME),
     ("md_sad-n_refs", lambda e: md_sad(e, n_refs=0), BAD_ARG, SAME),
