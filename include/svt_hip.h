@@ -876,6 +876,68 @@ int svt_hip_compound_search_host(const double *rate, const double *dist, const i
                                  int height, const void *pred, int64_t pred_samples, const int32_t *rates, int nrates, const SvtHipCompSearchJob *jobs, int njobs,
                                  SvtHipCompSearchResult *results, SvtHipCompSearchCand *cand);
 
+/* ------------------------------------------------------------------ the dual interpolation filter search of mode decision ---- */
+/* interpolation_filter_search (Encoder/Codec/EbEncInterPrediction.c:3047-3297) for a list of blocks, one launch (csrc/ifs_search.h, ifs_search.hip;
+ * docs/kernels/ifs.md).  The nine candidates are filter_sets[i] = {y filter, x filter} (:3034-3045; 0 EIGHTTAP_REGULAR, 1 EIGHTTAP_SMOOTH, 2 MULTITAP_SHARP), with
+ * interp_filters = y | x << 16 (av1_make_interp_filters, Common/Codec/filter.h:59-67).  Per candidate, luma only as the reference (use_uv = EB_FALSE):
+ *   prediction  type -1, one reference: what convolve[subpel_x != 0][subpel_y != 0][0] dispatches to, svt_av1_[highbd_]convolve_{2d_copy,x,y,2d}_sr
+ *               (Common/Codec/EbInterPrediction.c:349-469, :744-866), i.e. svt_hip_subpel_predict_batch_dev mode 0 with the candidate's banks; type 0 COMPOUND_AVERAGE
+ *               and 1 COMPOUND_DISTANCE, two references: the svt_av1_[highbd_]jnt_convolve_{2d_copy,x,y,2d} pair (:552-741, :944-1143) and the combination of
+ *               svt_hip_compound_predict_batch_dev, one filter pair for both references.  A direction whose phase is 0 does not see its filter.
+ *   sse         svt_spatial_full_distortion_kernel / svt_full_distortion_kernel16_bits against the source block (model_rd_for_sb, :2903-2996)
+ *   rate, dist  model_rd_from_sse (:2877-2901) -> svt_av1_model_rd_from_var_lapndz (:2855-2875) -> model_rd_norm (:2795-2853) on
+ *               ROUND_POWER_OF_TWO(sse, 2 * (bd - 8)), quantizer >> (bd - 5) and num_pels_log2_lookup[bsize]; dist <<= 4; rate += rate_tab[0][y] + rate_tab[1][x],
+ *               the caller's six values of svt_av1_get_switchable_rate (:2760-2789: switchable_interp_fac_bitss[ctx of dir 0][y] and [ctx of dir 1][x])
+ *   rd          RDCOST(full_lambda, rate, dist) as that file defines it (:2792-2793)
+ * The decision: order 0, the interpolation_search_level && enable_dual_filter branch, ascending over all nine with a strict `<` (the first minimum wins; its second
+ * loop cannot change the result, csrc/ifs_search.h); order 1, the else branch, descending from 8 to 0 with a strict `<` (among equals the highest index wins), with
+ * dual = 0 over the pairs with equal filters only; it also gives ifs_is_regular_last (regular_last; -1 under order 0, which does not touch it).
+ *   d_src, src_stride, width, height : the source luma plane (pix_bytes 1 with bd 8; pix_bytes 2 with bd 8 or 10); every block lies inside it
+ *   d_ref0 / d_ref1 : the reference planes; ref*_x / ref*_y are the caller's integer positions, already clamped, as for the prediction calls.  EVERY reference block
+ *                     is readable exactly 3 samples left and above and 4 samples right and below of it, whatever its phases; nothing further is read.  d_ref1
+ *                     may be NULL when no job has two references
+ *   d_dst           : NULL, or a plane that receives the winner's luma prediction of every job at (dst_x, dst_y): what svt_hip_subpel_predict_batch_dev /
+ *                     svt_hip_compound_predict_batch_dev write with the winner's banks
+ *                     The destination rectangle is NOT validated: (dst_x, dst_y) and dst_stride are the caller's, like the reference positions and strides, as for
+ *                     the prediction calls; rectangles of one call must not overlap
+ *   jobs            : HOST memory, checked before anything is launched and copied to the device by the call (stream-ordered)
+ *   d_results       : njobs results
+ *   d_cand          : NULL, or njobs * SVT_HIP_IFS_CANDS records; a pair that was not evaluated is {-1, 0, 0, 0}
+ * Refused with SVT_HIP_ERR_BAD_ARG before anything touches the device: a NULL where a pointer is needed, a two-reference job without d_ref1, a size with a dimension
+ * below 8 (17 sizes remain: the caller's cap is 4, so the 4-tap kernels are never reached), a block outside the source plane, a phase above 15, an unknown type or
+ * order, offsets that do not sum to 16 for type 1, quantizer outside 1 .. 32767, a sample format other than the three, njobs < 0 or above 2^24.  Stream-ordered
+ * and asynchronous apart from the job upload. */
+#define SVT_HIP_IFS_CANDS 9
+typedef struct {
+    int32_t  bsize;                    /* the reference's BlockSize (3 = 8x8 .. 15 = 128x128, 18 .. 21) */
+    int32_t  x, y;                     /* the block's top-left sample in the source plane */
+    int32_t  ref0_x, ref0_y, ref1_x, ref1_y; /* integer position of the block's top-left sample in reference plane 0 / 1 */
+    int32_t  subpel0_x, subpel0_y, subpel1_x, subpel1_y; /* q4 phases 0 .. 15 */
+    int32_t  type;                     /* -1 one reference, 0 COMPOUND_AVERAGE, 1 COMPOUND_DISTANCE */
+    int32_t  fwd_offset, bck_offset;   /* type 1: a row of quant_dist_lookup_table, sum 16 */
+    int32_t  order, dual;              /* the branch of the decision; dual = enable_dual_filter (read under order 1) */
+    int32_t  quantizer;                /* y_dequant_q3[base_q_idx][1] of the depth in use */
+    uint32_t full_lambda;              /* full_lambda_md of the depth in use, >> 2 * (bd - 8) as the reference divides it */
+    int32_t  rate_tab[2][3];           /* [0][y filter], [1][x filter] */
+    int32_t  dst_x, dst_y;             /* where the winner's prediction goes in d_dst */
+} SvtHipIfsJob;
+typedef struct {
+    int32_t  best;                     /* 0 .. 8 */
+    uint32_t interp_filters;
+    int32_t  switchable_rate;          /* what the reference adds to fast_luma_rate */
+    int32_t  regular_last;
+    int64_t  rd;
+} SvtHipIfsResult;
+typedef struct {
+    int64_t rate, sse, dist, rd;       /* rate: as it enters RDCOST, the two filter symbols included; sse: before the depth rounding */
+} SvtHipIfsCand;
+int svt_hip_ifs_search_batch_dev(SvtHipCtx *ctx, int pix_bytes, int bd, const void *d_src, int src_stride, int width, int height, const void *d_ref0, int ref0_stride,
+                                 const void *d_ref1, int ref1_stride, void *d_dst, int dst_stride, const SvtHipIfsJob *jobs, int njobs, SvtHipIfsResult *d_results,
+                                 SvtHipIfsCand *d_cand);
+/* the same on host pointers, serially, from csrc/ifs_search.h: no context */
+int svt_hip_ifs_search_host(int pix_bytes, int bd, const void *src, int src_stride, int width, int height, const void *ref0, int ref0_stride, const void *ref1,
+                            int ref1_stride, void *dst, int dst_stride, const SvtHipIfsJob *jobs, int njobs, SvtHipIfsResult *results, SvtHipIfsCand *cand);
+
 /* ------------------------------------------------------------------ picture formats around the high-bit-depth path ---- */
 /* The reference keeps 10-bit pictures as an 8-bit plane + a 2-bit plane; these are its conversions to / from the 16-bit samples the
  * kernels above take (Common/C_DEFAULT/EbPackUnPack_C.c):

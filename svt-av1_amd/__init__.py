@@ -559,6 +559,43 @@ def compound_search_host(grids, plane, pool, rates, jobs, bd=None, cands=True):
     return res, cand
 
 
+class IfsJob(C.Structure):
+    """SvtHipIfsJob (include/svt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("bsize", "x", "y", "ref0_x", "ref0_y", "ref1_x", "ref1_y", "subpel0_x", "subpel0_y", "subpel1_x", "subpel1_y", "type", "fwd_offset",
+                                         "bck_offset", "order", "dual", "quantizer")] + [("full_lambda", C.c_uint32), ("rate_tab", (C.c_int32 * 3) * 2), ("dst_x", C.c_int32),
+                                                                                         ("dst_y", C.c_int32)]
+
+
+class IfsResult(C.Structure):
+    """SvtHipIfsResult (include/svt_hip.h)."""
+    _fields_ = [("best", C.c_int32), ("interp_filters", C.c_uint32), ("switchable_rate", C.c_int32), ("regular_last", C.c_int32), ("rd", C.c_int64)]
+
+
+class IfsCand(C.Structure):
+    """SvtHipIfsCand (include/svt_hip.h)."""
+    _fields_ = [("rate", C.c_int64), ("sse", C.c_int64), ("dist", C.c_int64), ("rd", C.c_int64)]
+
+
+IFS_CANDS = 9   # SVT_HIP_IFS_CANDS
+
+
+def ifs_search_host(src, ref0, ref1, jobs, dst=None, bd=None, cands=True):
+    """svt_hip_ifs_search_host: `src` the 2-D source luma plane, `ref0` / `ref1` 2-D views whose sample (0, 0) is the reference picture's (the arrays behind them
+    hold the border; ref1 may be None), `dst` None or the 2-D plane the winners' predictions are written into in place, all of one dtype; `jobs` a ctypes array of
+    IfsJob.  -> (IfsResult * njobs, IfsCand * (9 njobs) or None)."""
+    pb, p, stride, w, h = _plane_args(src)
+    planes = [_plane_args(a) if a is not None else (pb, None, 0, 0, 0) for a in (ref0, ref1, dst)]
+    assert all(a is None or a.dtype == src.dtype for a in (ref0, ref1, dst))
+    n = len(jobs)
+    res = (IfsResult * max(n, 1))()
+    cand = (IfsCand * (IFS_CANDS * max(n, 1)))() if cands else None
+    rc = lib().svt_hip_ifs_search_host(pb, default_bd(pb, bd), p, stride, w, h, planes[0][1], planes[0][2], planes[1][1], planes[1][2], planes[2][1], planes[2][2],
+                                       C.cast(jobs, C.c_void_p), n, C.cast(res, C.c_void_p), C.cast(cand, C.c_void_p) if cands else None)
+    if rc != 0:
+        raise RuntimeError(f"svt_hip_ifs_search_host refused its arguments: status {rc}")
+    return res, cand
+
+
 class UpscalePlane(C.Structure):
     """SvtHipUpscalePlane (include/svt_hip.h)."""
     _fields_ = [("d_src", C.c_void_p), ("src_stride", C.c_int32), ("in_w", C.c_int32), ("d_dst", C.c_void_p), ("dst_stride", C.c_int32), ("out_w", C.c_int32),
@@ -859,6 +896,9 @@ PROTOTYPES = {
     "svt_hip_set_rd_curvfit_grids": (i32, [vp, vp, vp, vp]),
     "svt_hip_compound_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, i32, vp, vp]),
     "svt_hip_compound_search_host": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, C.c_int64, vp, i32, vp, i32, vp, vp]),
+    # ---- the dual interpolation filter search
+    "svt_hip_ifs_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
+    "svt_hip_ifs_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
     "svt_hip_ibc_full_search_scratch_bytes": (sz, [i32]),
     "svt_hip_ibc_full_search_batch_dev": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, sz]),
     "svt_hip_ibc_full_search_host": (i32, [i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
@@ -1214,6 +1254,30 @@ class Context:
                       rates.size, C.cast(jobs, C.c_void_p), n, d_r, d_c)
             self.sync()
             return s.structs_back(d_r, rk), (s.structs_back(d_c, ck) if cands else None)
+
+    # ---- the dual interpolation filter search
+    def ifs_search_batch(self, src, ref0, ref1, jobs, dst=None, bd=None, cands=True, fill=0xC3, calls=1, lists=None):
+        """svt_hip_ifs_search_batch_dev: `src` the 2-D source luma plane, `ref0` / `ref1` 2-D views whose sample (0, 0) is the reference picture's (the arrays behind
+        them hold the border and are uploaded whole; ref1 may be None), `dst` None or the initial content of the destination plane, all of one dtype; `jobs` a ctypes
+        array of IfsJob.  Results and candidate records start as the byte `fill`.  `calls` > 1 repeats the call back to back on the stream with no synchronisation in
+        between; `lists` = [(first, count), ...] launches those parts of the list in that order instead of the whole, each writing its own part of the outputs.
+        -> (IfsResult * njobs, IfsCand * (9 njobs) or None, dst after the calls or None)."""
+        h, w = src.shape
+        n = len(jobs)
+        rk, ck = IfsResult * max(n, 1), IfsCand * (IFS_CANDS * max(n, 1))
+        with self.scope() as s:
+            p, r0 = s.plane(src), s.plane(ref0)
+            r1 = s.plane(ref1) if ref1 is not None else None
+            d = s.plane(dst) if dst is not None else None
+            d_r = s.filled(C.sizeof(rk), fill, np.uint8)
+            d_c = s.filled(C.sizeof(ck), fill, np.uint8) if cands else None
+            for _ in range(calls):
+                for first, count in (lists if lists is not None else [(0, n)]):
+                    self.call("ifs_search_batch_dev", src.itemsize, default_bd(src.itemsize, bd), p.ptr, p.stride, w, h, r0.ptr, r0.stride, r1 and r1.ptr, r1.stride if r1 else 0,
+                              d and d.ptr, d.stride if d else 0, C.cast(C.byref(jobs, first * C.sizeof(IfsJob)), C.c_void_p), count,
+                              C.c_void_p(d_r.value + first * C.sizeof(IfsResult)), C.c_void_p(d_c.value + first * IFS_CANDS * C.sizeof(IfsCand)) if cands else None)
+            self.sync()
+            return s.structs_back(d_r, rk), (s.structs_back(d_c, ck) if cands else None), (s.plane_back(d) if d else None)
 
     # ---- OBMC in mode decision: the weighted target and the motion refinement
     def obmc_batch(self, plane=None, nbr=None, target_jobs=None, wm_samples=0, search=None, wsrc=None, mask=None, fill=0xC3):

@@ -17,6 +17,7 @@
 #include "scaled_pred.h"
 #include "comp_search.h"
 #include "obmc_search.h"
+#include "ifs_search.h"
 #include <mutex>
 
 struct SvtHipCtx {
@@ -41,8 +42,8 @@ struct SvtHipCtx {
     bool        rd_grids_set = false;
     void*       comp_jobs = nullptr;      // device staging of svt_hip_compound_search_batch_dev's job list, grown on demand
     size_t      comp_jobs_bytes = 0;
-    void*       obmc_jobs[2] = {nullptr, nullptr};   // device staging of the job lists of svt_hip_obmc_target_batch_dev [0] and svt_hip_obmc_search_batch_dev [1]
-    size_t      obmc_jobs_bytes[2] = {0, 0};
+    void*       job_stage[3] = {nullptr, nullptr, nullptr};   // device staging of the job lists of svt_hip_obmc_target_batch_dev [0], svt_hip_obmc_search_batch_dev [1]
+    size_t      job_stage_bytes[3] = {0, 0, 0};               // and svt_hip_ifs_search_batch_dev [2], each grown on demand
     std::string err;
 };
 
@@ -142,7 +143,7 @@ void svt_hip_destroy(SvtHipCtx* c) {
     if (c->wedge_masks) (void)hipFree(c->wedge_masks);
     if (c->rd_grids) (void)hipFree(c->rd_grids);
     if (c->comp_jobs) (void)hipFree(c->comp_jobs);
-    for (void* p : c->obmc_jobs)
+    for (void* p : c->job_stage)
         if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -277,7 +278,7 @@ int svt_hip_host_free(SvtHipCtx* c, void* host) {
     if (host) HIPCHK(c, hipHostFree(host));
     return SVT_HIP_OK;
 }
-#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(comp_search) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(obmc_search) X(palette) X(percall) X(pyramid) X(resize) X(scaled_pred) X(sgr) X(sgr_walk) X(tf_subpel) \
+#define SVT_HIP_TUS(X) X(cdef) X(cdef_select) X(comp_search) X(compound) X(conv) X(deblock) X(distortion) X(format) X(gm) X(gm_fit) X(gm_front) X(ibc_hash) X(ibc_search) X(ifs_search) X(intra) X(intra_cfl) X(md_pre) X(me_fullpel) X(obmc_search) X(palette) X(percall) X(pyramid) X(resize) X(scaled_pred) X(sgr) X(sgr_walk) X(tf_subpel) \
     X(tfilter) X(tpl) X(tpl_synth) X(txfm2d) X(warp) X(wiener)
 #define X(n) int svt_hip_tu_probe_##n();
 SVT_HIP_TUS(X)
@@ -490,16 +491,16 @@ int svt_hip_compound_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const
 // svt_hip_obmc_search_batch_dev: single_motion_search (Encoder/Codec/EbModeDecision.c:2951-3036) = svt_av1_obmc_full_pixel_search (Encoder/Codec/av1me.c:836-855) +
 // svt_av1_find_best_obmc_sub_pixel_tree_up (:1069-1254) + svt_av1_mv_bit_cost.  What each refuses is obmc::target_args_ok / obmc::search_args_ok, shared with the host forms.
 // the job list of a call, host memory that has been checked, in the context's staging buffer `slot`: stream-ordered, grown on demand
-static int obmc_stage_jobs(SvtHipCtx* c, int slot, const void* jobs, size_t bytes) {
-    if (bytes > c->obmc_jobs_bytes[slot]) {
+static int stage_jobs(SvtHipCtx* c, int slot, const void* jobs, size_t bytes) {
+    if (bytes > c->job_stage_bytes[slot]) {
         HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still read the old list
-        if (c->obmc_jobs[slot]) (void)hipFree(c->obmc_jobs[slot]);
-        c->obmc_jobs[slot] = nullptr;
-        c->obmc_jobs_bytes[slot] = 0;
-        HIPCHK(c, hipMalloc(&c->obmc_jobs[slot], bytes));
-        c->obmc_jobs_bytes[slot] = bytes;
+        if (c->job_stage[slot]) (void)hipFree(c->job_stage[slot]);
+        c->job_stage[slot] = nullptr;
+        c->job_stage_bytes[slot] = 0;
+        HIPCHK(c, hipMalloc(&c->job_stage[slot], bytes));
+        c->job_stage_bytes[slot] = bytes;
     }
-    HIPCHK(c, hipMemcpyAsync(c->obmc_jobs[slot], jobs, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->job_stage[slot], jobs, bytes, hipMemcpyHostToDevice, c->stream));
     return SVT_HIP_OK;
 }
 
@@ -509,8 +510,8 @@ int svt_hip_obmc_target_batch_dev(SvtHipCtx* c, const uint8_t* d_src, int src_st
     if (!c || !obmc::target_args_ok(d_src, src_stride, width, height, d_nbr, nbr_samples, jobs, njobs, d_wsrc, d_mask, wm_samples))
         return bad_arg(c, "svt_hip_obmc_target_batch_dev: bad argument");
     if (!njobs) return SVT_HIP_OK;
-    if (int rc = obmc_stage_jobs(c, 0, jobs, (size_t)njobs * sizeof(SvtHipObmcTargetJob))) return rc;
-    return launched(c, svt_hip_launch_obmc_target(c->stream, d_src, src_stride, d_nbr, (const SvtHipObmcTargetJob*)c->obmc_jobs[0], njobs, d_wsrc, d_mask),
+    if (int rc = stage_jobs(c, 0, jobs, (size_t)njobs * sizeof(SvtHipObmcTargetJob))) return rc;
+    return launched(c, svt_hip_launch_obmc_target(c->stream, d_src, src_stride, d_nbr, (const SvtHipObmcTargetJob*)c->job_stage[0], njobs, d_wsrc, d_mask),
                     "OBMC target launch");
 }
 
@@ -522,10 +523,25 @@ int svt_hip_obmc_search_batch_dev(SvtHipCtx* c, const uint8_t* d_ref, int ref_st
     if (!c || !obmc::search_args_ok(P, d_wsrc, d_mask, wm_samples, d_mv_joint_cost, d_mv_comp_cost, jobs, njobs, d_results))
         return bad_arg(c, "svt_hip_obmc_search_batch_dev: bad argument");
     if (!njobs) return SVT_HIP_OK;
-    if (int rc = obmc_stage_jobs(c, 1, jobs, (size_t)njobs * sizeof(SvtHipObmcSearchJob))) return rc;
+    if (int rc = stage_jobs(c, 1, jobs, (size_t)njobs * sizeof(SvtHipObmcSearchJob))) return rc;
     return launched(c, svt_hip_launch_obmc_search(c->stream, d_ref, ref_stride, width, height, pad_w, pad_h, mi_rows, mi_cols, d_wsrc, d_mask, wm_samples, d_mv_joint_cost,
-                                                  d_mv_comp_cost, (const SvtHipObmcSearchJob*)c->obmc_jobs[1], njobs, d_results),
+                                                  d_mv_comp_cost, (const SvtHipObmcSearchJob*)c->job_stage[1], njobs, d_results),
                     "OBMC search launch");
+}
+
+/* ---------------------------------------------------------------------------------- the dual interpolation filter search of mode decision (ifs_search.hip) */
+// interpolation_filter_search (Encoder/Codec/EbEncInterPrediction.c:3047-3297) for a list of blocks.  What it refuses is ifs::search_args_ok, shared with the host form.
+int svt_hip_ifs_search_batch_dev(SvtHipCtx* c, int pix_bytes, int bd, const void* d_src, int src_stride, int width, int height, const void* d_ref0, int ref0_stride,
+                                 const void* d_ref1, int ref1_stride, void* d_dst, int dst_stride, const SvtHipIfsJob* jobs, int njobs, SvtHipIfsResult* d_results,
+                                 SvtHipIfsCand* d_cand) {
+    SVT_HIP_ENTER(c);
+    if (!c || !ifs::search_args_ok(pix_bytes, bd, d_src, src_stride, width, height, d_ref0, ref0_stride, d_ref1, ref1_stride, d_dst, dst_stride, jobs, njobs, d_results))
+        return bad_arg(c, "svt_hip_ifs_search_batch_dev: bad argument");
+    if (!njobs) return SVT_HIP_OK;
+    if (int rc = stage_jobs(c, 2, jobs, (size_t)njobs * sizeof(SvtHipIfsJob))) return rc;
+    return launched(c, svt_hip_launch_ifs_search(c->stream, pix_bytes, bd, d_src, src_stride, d_ref0, ref0_stride, d_ref1, ref1_stride, d_dst, dst_stride,
+                                                 (const SvtHipIfsJob*)c->job_stage[2], njobs, d_results, d_cand),
+                    "interpolation filter search launch");
 }
 
 /* ---------------------------------------------------------------------------------- TPL dispenser */

@@ -12,6 +12,7 @@
 #include "ibc_search.h"
 #include "comp_search.h"
 #include "obmc_search.h"
+#include "ifs_search.h"
 #include <vector>
 
 extern "C" {
@@ -381,6 +382,15 @@ int svt_hip_obmc_search_host(const uint8_t* ref, int ref_stride, int width, int 
     const obmc::Plane P{ref, ref_stride, width, height, pad_w, pad_h, mi_rows, mi_cols};
     if (!obmc::search_args_ok(P, wsrc, mask, wm_samples, mv_joint_cost, mv_comp_cost, jobs, njobs, results)) return SVT_HIP_ERR_BAD_ARG;
     obmc::search_host(P, wsrc, mask, wm_samples, mv_joint_cost, mv_comp_cost, jobs, njobs, results);
+    return SVT_HIP_OK;
+}
+
+/* ------------------------------------------------------------------------------------------- the dual interpolation filter search: ifs_search.h run serially */
+/* the contract of svt_hip_ifs_search_batch_dev on host pointers */
+int svt_hip_ifs_search_host(int pix_bytes, int bd, const void* src, int src_stride, int width, int height, const void* ref0, int ref0_stride, const void* ref1, int ref1_stride,
+                            void* dst, int dst_stride, const SvtHipIfsJob* jobs, int njobs, SvtHipIfsResult* results, SvtHipIfsCand* cand) {
+    if (!ifs::search_args_ok(pix_bytes, bd, src, src_stride, width, height, ref0, ref0_stride, ref1, ref1_stride, dst, dst_stride, jobs, njobs, results)) return SVT_HIP_ERR_BAD_ARG;
+    ifs::search_host(pix_bytes, bd, src, src_stride, ref0, ref0_stride, ref1, ref1_stride, dst, dst_stride, jobs, njobs, results, cand);
     return SVT_HIP_OK;
 }
 

@@ -70,6 +70,9 @@ int svt_hip_launch_obmc_search(hipStream_t st, const uint8_t* ref, int stride, i
 int svt_hip_launch_compound_search(hipStream_t st, int pix_bytes, int bd, const void* src, int stride, const void* pred, const int32_t* rates, const uint8_t* masks,
                                    const double* rate_grid, const double* dist_grid, const int32_t* bsize_cat, const SvtHipCompSearchJob* jobs, int njobs,
                                    SvtHipCompSearchResult* results, SvtHipCompSearchCand* cands);
+/* ifs_search.hip; the arithmetic both sides share is ifs_search.h.  Every pointer is device memory (ref1, dst and cands may be NULL); the jobs have passed ifs::job_ok */
+int svt_hip_launch_ifs_search(hipStream_t st, int pix_bytes, int bd, const void* src, int src_stride, const void* ref0, int ref0_stride, const void* ref1, int ref1_stride,
+                              void* dst, int dst_stride, const SvtHipIfsJob* jobs, int njobs, SvtHipIfsResult* results, SvtHipIfsCand* cands);
 /* conv.hip */
 int svt_hip_launch_subpel_jobs_from_me(hipStream_t st, const uint32_t* mv, int sb_cols, int w, int h, const uint8_t* frac, SvtHipConvBlk* out);
 int svt_hip_launch_subpel_predict(hipStream_t st, int pix_bytes, int bd, const void* ref, int ref_stride, void* dst, int dst_stride,
